@@ -10,19 +10,28 @@ Workload (BASELINE.json):
   N = 1   configs[2]: batch 65536, nx=12 nu=4 ny=4, Hp=30 Hc=10, hard umin/umax, soft ymax ("C3").
   N > 1   configs[3]: the same shapes, GLOBAL batch 262144 split into contiguous index ranges over the
           ranks (32768 per GPU at N = 8; `sharding.shard_range`, the rule of mpcqp_multi_create) with no
-          collective on the data path -- `"scaling": "strong"`; the weak-scaling figure (65536
-          controllers per GPU, global 65536 N) is measured in the same run and reported under
+          collective on the data path -- `"scaling": "strong"`; with `--full` the weak-scaling figure
+          (65536 controllers per GPU, global 65536 N) is measured in the same run and reported under
           `config.weak_scaling`.  `--mode weak` makes the weak run the headline instead.
-After the timed region the ranks gather status and first moves of the whole batch with ONE all_gather
-each over RCCL, and one period's inputs born on rank 0 are scattered to the ranks with ONE scatter each (the
-scatter/gather of the north star; both are outside the step and timed separately: config.scatter / config.gather).
+With `--full`, after the timed region the ranks gather status and first moves of the whole batch with ONE
+all_gather each over RCCL, and one period's inputs born on rank 0 are scattered to the ranks with ONE scatter each
+(the scatter/gather of the north star; both are outside the step and timed separately: config.scatter / config.gather).
 
 `--config C5` runs BASELINE configs[4] instead (linear MovingHorizonEstimator, one estimator period per
 step): see bench_mhe.py.
 
 Prints ONE JSON line (rank 0) with `roofline` (FP64 flops of the dominant kernel k_step against the
-chip's FP64 peak, kernel time from HIP events on the launch stream) and `cpu_baseline` (the oracle's C
-port on the host cores, bounded sample, rank 0 at N = 1 only).
+chip's FP64 peak, kernel time from HIP events on the launch stream of the timed steps).
+
+A plain run sets up, warms up, times the K steps and prints that line.  Everything else is measured only
+with `--full`: `cpu_baseline` (the oracle's C port on the host cores, bounded sample, rank 0 at N = 1
+only), `config.secondary` (the other single-GPU configurations), the re-condensation, closed-loop and
+end-to-end timings, the active rows of the optimum and, at N > 1, the weak-scaling run, the scatter and
+the gather.
+
+`--dump-outputs DIR` writes what the last timed step returned (rank 0's shard) as DIR/<name>.npy in
+float64 (`dump_outputs`: at most 64 MB, else a fixed seeded sample of the batch rows, whose indices go
+to DIR/sample_rows.npy).
 """
 from __future__ import annotations
 
@@ -105,6 +114,27 @@ class Shard:
 
 
 COLL_DEVICE = [None]      # device of the collectives when it is not the shard's GPU (MPCQP_BENCH_ONE_GPU)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, seed=0):
+    """arrays: name -> array (torch or NumPy) whose first axis is the batch.  Each goes to path/<name>.npy as float64.
+    When they would exceed DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of batch rows (sorted, ascending) is
+    kept of every array, and its indices are written as path/sample_rows.npy."""
+    arrs = {}
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        arrs[name] = a.astype(np.float64, copy=False)
+    B = min(a.shape[0] for a in arrs.values())
+    row_bytes = sum(a[:1].nbytes for a in arrs.values())
+    os.makedirs(path, exist_ok=True)
+    if row_bytes * B > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 8 * B) // row_bytes)
+        rows = np.sort(np.random.default_rng(seed).choice(B, size=keep, replace=False))
+        arrs = {name: a[rows] for name, a in arrs.items()}
+        np.save(os.path.join(path, "sample_rows.npy"), rows.astype(np.float64))
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def timed_run(sh, steps, warmup, dist):
@@ -149,6 +179,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-secondary", action="store_true", help="skip the C2 / C5 records of config.secondary")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baseline, config.secondary, re-condensation, "
+                         "closed loop, end to end, active rows; N > 1: weak-scaling run, scatter and gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0's shard) as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -183,7 +218,10 @@ def main():
         # the linear MovingHorizonEstimator (BASELINE configs[4]) -- bench_mhe.py
         import bench_mhe
         args.config = args.config[4:] if args.config.startswith("mhe:") else args.config
-        bench_mhe.run(args, rank, world, local, dist)
+        outputs = {} if args.dump_outputs else None
+        bench_mhe.run(args, rank, world, local, dist, outputs=outputs)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, outputs, args.seed)
         if dist is not None:
             dist.barrier()
             dist.destroy_process_group()
@@ -202,6 +240,8 @@ def main():
     sh = Shard(cfg, lo, B, args.seed, local)
     hd = sh.hd
     elapsed, kern_ms = timed_run(sh, args.steps, args.warmup, dist)
+    if args.dump_outputs and rank == 0:        # what mpcqp_step_device returned in the last timed step
+        dump_outputs(args.dump_outputs, {"Z": sh.t_Z, "u0": sh.t_u0, "status": sh.t_st, "iters": sh.t_it}, args.seed)
 
     status = sh.t_st.cpu().numpy()
     iters = sh.t_it.cpu().numpy()
@@ -214,7 +254,7 @@ def main():
 
     # the gather of the north star (outside the step): status and first moves of the whole batch on every rank
     gather = None
-    if dist is not None:
+    if dist is not None and args.full:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         st_all = sharding.gather(sh.t_st, Bglobal, dist, device=args.coll_device)
@@ -227,7 +267,7 @@ def main():
     # ... and the scatter: one period's inputs (x̂0, lastu0, ry of the whole batch) born on rank 0 reach the ranks as their
     # slices, ONE scatter collective per array; checked against the shard every rank generated itself
     scatter = None
-    if dist is not None:
+    if dist is not None and args.full:
         from mpcqp import synth as _synth
         whole = _synth.make_batch(cfg, Bglobal, seed=args.seed) if rank == 0 else None
         dev_c = args.coll_device
@@ -246,7 +286,7 @@ def main():
 
     # weak-scaling figure next to the config-4 run
     weak = None
-    if strong:
+    if strong and args.full:
         shw = Shard(cfg, rank * PER_GPU, PER_GPU, args.seed, local)
         ew, _ = timed_run(shw, args.steps, args.warmup, dist)
         weak = {"batch_per_gpu": PER_GPU, "global_batch": PER_GPU * world, "value": PER_GPU * world * args.steps / ew,
@@ -254,15 +294,17 @@ def main():
         del shw
 
     # setmodel! path (K1 + K2 re-condensation of all models), reported next to the step time
-    hd.recondense_device(stream=sh.stream.cuda_stream)
-    torch.cuda.synchronize()
-    recond_ms, k1_ms = hd.last_condense_ms(), hd.last_predmat_ms()
+    recond_ms = k1_ms = None
+    if args.full:
+        hd.recondense_device(stream=sh.stream.cuda_stream)
+        torch.cuda.synchronize()
+        recond_ms, k1_ms = hd.last_condense_ms(), hd.last_predmat_ms()
 
     # resident closed loop: Kalman correction + moveinput! + Kalman prediction of one period in ONE launch
     # (mpcqp_loop_device); x̂0, u stay in HBM, the measurement is synthetic noise, the gain a synthetic
     # (B, nx̂, ny) array -- the arithmetic of a period does not depend on their values
     loop = None
-    if world == 1:
+    if world == 1 and args.full:
         rg = np.random.default_rng(1)
         hd.kf_set(np.ascontiguousarray(0.05 * rg.standard_normal((B, cfg.ny, cfg.nxh))), np.arange(cfg.ny))
         t_y = torch.from_numpy(0.1 * rg.standard_normal((B, cfg.ny))).to(sh.dev)
@@ -281,7 +323,7 @@ def main():
 
     # end to end through host pointers (PCIe both ways, pageable NumPy arrays): never the reported value
     e2e_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         Zh = np.zeros((B, hd.nZ))
         hd.step(sh.bt["xhat0"], sh.bt["lastu0"], sh.bt["ry"], Zh)
         t0 = time.perf_counter()
@@ -300,13 +342,15 @@ def main():
         kms, kmed = float(np.mean(kern_ms)), float(np.median(kern_ms))
         achieved = flops * B / (kms * 1e-3) / 1e12
         # rows active at the optimum (rank 0's shard): inputs on a bound, outputs on the soft bound
-        Zr = sh.t_Z.cpu().numpy()
-        nDU = hd.nDU
-        U0 = np.cumsum(Zr[:, :nDU].reshape(B, cfg.Hc, cfg.nu), axis=1) + sh.bt["lastu0"][:, None, :]
-        act_u = (np.abs(U0 - cfg.umax) <= 1e-9) | (np.abs(U0 - cfg.umin) <= 1e-9) if np.isfinite(cfg.umax) else np.zeros_like(U0, bool)
-        soft_on = Zr[:, -1] > 1e-9 if neps else np.zeros(B, bool)
-        active = {"controllers_with_an_active_row": float((act_u.any(axis=(1, 2)) | soft_on).mean()),
-                  "input_rows_on_a_bound": float(act_u.mean()), "controllers_with_slack": float(soft_on.mean())}
+        active = None
+        if args.full:
+            Zr = sh.t_Z.cpu().numpy()
+            nDU = hd.nDU
+            U0 = np.cumsum(Zr[:, :nDU].reshape(B, cfg.Hc, cfg.nu), axis=1) + sh.bt["lastu0"][:, None, :]
+            act_u = (np.abs(U0 - cfg.umax) <= 1e-9) | (np.abs(U0 - cfg.umin) <= 1e-9) if np.isfinite(cfg.umax) else np.zeros_like(U0, bool)
+            soft_on = Zr[:, -1] > 1e-9 if neps else np.zeros(B, bool)
+            active = {"controllers_with_an_active_row": float((act_u.any(axis=(1, 2)) | soft_on).mean()),
+                      "input_rows_on_a_bound": float(act_u.mean()), "controllers_with_slack": float(soft_on.mean())}
         # HBM bytes per launch: counters need rocprofv3 around the process (separate --pmc passes), so this is NOT a
         # measurement of this run but the figure of the committed passes over the same command (scripts/profile_all.sh);
         # traffic_source says which
@@ -326,7 +370,7 @@ def main():
                                   3: "small-problem kernel (four controllers per wavefront)"}[sh.kernel],
                        "value_from_median_step": Bglobal / (kmed * 1e-3) if world == 1 else None,
                        "median_kernel_ms": kmed,
-                       "recondense_ms": recond_ms, "recondense_K1_ms": k1_ms, "recondense_K2_ms": recond_ms - k1_ms,
+                       "recondense_ms": recond_ms, "recondense_K1_ms": k1_ms, "recondense_K2_ms": None if recond_ms is None else recond_ms - k1_ms,
                        "end_to_end_ms": e2e_ms, "active_rows": active, "closed_loop": loop,
                        "weak_scaling": weak, "scatter": scatter, "gather": gather,
                        "sharding": "contiguous index ranges (sharding.shard_range), no collective on the data path"},
@@ -340,10 +384,10 @@ def main():
                                  "W_grad + I W_iter, SURVEY 8(d) structure-exploiting count, I = mean "
                                  "factorisations per solve (interior-point iterations + polish)"},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, args, B)
     # the other single-GPU BASELINE configurations, after the headline's timed region: config.secondary
-    if world == 1 and args.config == "C3" and not args.batch and not args.no_secondary:
+    if world == 1 and args.full and args.config == "C3" and not args.batch and not args.no_secondary:
         del sh, hd
         torch.cuda.empty_cache()
         out["config"]["secondary"] = secondary(args, local)

@@ -71,8 +71,10 @@ class MheShard:
             self.kern_ms.append(self.h.last_ms())
 
 
-def measure(args, rank, world, local, dist, cpu=True):
-    """One benchmark of the estimator period; returns the JSON-able record on rank 0 (None elsewhere)."""
+def measure(args, rank, world, local, dist, cpu=True, full=True, outputs=None):
+    """One benchmark of the estimator period; returns the JSON-able record on rank 0 (None elsewhere).  Without `full`
+    only the timed periods run: no kernel-time periods after them (no `roofline`), no bound check, no CPU baseline.
+    `outputs` (a dict) receives what the last timed period left for a caller: x̂, Z̃, status and iterations."""
     import torch
     from mpcqp import mhe as pm
     from mpcqp import synth
@@ -102,12 +104,15 @@ def measure(args, rank, world, local, dist, cpu=True):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     status, iters = sh.h.get(pm.GET_STATUS), sh.h.get(pm.GET_ITERS)
+    if outputs is not None:
+        outputs.update(xhat=sh.h.get(pm.GET_XHAT0), Ztilde=sh.h.get(pm.GET_ZTILDE), status=status, iters=iters)
     # kernel time of the solve from the handle's HIP events (recorded on the handle's stream around
     # k_mhe_step), measured in extra periods after the timed region so that the timed loop stays asynchronous
     sh.periods += 0
     sh.k = fill
-    for _ in range(min(args.steps, periods - fill)):
-        sh.step(record=True)
+    if full:
+        for _ in range(min(args.steps, periods - fill)):
+            sh.step(record=True)
     n_opt, it_sum = int((status == 0).sum()), float(iters.sum())
     if dist is not None:
         agg = torch.tensor([n_opt, it_sum], dtype=torch.float64, device=args.coll_device)
@@ -118,9 +123,9 @@ def measure(args, rank, world, local, dist, cpu=True):
     mean_it = it_sum / Bglobal
     # (the reported iteration count of an estimator is its last iteration index: factorisations = it + 1)
     flops, w_iter = mhe_flops(cfg, mean_it + 1.0)
-    kms = float(np.mean(sh.kern_ms))
-    achieved = flops * B / (kms * 1e-3) / 1e12
-    Zt = sh.h.get(pm.GET_ZTILDE)
+    kms = float(np.mean(sh.kern_ms)) if full else None
+    achieved = flops * B / (kms * 1e-3) / 1e12 if full else None
+    Zt = sh.h.get(pm.GET_ZTILDE) if full else None
     # HBM bytes per launch from the PMC passes committed under profiles/ (traffic.json: scripts/profile_all.sh +
     # pmc_summary_all.py, the steady-state launch of each variant) and the algorithmic bytes of one period next to them
     traffic, algo = None, None
@@ -144,28 +149,29 @@ def measure(args, rank, world, local, dist, cpu=True):
                                + 2 * cfg.nym * cfg.He * np.isfinite(cfg.vabs)),
                    "ipm_mean_iters": mean_it + 1.0, "optimal_fraction": n_opt / Bglobal,
                    "estimators_on_a_state_bound": float(np.mean(np.abs(Zt[:, :cfg.nxh]).max(axis=1) >= cfg.xabs - 1e-6))
-                   if np.isfinite(cfg.xabs) else None,
+                   if full and np.isfinite(cfg.xabs) else None,
                    "register_columns": sh.h.register_columns(),
                    "kernels_per_period": "k_mhe_cov (correct) + k_mhe_step + k_mhe_cov (predict)"},
-        "roofline": {"bound": "mfma", "kernel": "k_mhe_step", "achieved": achieved, "peak": FP64_PEAK_TFLOPS,
-                     "unit": "TFLOP/s", "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic, "kernel_ms": kms,
-                     "hbm_measured_GBps": (traffic / (kms * 1e-3) / 1e9) if traffic else None,
-                     "algorithmic_bytes_per_period": algo,
-                     "traffic_over_algorithmic": (traffic / B / algo) if (traffic and algo) else None,
-                     "flops_per_solve": flops,
-                     "note": "FP64 vector peak (v_fma_f64; the kernel's blocks are 12 x 12, below the 16 x 16 x 4 MFMA "
-                             "tile, and run on v_fma_f64 + DPP row broadcasts); flops = setup + I W_iter, block "
-                             "tridiagonal count, I = mean factorisations per solve; the window state of a wavefront (~190 KB) "
-                             "streams through HBM: traffic / kernel_ms is the measured HBM rate (peak 8000 GB/s), the "
-                             "limiter of this kernel next to its dependent sweeps"},
     }
-    if world == 1 and cpu and not args.no_cpu_baseline:
+    if full:
+        out["roofline"] = {"bound": "mfma", "kernel": "k_mhe_step", "achieved": achieved, "peak": FP64_PEAK_TFLOPS,
+                           "unit": "TFLOP/s", "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic, "kernel_ms": kms,
+                           "hbm_measured_GBps": (traffic / (kms * 1e-3) / 1e9) if traffic else None,
+                           "algorithmic_bytes_per_period": algo,
+                           "traffic_over_algorithmic": (traffic / B / algo) if (traffic and algo) else None,
+                           "flops_per_solve": flops,
+                           "note": "FP64 vector peak (v_fma_f64; the kernel's blocks are 12 x 12, below the 16 x 16 x 4 MFMA "
+                                   "tile, and run on v_fma_f64 + DPP row broadcasts); flops = setup + I W_iter, block "
+                                   "tridiagonal count, I = mean factorisations per solve; the window state of a wavefront (~190 KB) "
+                                   "streams through HBM: traffic / kernel_ms is the measured HBM rate (peak 8000 GB/s), the "
+                                   "limiter of this kernel next to its dependent sweeps"}
+    if world == 1 and cpu and full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, args)
     return out
 
 
-def run(args, rank, world, local, dist):
-    out = measure(args, rank, world, local, dist)
+def run(args, rank, world, local, dist, outputs=None):
+    out = measure(args, rank, world, local, dist, full=args.full, outputs=outputs)
     if out is not None:
         print(json.dumps(out), flush=True)
 
