@@ -135,8 +135,8 @@ int mpcqp_set_weights(mpcqp_handle h, const double* Mdiag, const double* Ndiag,
  *                            same optimal ΔU; mpcqp_step writes Z̃ = [ΔU; ϵ] as always and X̂0 is read with
  *                            mpcqp_get(MPCQP_GET_XHAT_MS).
  * Not every handle can run MultipleShooting: mpcqp_transcription_supported returns 0 when it can, else a bit mask
- * (1 block / dense weight matrices, 2 custom linear constraints, 4 stage data beyond 160 KB of LDS, 8 KEEP_QP / WARM_DUAL
- * flags); a step of an unsupported MultipleShooting handle returns MPCQP_ERR_UNSUPPORTED, and so do mpcqp_prepare and
+ * (1 block / dense weight matrices, 4 stage data beyond 160 KB of LDS, 8 KEEP_QP / WARM_DUAL flags; 2, custom linear
+ * constraints, is kept as a value but no longer set: the stage-structured kernel takes them, every row in one stage); a step of an unsupported MultipleShooting handle returns MPCQP_ERR_UNSUPPORTED, and so do mpcqp_prepare and
  * mpcqp_kernel_kind for it (the Python mirror then keeps the SingleShooting kernels and says so).  The fused Kalman loop
  * (mpcqp_loop_device) runs on the stage-structured kernel too (round 6; MPCQP_ERR_UNSUPPORTED before).
  *
@@ -189,7 +189,9 @@ int mpcqp_set_dense_weights(mpcqp_handle h, const double* M_Hp, const double* N_
  * mpcqp_set_current_setpoint.  nw = 0 removes them.
  * Bounds and softness (default 1, like c_wmin/c_wmax): Wmin, Wmax, C_wmin, C_wmax (nw (Hp+1), B),
  * NULL = absent (±Inf).  Problems with custom constraints run on an on-demand specialisation that has the rows
- * compiled in (mpcqp_prepare after this call) or on the runtime-dimension kernel.                   */
+ * compiled in (mpcqp_prepare after this call) or on the runtime-dimension kernel; under MPCQP_MULTIPLE_SHOOTING, and
+ * for a SingleShooting problem beyond the LDS (see mpcqp_set_transcription), on the stage-structured kernel, which
+ * has its own instantiation with the rows (a handle without them keeps the kernel it had).                    */
 int mpcqp_set_custom_constraints(mpcqp_handle h, int nw, const double* Wy, const double* Wu,
                                  const double* Wd, const double* Wr, const double* w_op);
 int mpcqp_set_custom_bounds(mpcqp_handle h, const double* Wmin, const double* Wmax,

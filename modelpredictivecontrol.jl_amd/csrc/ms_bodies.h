@@ -27,6 +27,20 @@
 // column phi of Phi goes through the same recursion once per factorisation (psi = -Phi^-1 phi) and deps follows from the
 // scalar Schur complement, like the arrow border of the MHE kernel (mhe_bodies.h).
 //
+// Custom linear constraints  wmin <= Wy y^(k+j) + Wu u(k+j) + Wd d^(k+j) + Wr r^(k+j) <= wmax,  j = 0..Hp  (relaxW,
+// construct.jl:1138-1160; linconstraint_custom!, execute.jl:337-364) are written on (xi_j, du_j) with u0(k+j) = v_{j-1} + du_j
+// (a model equation, so the QP is the same): row (j, i) has the variable part g_xi'xi_j + g_u'du_j with g_xi = [C^'Wy_i'; Wu_i']
+// (0 for j = 0: xi_0 is data), g_u = Wu_i' at a free move of step j (else none; none for j = Hp, where u(k+Hp) = u(k+Hp-1)),
+// and a constant part F_w (MsStep::Fw).  Every row lives in ONE stage; what is new is a cross term of xi_t and du_t in the
+// stage Hessian.  With D~ the diagonal of the row weights of step t:
+//     Lam = R_t + Bbar'P Bbar + G_u'D~ G_u   (dense nu x nu),     K_t = -Lam^-1 (Bbar'P Abar + G_u'D~ G_xi)
+//     P_t = Acl'P_{t+1} Acl + Q_t + K'R_t K + (G_xi + G_u K)'D~ (G_xi + G_u K)      (Joseph form: still a sum of PSD terms)
+// and a step without a free move (and step Hp) adds G_xi'D~ G_xi to Q.  The vector recursions keep their form: with the
+// new K, (S_xu + Abar'P Bbar) + K'Lam = 0 removes the k_t terms from p_t, so p_t = g_xi + Abar'w + K'(g_u + Bbar'w) as
+// before; the adjoint pass adds the cross term to the state rows, nu+_t += G_xi'D~ (G_xi dxi_t + G_u du_t).  The rows enter
+// G' (MsStep::Gt_apply), the slack border phi and the row loops (residuals, polish) through MsStep::wrow.  The custom-row
+// code is compiled only into the kernels of handles that have such rows (template flag HAS_W).
+//
 // Written against the wave interface W of mpcqp_bodies.h (gfx950: DevWave; tests/emu: 64 host threads).
 #pragma once
 #include <math.h>
@@ -74,7 +88,9 @@ struct MsIO {
     int* next;        // work counter of the persistent grid (HBM placement)
 };
 
-enum { MS_UMIN = 0, MS_UMAX, MS_DUMIN, MS_DUMAX, MS_YMIN, MS_YMAX, MS_XMIN, MS_XMAX, MS_EPS, MS_NGROUP };
+// (the custom rows come after the slack row: a handle without them keeps the groups, and the code, it had before them)
+enum { MS_UMIN = 0, MS_UMAX, MS_DUMIN, MS_DUMAX, MS_YMIN, MS_YMAX, MS_XMIN, MS_XMAX, MS_EPS, MS_NGROUP,
+       MS_WMIN = MS_NGROUP, MS_WMAX, MS_NGROUP_W };
 constexpr int MS_NROWARR = 8;     // h, s, lam, rp, gd, pp, cs, wi
 
 struct MsCarve {
@@ -95,8 +111,11 @@ struct MsCarve {
     int P, K, Li, Lm, pv, kk;               // factor data the sweeps read: P_{t+1} c_t [Hp][ns], K_t [Hc][nu][ns], Lam^-1, Lam [Hc][nu][nu] (pv, kk: unused)
     int S, T, wv, av, Pl, Pl2, Kl, Ll, Lml, pl, xl, kkl, ul, stg;   // stage work in LDS: S, T (ns x ns), w, a (ns), P_{t+1} / P_t, K_t, Lam^-1, Lam, sweep carries
     int x0, lu;                         // x^0(k), u0(k-1)
+    int Wy, Wu, WC, Hw, sDw, wsc;       // custom rows: Wy [nw][ny], Wu [nw][nu], Wy C^ [nw][nx], stage rows h_i [nw][ns], D~ of the
+                                        // stage's rows [nw], adjoint scratch [nw + ns]  (always in LDS)
+    int DW;                             // custom rows: D~ of every row [nW] (horizon-long)
     int rows[MS_NROWARR];
-    int rowoff[MS_NGROUP + 1];
+    int rowoff[MS_NGROUP_W + 1];
     int jl, ctrl;                       // int tables: first step of block j [Hc+1]; block that starts at step t or -1 [Hp]
     int nrows, total;
     int small, big;                     // doubles of the always-in-LDS block / of the horizon-long data
@@ -109,6 +128,7 @@ MPCQP_HD inline int ms_group_count(const Dims& d, int g) {
         case MS_DUMIN: case MS_DUMAX: return d.nDU;
         case MS_YMIN: case MS_YMAX: return d.nY;
         case MS_XMIN: case MS_XMAX: return d.nxh;
+        case MS_WMIN: case MS_WMAX: return d.nW;
         default: return 1;
     }
 }
@@ -122,10 +142,14 @@ MPCQP_HD inline bool ms_group_on(const Dims& d, const Model& m, int g) {
         case MS_YMAX: return m.Y0max != nullptr;
         case MS_XMIN: return m.x0min != nullptr;
         case MS_XMAX: return m.x0max != nullptr;
+        case MS_WMIN: return d.nw > 0 && m.Wmin != nullptr;
+        case MS_WMAX: return d.nw > 0 && m.Wmax != nullptr;
         default: return d.neps != 0;
     }
 }
 
+// HAS_W = false: the carve of a handle without custom rows (the kernels instantiated for d.nw == 0 never look at them)
+template <bool HAS_W = true>
 MPCQP_HD inline MsCarve make_ms_carve(const Dims& d, const Model& m) {
     MsCarve c{};
     const int nx = d.nxh, nu = d.nu, ny = d.ny, ns = nx + nu, Hp = d.Hp, Hc = d.Hc;
@@ -142,6 +166,11 @@ MPCQP_HD inline MsCarve make_ms_carve(const Dims& d, const Model& m) {
     c.x0 = take(nx); c.lu = take(nu);
     c.jl = take((Hc + 2) / 2 + 1);
     c.ctrl = take((Hp + 1) / 2 + 1);
+    const bool wr = HAS_W && d.nw > 0;
+    if (wr) {
+        const int nw = d.nw;
+        c.Wy = take(nw * ny); c.Wu = take(nw * nu); c.WC = take(nw * nx); c.Hw = take(nw * ns); c.sDw = take(nw); c.wsc = take(nw + ns);
+    }
     c.small = o;
     // -- the horizon-long data (offsets from the "big" base): behind the small block in LDS when everything fits a share
     //    of the LDS that keeps eight wavefronts per CU resident, else in a per-wavefront scratch in HBM (make_ms_carve's
@@ -163,20 +192,22 @@ MPCQP_HD inline MsCarve make_ms_carve(const Dims& d, const Model& m) {
     c.P = take(Hp * ns);                 // the vectors P_{t+1} c_t of the iterate's defects: all the sweeps need of the cost-to-go
     c.K = take(Hc * nu * ns); c.Li = take(Hc * nu * nu); c.Lm = take(Hc * nu * nu); c.pv = take(0); c.kk = take(0);
     int r = 0;
-    for (int g = 0; g < MS_NGROUP; ++g) {
+    for (int g = 0; g < (wr ? MS_NGROUP_W : MS_NGROUP); ++g) {
         c.rowoff[g] = r;
         if (ms_group_on(d, m, g)) r += ms_group_count(d, g);
     }
-    c.rowoff[MS_NGROUP] = r;
+    for (int g = wr ? MS_NGROUP_W : MS_NGROUP; g <= MS_NGROUP_W; ++g) c.rowoff[g] = r;
     c.nrows = r;
     for (int a = 0; a < MS_NROWARR; ++a) c.rows[a] = take(r);
+    if (wr) c.DW = take(d.nW);
     c.big = o;
     c.big_in_lds = (size_t)(c.small + c.big) * sizeof(double) <= MPCQP_MS_LDS_SHARE;
     c.total = c.small + (c.big_in_lds ? c.big : 0);      // doubles of LDS per wavefront
     return c;
 }
 
-template <class W>
+// HAS_W: the handle has custom rows (d.nw > 0); false compiles the kernel of a handle without them, unchanged
+template <class W, bool HAS_W = false>
 struct MsStep {
     W& w;
     double* bg;         // base of the horizon-long data: LDS behind the small block, or this wavefront's HBM scratch
@@ -199,7 +230,7 @@ struct MsStep {
     // of this controller, or null (diagonal Mdiag)
     MPCQP_HD const double* Mblk_() const { return m.Mblk ? m.Mblk + (size_t)b * d.Hp * d.ny * d.ny : nullptr; }
     MPCQP_HD MsStep(W& w_, const Dims& d_, const Model& m_, const StepIO& io_, int b_, double* sm_, double* big_)
-        : w(w_), bg(big_), d(d_), m(m_), io(io_), b(b_), sm(sm_), c(make_ms_carve(d_, m_)), nx(d_.nxh), nu(d_.nu), ny(d_.ny), nd(d_.nd),
+        : w(w_), bg(big_), d(d_), m(m_), io(io_), b(b_), sm(sm_), c(make_ms_carve<HAS_W>(d_, m_)), nx(d_.nxh), nu(d_.nu), ny(d_.ny), nd(d_.nd),
           ns(d_.nxh + d_.nu), Hp(d_.Hp), Hc(d_.Hc), nDU(d_.nDU), nY(d_.nY), nXt(d_.nxh * d_.Hp), nVt(d_.nu * d_.Hp),
           npk((d_.nxh + d_.nu) * (d_.nxh + d_.nu + 1) / 2) {
         jlt = reinterpret_cast<int*>(sm + c.jl);
@@ -224,6 +255,10 @@ struct MsStep {
     // softness of row k of group g (reference defaults: 0 for u and du, 1 for y and x^end; construct.jl:909-913)
     MPCQP_HD double softness(int g, int k) const {
         if (!d.neps) return 0.0;
+        if constexpr (HAS_W) {          // custom rows: default 1 (construct.jl:909-913, as the condensed kernels)
+            if (g == MS_WMIN) return m.C_wmin ? m.C_wmin[(size_t)b * d.nW + k] : 1.0;
+            if (g == MS_WMAX) return m.C_wmax ? m.C_wmax[(size_t)b * d.nW + k] : 1.0;
+        }
         const double* p = nullptr;
         double def = 0.0;
         size_t n = 0;
@@ -244,7 +279,7 @@ struct MsStep {
     // fn(group, k, row index) for every row slot owned by this lane
     template <class Fn>
     MPCQP_HD void for_rows(Fn fn) {
-        for (int g = 0; g < MS_NGROUP; ++g) {
+        for (int g = 0; g < (HAS_W ? MS_NGROUP_W : MS_NGROUP); ++g) {
             const int r0 = c.rowoff[g], n = c.rowoff[g + 1] - r0;
             for (int k = w.lane; k < n; k += WAVE) fn(g, k, r0 + k);
         }
@@ -262,6 +297,19 @@ struct MsStep {
         for (int t = w.lane; t < Hp; t += WAVE) ctrl[t] = -1;
         for (int i = w.lane; i < nx; i += WAVE) sm[c.x0 + i] = io.xhat0[(size_t)b * nx + i];
         for (int i = w.lane; i < nu; i += WAVE) sm[c.lu + i] = io.lastu0[(size_t)b * nu + i];
+        if constexpr (HAS_W) {      // custom rows: Wy, Wu (ABI (nw, .) column-major) row by row, and Wy C^
+            const int nw = d.nw;
+            const double* gWy = m.Wy + (size_t)b * nw * ny;
+            const double* gWu = m.Wu + (size_t)b * nw * nu;
+            for (int idx = w.lane; idx < nw * ny; idx += WAVE) { const int i = idx / ny, a = idx - i * ny; sm[c.Wy + idx] = gWy[i + nw * a]; }
+            for (int idx = w.lane; idx < nw * nu; idx += WAVE) { const int i = idx / nu, cc = idx - i * nu; sm[c.Wu + idx] = gWu[i + nw * cc]; }
+            for (int idx = w.lane; idx < nw * nx; idx += WAVE) {
+                const int i = idx / nx, k = idx - i * nx;
+                double acc = 0.0;
+                for (int a = 0; a < ny; ++a) acc += gWy[i + nw * a] * gC[a + ny * k];
+                sm[c.WC + idx] = acc;
+            }
+        }
         w.sync();
         if (io.kf_y0m) {
             // fused control period (mpcqp_loop_device, round 6 on this kernel too): the SteadyKalmanFilter correction first
@@ -334,7 +382,13 @@ struct MsStep {
                 }
                 case MS_XMIN: bound = -m.x0min[(size_t)b * nx + k]; break;
                 case MS_XMAX: bound = m.x0max[(size_t)b * nx + k]; break;
-                default: bound = 0.0; break;          // -eps <= 0
+                default:
+                    bound = 0.0;                      // -eps <= 0
+                    if constexpr (HAS_W) {
+                        if (g == MS_WMIN) bound = -m.Wmin[(size_t)b * d.nW + k] + Fw(k);
+                        else if (g == MS_WMAX) bound = m.Wmax[(size_t)b * d.nW + k] - Fw(k);
+                    }
+                    break;
             }
             const bool ok = fabs(bound) < BIG && bound == bound;
             rh[r] = ok ? bound : 2.0 * BIG;
@@ -347,6 +401,43 @@ struct MsStep {
         nh = 1.0 + w.maxv(hmax);
         w.sync();
     }
+
+    // Constant part F_w of custom row k = (j, i), j = 0..Hp, in stage form (linconstraint_custom!, execute.jl:337-364; the
+    // condensed kernels' Fw_at with the MultipleShooting prediction offset): the output term is D^d d^0(k+j) for j >= 1 (the
+    // C^ x^0(k+j) part is the variable X^0) and y^0(k) = C^ x^0 + D^d d0 for j = 0; the input term is u0(k-1) for j = 0 only
+    // (u0(k+j) = v_{j-1} + du_j is a variable for j >= 1); plus w_op and the Wd, Wr terms (r^e(k) = ry(k): ry_now).
+    MPCQP_HD double Fw(int k) const {
+        const int nw = d.nw, t = k / nw, i = k - t * nw;
+        const bool rconst = d.flags & 1u;
+        const double* x0 = sm + c.x0;
+        double acc = m.w_op ? m.w_op[(size_t)b * nw + i] : 0.0;
+        for (int a = 0; a < ny; ++a) {
+            double ye = 0.0;
+            if (t == 0)
+                for (int kk = 0; kk < nx; ++kk) ye += Cm[a + ny * kk] * x0[kk];
+            for (int e = 0; e < nd; ++e)
+                ye += m.Dd[(size_t)b * ny * nd + a + ny * e] * (t == 0 ? io.d0[(size_t)b * nd + e] : io.Dhat0[(size_t)b * d.nD + (t - 1) * nd + e]);
+            acc += sm[c.Wy + i * ny + a] * ye;
+            if (m.Wr) {
+                const int tr = t == 0 ? 0 : t - 1;
+                const double re = rconst ? io.Ry[(size_t)b * ny + a]
+                                  : (t == 0 && m.ry_now) ? m.ry_now[(size_t)b * ny + a]
+                                                         : io.Ry[(size_t)b * d.nY + tr * ny + a];
+                acc += m.Wr[(size_t)b * nw * ny + i + nw * a] * re;
+            }
+        }
+        if (t == 0)
+            for (int cc = 0; cc < nu; ++cc) acc += sm[c.Wu + i * nu + cc] * sm[c.lu + cc];
+        if (m.Wd && nd > 0)
+            for (int e = 0; e < nd; ++e) {
+                const double de = t == 0 ? io.d0[(size_t)b * nd + e] : io.Dhat0[(size_t)b * d.nD + (t - 1) * nd + e];
+                acc += m.Wd[(size_t)b * nw * nd + i + nw * e] * de;
+            }
+        return acc;
+    }
+
+    // coefficient of custom row i on component k of the stage state xi_j = [x^0(k+j); u0(k+j-1)] (j >= 1): [Wy C^, Wu]
+    MPCQP_HD double gxi(int i, int k) const { return k < nx ? sm[c.WC + i * nx + k] : sm[c.Wu + i * nu + (k - nx)]; }
 
     // ---- model operators ---------------------------------------------------------------------------------
     // state of stage t (t = -1: the given x^0(k), u0(k-1); directions: zero)
@@ -382,6 +473,10 @@ struct MsStep {
 
     // (G z)[row] without the slack column, from the stage variables (CXv = C^ Xv)
     MPCQP_HD double prim(int g, int k, const double* Xv, const double* Vv, const double* DUv, const double* CXv, double e) const {
+        if constexpr (HAS_W) {
+            if (g == MS_WMIN) return -wrow(k, Vv, DUv, CXv);
+            if (g == MS_WMAX) return wrow(k, Vv, DUv, CXv);
+        }
         switch (g) {
             case MS_UMIN: return -Vv[k];
             case MS_UMAX: return Vv[k];
@@ -393,6 +488,24 @@ struct MsStep {
             case MS_XMAX: return Xv[(Hp - 1) * nx + k];
             default: return -e;
         }
+    }
+
+    // variable part of custom row k = (j, i): Wy C^ x^0(k+j) + Wu (v_{j-1} + du_j) for 1 <= j < Hp (du_j: a free move at
+    // step j, else 0), Wu du_0 for j = 0, Wy C^ x^0(k+Hp) + Wu v_{Hp-1} for j = Hp (u(k+Hp) = u(k+Hp-1), relaxW).  The row is
+    // written on (xi_j, du_j) instead of on u0(k+j) = v_j: the same QP (v_j = v_{j-1} + du_j is one of the model equations),
+    // and every row then lives in ONE stage of the Riccati recursion.
+    MPCQP_HD double wrow(int k, const double* Vv, const double* DUv, const double* CXv) const {
+        const int nw = d.nw, j = k / nw, i = k - j * nw;
+        const double* Wy = sm + c.Wy + i * ny;
+        const double* Wu = sm + c.Wu + i * nu;
+        double acc = 0.0;
+        if (j > 0) {
+            for (int a = 0; a < ny; ++a) acc += Wy[a] * CXv[(j - 1) * ny + a];
+            for (int cc = 0; cc < nu; ++cc) acc += Wu[cc] * Vv[(j - 1) * nu + cc];
+        }
+        if (j < Hp && ctrl[j] >= 0)
+            for (int cc = 0; cc < nu; ++cc) acc += Wu[cc] * DUv[ctrl[j] * nu + cc];
+        return acc;
     }
 
     // gX, gV, gDU (+ returned slack entry) <- G' wv(row) summed onto `base` gradients (which may be null = 0):
@@ -409,6 +522,8 @@ struct MsStep {
         eacc = w.sum(eacc);
         w.sync();
         auto rowv = [&](int g, int k) { return on(g) ? rgd[c.rowoff[g] + k] : 0.0; };
+        // custom rows: G' reaches xi_j through [Wy C^, Wu]' and du_j through Wu' (wrow)
+        auto rww = [&](int j, int i) { return rowv(MS_WMAX, j * d.nw + i) - rowv(MS_WMIN, j * d.nw + i); };
         // outputs: C^'(tYmax - tYmin) (+ cost gradient 2 M (C^ x - ry))
         for (int i = w.lane; i < nXt; i += WAVE) {
             const int t = i / nx, k = i - t * nx;
@@ -416,6 +531,8 @@ struct MsStep {
             for (int a = 0; a < ny; ++a) {
                 const int r = t * ny + a;
                 double ty = rowv(MS_YMAX, r) - rowv(MS_YMIN, r);
+                if constexpr (HAS_W)
+                    for (int ii = 0; ii < d.nw; ++ii) ty += sm[c.Wy + ii * ny + a] * rww(t + 1, ii);
                 if (with_cost) {
                     if (const double* Mb = Mblk_()) {
                         for (int a2 = 0; a2 < ny; ++a2)
@@ -432,11 +549,19 @@ struct MsStep {
         for (int i = w.lane; i < nVt; i += WAVE) {
             double acc = rowv(MS_UMAX, i) - rowv(MS_UMIN, i);
             if (with_cost) acc += 2.0 * m.Ldiag[(size_t)b * d.nU + i] * (bg[c.V + i] - bg[c.ru + i]);
+            if constexpr (HAS_W) {
+                const int t = i / nu, cc = i - t * nu;
+                for (int ii = 0; ii < d.nw; ++ii) acc += sm[c.Wu + ii * nu + cc] * rww(t + 1, ii);
+            }
             oV[i] = acc;
         }
         for (int i = w.lane; i < nDU; i += WAVE) {
             double acc = rowv(MS_DUMAX, i) - rowv(MS_DUMIN, i);
             if (with_cost) acc += 2.0 * m.Ndiag[(size_t)b * nDU + i] * bg[c.DU + i];
+            if constexpr (HAS_W) {
+                const int jj = i / nu, cc = i - jj * nu, ts = jlt[jj];
+                for (int ii = 0; ii < d.nw; ++ii) acc += sm[c.Wu + ii * nu + cc] * rww(ts, ii);
+            }
             oDU[i] = acc;
         }
         w.sync();
@@ -545,6 +670,13 @@ struct MsStep {
             } else if (i == j) {
                 acc = bg[c.QV + t * nu + (i - nx)];
             }
+            if constexpr (HAS_W) {
+                // custom rows of step t + 1 without a free move (and of step Hp): g_xi' D~ g_xi.  (Those with a free move
+                // enter P through the Joseph form of factor(), with the gain.)
+                const int js = t + 1;
+                if (js == Hp || ctrl[js] < 0)
+                    for (int ii = 0; ii < d.nw; ++ii) acc += bg[c.DW + js * d.nw + ii] * gxi(ii, i) * gxi(ii, j);
+            }
             Pt[idx] += acc;
         }
     }
@@ -596,6 +728,7 @@ struct MsStep {
         double* K = sm + c.Kl;
         double* Li = sm + c.Ll;
         double* Lm = sm + c.Lml;
+        const double* sD = sm + c.sDw;  // D~ of the custom rows of the stage in flight
         bool ok = true;
         for (int i = w.lane; i < ns * ns; i += WAVE) Pa[i] = 0.0;
         w.sync_lds();
@@ -604,6 +737,8 @@ struct MsStep {
         for (int t = Hp - 1; t >= 0; --t) {
             // stage t maps xi_t (stored at t-1; given for t = 0) to xi_{t+1} (stored at t)
             const int j = ctrl[t];
+            if constexpr (HAS_W)        // D~ of the custom rows of step t (the fence behind the next product covers it)
+                if (j >= 0) for (int i = w.lane; i < d.nw; i += WAVE) sm[c.sDw + i] = bg[c.DW + t * d.nw + i];
             // P_{t+1} c_t for the sweeps (c: the defects of the iterate, the same for every solve of this iteration)
             for (int i = w.lane; i < ns; i += WAVE) {
                 double acc = 0.0;
@@ -629,11 +764,25 @@ struct MsStep {
                 for (int idx = w.lane; idx < nu * nu; idx += WAVE) {
                     const int a = idx / nu, e = idx - a * nu;
                     // (symmetrised: the two triangles of Bbar'P Bbar differ by rounding)
-                    const double v = 0.5 * (S[a * ns + nx + e] + S[e * ns + nx + a]) + (a == e ? bg[c.RD + j * nu + a] : 0.0);
+                    double v = 0.5 * (S[a * ns + nx + e] + S[e * ns + nx + a]) + (a == e ? bg[c.RD + j * nu + a] : 0.0);
+                    if constexpr (HAS_W)               // + Wu' D~ Wu of the custom rows of step t (dense nu x nu)
+                        for (int ii = 0; ii < d.nw; ++ii) v += sm[c.Wu + ii * nu + a] * sD[ii] * sm[c.Wu + ii * nu + e];
                     Li[idx] = v;
                     Lm[idx] = v;
                 }
                 w.sync_lds();
+                if constexpr (HAS_W) {
+                    // S_u. += Wu' D~ g_xi of the custom rows of step t (g_xi = 0 for t = 0: xi_0 is data), so that
+                    // K_t = -Lam^-1 (Bbar'P Abar + Wu' D~ g_xi); entry by entry in place (the fences of invert_spd order it
+                    // before the gain reads S)
+                    if (t > 0)
+                        for (int idx = w.lane; idx < nu * ns; idx += WAVE) {
+                            const int a = idx / ns, col = idx - a * ns;
+                            double acc = 0.0;
+                            for (int ii = 0; ii < d.nw; ++ii) acc += sm[c.Wu + ii * nu + a] * sD[ii] * gxi(ii, col);
+                            S[idx] += acc;
+                        }
+                }
                 ok = invert_spd(Li) && ok;
                 for (int idx = w.lane; idx < nu * ns; idx += WAVE) {          // K = -Lam^-1 S_u.
                     const int a = idx / ns, col = idx - a * ns;
@@ -679,6 +828,15 @@ struct MsStep {
                     }
                     S[idx] = acc;
                 }
+                if constexpr (HAS_W) {          // rows h_i = g_xi_i' + Wu_i K of the custom rows of step t (closed loop)
+                    double* Hw = sm + c.Hw;
+                    for (int idx = w.lane; idx < d.nw * ns; idx += WAVE) {
+                        const int ii = idx / ns, col = idx - ii * ns;
+                        double acc = gxi(ii, col);
+                        for (int e = 0; e < nu; ++e) acc += sm[c.Wu + ii * nu + e] * K[e * ns + col];
+                        Hw[idx] = acc;
+                    }
+                }
                 w.sync_lds();
                 {
                     double* T = sm + c.T;
@@ -692,10 +850,21 @@ struct MsStep {
                     for (int e = w.lane; e < nu; e += WAVE) sm[c.wv + e] = Rd[e];         // (R of the stage into LDS: read per k)
                     w.sync_lds();
                     const double* Rl = sm + c.wv;
-                    mm(ns, ns, ns + nu, true,
-                       [&](int i, int k) { return k < ns ? S[k * ns + i] : K[(k - ns) * ns + i] * Rl[k - ns]; },
-                       [&](int k, int jj) { return k < ns ? T[k * ns + jj] : K[(k - ns) * ns + jj]; },
-                       [&](int i, int jj, double v) { Pn[i * ns + jj] = v; Pn[jj * ns + i] = v; });
+                    if constexpr (HAS_W) {
+                        // ... + sum_i D~_i h_i' h_i: the custom rows of step t, one more term of the same sum (inner index
+                        // ns + nu .. ns + nu + nw)
+                        const double* Hw = sm + c.Hw;
+                        const int n2 = ns + nu;
+                        mm(ns, ns, n2 + d.nw, true,
+                           [&](int i, int k) { return k < ns ? S[k * ns + i] : k < n2 ? K[(k - ns) * ns + i] * Rl[k - ns] : Hw[(k - n2) * ns + i] * sD[k - n2]; },
+                           [&](int k, int jj) { return k < ns ? T[k * ns + jj] : k < n2 ? K[(k - ns) * ns + jj] : Hw[(k - n2) * ns + jj]; },
+                           [&](int i, int jj, double v) { Pn[i * ns + jj] = v; Pn[jj * ns + i] = v; });
+                    } else {
+                        mm(ns, ns, ns + nu, true,
+                           [&](int i, int k) { return k < ns ? S[k * ns + i] : K[(k - ns) * ns + i] * Rl[k - ns]; },
+                           [&](int k, int jj) { return k < ns ? T[k * ns + jj] : K[(k - ns) * ns + jj]; },
+                           [&](int i, int jj, double v) { Pn[i * ns + jj] = v; Pn[jj * ns + i] = v; });
+                    }
                 }
             } else {
                 {
@@ -853,6 +1022,24 @@ struct MsStep {
             copy(sv1, gX + t * nx, nx); copy(sv1 + nx, gV + t * nu, nu);               // g_{t+1}
             copy(sv2, bg + c.QV + t * nu, nu); copy(sv2 + nu, bg + c.QY + t * ny, ny);  // stage Hessian diagonals
             w.sync_lds();
+            if constexpr (HAS_W) {
+                // custom rows of step t + 1: g_xi' D~ (g_xi dxi_{t+1} + Wu du_{t+1}), the cross term of Phi included
+                double* wsc = sm + c.wsc;              // [nw] D~ (G dz) of the rows, [ns] g_xi' of that
+                const int js = t + 1, nw = d.nw, jb = js < Hp ? ctrl[js] : -1;
+                for (int ii = w.lane; ii < nw; ii += WAVE) {
+                    double acc = 0.0;
+                    for (int k = 0; k < ns; ++k) acc += gxi(ii, k) * sv0[k];
+                    if (jb >= 0)
+                        for (int cc = 0; cc < nu; ++cc) acc += sm[c.Wu + ii * nu + cc] * oDU[jb * nu + cc];
+                    wsc[ii] = bg[c.DW + js * nw + ii] * acc;
+                }
+                w.sync_lds();
+                for (int k = w.lane; k < ns; k += WAVE) {
+                    double acc = 0.0;
+                    for (int ii = 0; ii < nw; ++ii) acc += gxi(ii, k) * wsc[ii];
+                    wsc[nw + k] = acc;
+                }
+            }
             if (const double* Mb = Mblk_()) {        // (2 M_t + diag) (C^ dx): C^ dx first, then the block product
                 for (int a = w.lane; a < ny; a += WAVE) {
                     double acc = 0.0;
@@ -885,10 +1072,12 @@ struct MsStep {
                     for (int a = 0; a < ny; ++a) acc += Cm[a + ny * i] * ul[a];
                     if (t == Hp - 1) acc += xterm(i) * sv0[i];
                     for (int k = 0; k < nx; ++k) acc += A[k + nx * i] * na[k];
+                    if constexpr (HAS_W) acc += sm[c.wsc + d.nw + i];
                     nuX[t * nx + i] = acc;
                 } else {
                     const int cc = i - nx;
                     acc = sv1[i] + sv2[cc] * sv0[i];
+                    if constexpr (HAS_W) acc += sm[c.wsc + d.nw + i];
                     for (int k = 0; k < nx; ++k) acc += Bu[k + nx * cc] * na[k];
                     acc += na[i];
                     nuV[t * nu + cc] = acc;
@@ -1116,17 +1305,36 @@ struct MsStep {
         w.sync();
         auto dt_ = [&](int g, int k) { return on(g) ? rgd[c.rowoff[g] + k] : 0.0; };
         auto cs_ = [&](int g, int k) { return on(g) ? rcs[c.rowoff[g] + k] : 0.0; };
+        // custom rows: their D~ (the factorisation and the sweeps read it per step) and their part of phi, G_w' tB_w
+        auto tw_ = [&](int j, int i) { const int k = j * d.nw + i; return cs_(MS_WMIN, k) * dt_(MS_WMIN, k) - cs_(MS_WMAX, k) * dt_(MS_WMAX, k); };
+        if constexpr (HAS_W)
+            for (int k = w.lane; k < d.nW; k += WAVE) bg[c.DW + k] = dt_(MS_WMIN, k) + dt_(MS_WMAX, k);
         for (int r = w.lane; r < nY; r += WAVE) {
             bg[c.QY + r] = (m.Mblk ? 0.0 : 2.0 * m.Mdiag[(size_t)b * nY + r]) + dt_(MS_YMIN, r) + dt_(MS_YMAX, r);   // (block weights: add_Q, sweep)
-            bg[c.CD + r] = cs_(MS_YMIN, r) * dt_(MS_YMIN, r) - cs_(MS_YMAX, r) * dt_(MS_YMAX, r);      // tB of the output rows
+            double cd = cs_(MS_YMIN, r) * dt_(MS_YMIN, r) - cs_(MS_YMAX, r) * dt_(MS_YMAX, r);      // tB of the output rows
+            if constexpr (HAS_W) {
+                const int t = r / ny, a = r - t * ny;
+                for (int ii = 0; ii < d.nw; ++ii) cd += sm[c.Wy + ii * ny + a] * tw_(t + 1, ii);
+            }
+            bg[c.CD + r] = cd;
         }
         for (int r = w.lane; r < nVt; r += WAVE) {
             bg[c.QV + r] = 2.0 * m.Ldiag[(size_t)b * d.nU + r] + dt_(MS_UMIN, r) + dt_(MS_UMAX, r);
-            bg[c.fV + r] = cs_(MS_UMIN, r) * dt_(MS_UMIN, r) - cs_(MS_UMAX, r) * dt_(MS_UMAX, r);
+            double fv = cs_(MS_UMIN, r) * dt_(MS_UMIN, r) - cs_(MS_UMAX, r) * dt_(MS_UMAX, r);
+            if constexpr (HAS_W) {
+                const int t = r / nu, cc = r - t * nu;
+                for (int ii = 0; ii < d.nw; ++ii) fv += sm[c.Wu + ii * nu + cc] * tw_(t + 1, ii);
+            }
+            bg[c.fV + r] = fv;
         }
         for (int r = w.lane; r < nDU; r += WAVE) {
             bg[c.RD + r] = 2.0 * m.Ndiag[(size_t)b * nDU + r] + dt_(MS_DUMIN, r) + dt_(MS_DUMAX, r);
-            bg[c.fDU + r] = cs_(MS_DUMIN, r) * dt_(MS_DUMIN, r) - cs_(MS_DUMAX, r) * dt_(MS_DUMAX, r);
+            double fd = cs_(MS_DUMIN, r) * dt_(MS_DUMIN, r) - cs_(MS_DUMAX, r) * dt_(MS_DUMAX, r);
+            if constexpr (HAS_W) {
+                const int jj = r / nu, cc = r - jj * nu, ts = jlt[jj];
+                for (int ii = 0; ii < d.nw; ++ii) fd += sm[c.Wu + ii * nu + cc] * tw_(ts, ii);
+            }
+            bg[c.fDU + r] = fd;
         }
         for (int k = w.lane; k < nx; k += WAVE) bg[c.XT + k] = dt_(MS_XMIN, k) + dt_(MS_XMAX, k);
         w.sync();
@@ -1455,13 +1663,14 @@ struct MsStep {
 // in LDS behind the small block.  (A template parameter, not a run-time choice: a pointer that may be LDS or HBM is a
 // generic pointer, every access a flat_load / flat_store -- which count on BOTH memory counters, so that not even the
 // LDS-only fences of the stage loops could run ahead of the stores.)
-template <bool IN_HBM, class W>
-MPCQP_HD void ms_step_body(W& w, const Dims& d, const Model& m, const StepIO& io, const MsIO& ms, int b, double* sm, double* scratch) {
+// HAS_W: instantiated for handles with custom rows (d.nw > 0); the kernels choose at launch.
+template <bool IN_HBM, bool HAS_W, class W>
+MPCQP_HD void ms_step_body_t(W& w, const Dims& d, const Model& m, const StepIO& io, const MsIO& ms, int b, double* sm, double* scratch) {
     double* big;
     if constexpr (IN_HBM) big = scratch;
-    else big = sm + make_ms_carve(d, m).small;
-    MsStep<W> st(w, d, m, io, b, sm, big);
-    const long long tp0_ = MsStep<W>::clk();
+    else big = sm + make_ms_carve<HAS_W>(d, m).small;
+    MsStep<W, HAS_W> st(w, d, m, io, b, sm, big);
+    const long long tp0_ = MsStep<W, HAS_W>::clk();
     (void)tp0_;
     st.load();
     st.build_rows();
@@ -1498,13 +1707,20 @@ MPCQP_HD void ms_step_body(W& w, const Dims& d, const Model& m, const StepIO& io
     if (ms.Xhat)
         for (int i = w.lane; i < d.nxh * d.Hp; i += WAVE) ms.Xhat[(size_t)b * d.nxh * d.Hp + i] = st.bg[st.c.X + i];
 #if defined(MPCQP_MS_PROFILE)
-    if (ms.Xhat && w.lane == 0) { st.prof_[7] = (double)(MsStep<W>::clk() - tp0_); for (int i = 0; i < 8; ++i) ms.Xhat[(size_t)b * d.nxh * d.Hp + i] = st.prof_[i]; }
+    if (ms.Xhat && w.lane == 0) { st.prof_[7] = (double)(MsStep<W, HAS_W>::clk() - tp0_); for (int i = 0; i < 8; ++i) ms.Xhat[(size_t)b * d.nxh * d.Hp + i] = st.prof_[i]; }
 #endif
     if (w.lane == 0) {
         io.status[b] = status;
         if (io.iters) io.iters[b] = iters;
         if (ms.defect) ms.defect[b] = defect;
     }
+}
+
+// run-time choice between the two instantiations (the CPU emulator; the gfx950 kernels instantiate one each)
+template <bool IN_HBM, class W>
+MPCQP_HD void ms_step_body(W& w, const Dims& d, const Model& m, const StepIO& io, const MsIO& ms, int b, double* sm, double* scratch) {
+    if (d.nw > 0) ms_step_body_t<IN_HBM, true>(w, d, m, io, ms, b, sm, scratch);
+    else ms_step_body_t<IN_HBM, false>(w, d, m, io, ms, b, sm, scratch);
 }
 
 }  // namespace mpcqp

@@ -16,45 +16,45 @@
 
 namespace mpcqp {
 
+// (custom linear constraints: the _w kernels, instantiated with the rows; a handle without them runs the kernels it ran before)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void k_ms_step(Dims d, Model m, StepIO io, MsIO ms) {
     DevWave w{(int)threadIdx.x};
-    ms_step_body<false>(w, d, m, io, ms, (int)blockIdx.x, mpcqp_smem, (double*)nullptr);
+    ms_step_body_t<false, false>(w, d, m, io, ms, (int)blockIdx.x, mpcqp_smem, (double*)nullptr);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void k_ms_step_w(Dims d, Model m, StepIO io, MsIO ms) {
+    DevWave w{(int)threadIdx.x};
+    ms_step_body_t<false, true>(w, d, m, io, ms, (int)blockIdx.x, mpcqp_smem, (double*)nullptr);
 }
 
 #ifndef MPCQP_MS_WAVES
 #define MPCQP_MS_WAVES 2
 #endif
+// controllers are handed out one at a time (ms.next: a counter in HBM, zeroed before the launch): a solve that runs to
+// its iteration limit (80 iterations against a mean of 13) then delays its own wavefront, not a fixed share of the
+// batch -- with the static assignment b = blockIdx + k gridDim one such controller set the time of the whole launch
+// (measured: 131 ms for 2048 C3 controllers of which one is at the limit, 25 ms of work per wavefront otherwise)
 // (two wavefronts per SIMD: without the attribute the compiler takes 372 registers and leaves one)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MPCQP_MS_WAVES, 8))) void k_ms_step_g(Dims d, Model m, StepIO io, MsIO ms, size_t big) {
     DevWave w{(int)threadIdx.x};
     double* scratch = ms.scratch + (size_t)blockIdx.x * big;
-    // controllers are handed out one at a time (ms.next: a counter in HBM, zeroed before the launch): a solve that runs to
-    // its iteration limit (80 iterations against a mean of 13) then delays its own wavefront, not a fixed share of the
-    // batch -- with the static assignment b = blockIdx + k gridDim one such controller set the time of the whole launch
-    // (measured: 131 ms for 2048 C3 controllers of which one is at the limit, 25 ms of work per wavefront otherwise)
-#ifdef MPCQP_MS_CONST_EXP
-    // (experiment: what compile-time dimensions would buy this kernel -- the bench shape 6,2,2,50,50 with its dimensions as constants)
-    if (d.nxh == 8 && d.nu == 2 && d.ny == 2 && d.Hp == 50 && d.Hc == 50 && d.neps == 1 && d.nd == 0 && d.nw == 0 && d.default_nb == 1) {
-        Dims dc = d;
-        dc.nxh = 8; dc.nu = 2; dc.ny = 2; dc.Hp = 50; dc.Hc = 50; dc.neps = 1; dc.nd = 0; dc.nD = 0; dc.nw = 0; dc.nW = 0;
-        dc.nDU = 100; dc.nZ = 101; dc.nU = 100; dc.nY = 100; dc.default_nb = 1;
-        for (;;) {
-            int b = 0;
-            if (threadIdx.x == 0) b = atomicAdd(ms.next, 1);
-            b = __builtin_amdgcn_readfirstlane(b);
-            if (b >= dc.B) break;
-            ms_step_body<true>(w, dc, m, io, ms, b, mpcqp_smem, scratch);
-            w.sync();
-        }
-        return;
-    }
-#endif
     for (;;) {
         int b = 0;
         if (threadIdx.x == 0) b = atomicAdd(ms.next, 1);
         b = __builtin_amdgcn_readfirstlane(b);
         if (b >= d.B) break;
-        ms_step_body<true>(w, d, m, io, ms, b, mpcqp_smem, scratch);
+        ms_step_body_t<true, false>(w, d, m, io, ms, b, mpcqp_smem, scratch);
+        w.sync();
+    }
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MPCQP_MS_WAVES, 8))) void k_ms_step_gw(Dims d, Model m, StepIO io, MsIO ms, size_t big) {
+    DevWave w{(int)threadIdx.x};
+    double* scratch = ms.scratch + (size_t)blockIdx.x * big;
+    for (;;) {
+        int b = 0;
+        if (threadIdx.x == 0) b = atomicAdd(ms.next, 1);
+        b = __builtin_amdgcn_readfirstlane(b);
+        if (b >= d.B) break;
+        ms_step_body_t<true, true>(w, d, m, io, ms, b, mpcqp_smem, scratch);
         w.sync();
     }
 }
@@ -72,20 +72,21 @@ size_t ms_scratch_bytes(const Dims& d, const Model& m, int* nslots) {
     // so that a step does no runtime queries.
     int dev = 0, cus = 256, per_cu = 0;
     (void)hipGetDevice(&dev);
+    const void* kern = d.nw > 0 ? (const void*)k_ms_step_gw : (const void*)k_ms_step_g;
     {
         static std::mutex mu;
-        static std::map<std::pair<int, size_t>, std::pair<int, int>> seen;
+        static std::map<std::pair<std::pair<int, size_t>, const void*>, std::pair<int, int>> seen;
         std::lock_guard<std::mutex> lock(mu);
-        auto it = seen.find({dev, lds});
+        auto it = seen.find({{dev, lds}, kern});
         if (it == seen.end()) {
             hipDeviceProp_t prop;
             if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-            if (ensure_lds((const void*)k_ms_step_g, lds) != hipSuccess ||
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_ms_step_g, WAVE, lds) != hipSuccess || per_cu < 1) {
+            if (ensure_lds(kern, lds) != hipSuccess ||
+                hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, WAVE, lds) != hipSuccess || per_cu < 1) {
                 per_cu = (int)((160 * 1024) / (lds ? lds : 1));
                 per_cu = per_cu > 8 ? 8 : per_cu < 1 ? 1 : per_cu;
             }
-            it = seen.emplace(std::make_pair(dev, lds), std::make_pair(cus, per_cu)).first;
+            it = seen.emplace(std::make_pair(std::make_pair(dev, lds), kern), std::make_pair(cus, per_cu)).first;
         }
         cus = it->second.first; per_cu = it->second.second;
     }
@@ -98,18 +99,21 @@ size_t ms_scratch_bytes(const Dims& d, const Model& m, int* nslots) {
 hipError_t launch_ms_step(const Dims& d, const Model& m, const StepIO& io, const MsIO& ms, hipStream_t st) {
     const MsCarve c = make_ms_carve(d, m);
     const size_t lds = (size_t)c.total * sizeof(double);
+    const bool hw = d.nw > 0;
     if (c.big_in_lds) {
-        hipError_t e = ensure_lds((const void*)k_ms_step, lds);
+        hipError_t e = ensure_lds(hw ? (const void*)k_ms_step_w : (const void*)k_ms_step, lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ms_step, dim3(d.B), dim3(WAVE), lds, st, d, m, io, ms);
+        if (hw) hipLaunchKernelGGL(k_ms_step_w, dim3(d.B), dim3(WAVE), lds, st, d, m, io, ms);
+        else hipLaunchKernelGGL(k_ms_step, dim3(d.B), dim3(WAVE), lds, st, d, m, io, ms);
     } else {
         if (!ms.scratch || ms.nslots < 1) return hipErrorInvalidValue;
-        hipError_t e = ensure_lds((const void*)k_ms_step_g, lds);
+        hipError_t e = ensure_lds(hw ? (const void*)k_ms_step_gw : (const void*)k_ms_step_g, lds);
         if (e != hipSuccess) return e;
         if (!ms.next) return hipErrorInvalidValue;
         e = hipMemsetAsync(ms.next, 0, sizeof(int), st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ms_step_g, dim3(ms.nslots), dim3(WAVE), lds, st, d, m, io, ms, (size_t)c.big);
+        if (hw) hipLaunchKernelGGL(k_ms_step_gw, dim3(ms.nslots), dim3(WAVE), lds, st, d, m, io, ms, (size_t)c.big);
+        else hipLaunchKernelGGL(k_ms_step_g, dim3(ms.nslots), dim3(WAVE), lds, st, d, m, io, ms, (size_t)c.big);
     }
     return hipGetLastError();
 }
