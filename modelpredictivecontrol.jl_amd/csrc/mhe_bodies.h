@@ -39,15 +39,6 @@
 #ifndef MPCQP_MHE_DEPTH_U
 #define MPCQP_MHE_DEPTH_U 2
 #endif
-#ifndef MPCQP_MHE_EXACT_PIVOT
-#define MPCQP_MHE_EXACT_PIVOT 0
-#endif
-#ifndef MPCQP_MHE_GJ_DEFER
-#define MPCQP_MHE_GJ_DEFER 1     // Gauss-Jordan inverse with the row scalings deferred to the end (Ops::gj)
-#endif
-#ifndef MPCQP_MHE_BMID_LDS
-#define MPCQP_MHE_BMID_LDS 1     // middle diagonal block of the Hessian in LDS (18 KB per wave) or read from the constant block (12 KB)
-#endif
 
 namespace mpcqp {
 namespace mhe {
@@ -129,23 +120,18 @@ struct Ops {
     }
     // in-place inverse of a symmetric positive definite matrix (Gauss-Jordan, no pivoting: the pivots
     // are those of the LDL' factorisation).  Returns false (for the whole group) on a bad pivot.
-    // MPCQP_MHE_GJ_DEFER: the pivot row is NOT divided by its pivot when it is eliminated with -- a row scaling commutes
+    // The pivot row is NOT divided by its pivot when it is eliminated with -- a row scaling commutes
     // with the later eliminations (they see d_k times the scaled row and form d_k times its update) -- so the step is one
     // in-place multiply-add per entry (the pivot lane with factor 0) instead of a multiply and a multiply-add, and every
     // lane scales its row by its own 1/d once at the end: NX^2 + NX instead of 2 NX^2 FP64 instructions per inverse.
     MPCQP_HD bool gj(Row& a, int r) const {
         bool ok = true;
-#if MPCQP_MHE_GJ_DEFER
         double mypinv = 0.0;
         sfor<NX>([&](auto ik) {
             constexpr int k = decltype(ik)::v;
             const double dk = w.template rowbc<k>(a[k]);      // (gjacc4 ends with the wait states a DPP read of its results needs)
             ok = ok && (dk > 1e-280) && (dk < 1e280);
-#if MPCQP_MHE_EXACT_PIVOT
-            const double pinv = 1.0 / dk;
-#else
             const double pinv = recip(dk);
-#endif
             // one = 1 on the pivot lane, 0 elsewhere (a select of the high word only); the three lane-dependent values follow
             // by arithmetic: g = x - one x (exactly 0 on the pivot lane), the lane's own 1/d, the new column k
             const double one = (r == k) ? 1.0 : 0.0;
@@ -160,29 +146,6 @@ struct Ops {
             a[k] = g + one;
         });
         sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; a[c] *= mypinv; });
-#else
-        sfor<NX>([&](auto ik) {
-            constexpr int k = decltype(ik)::v;
-            const double dk = w.template rowbc<k>(a[k]);
-            ok = ok && (dk > 1e-280) && (dk < 1e280);
-#if MPCQP_MHE_EXACT_PIVOT
-            const double pinv = 1.0 / dk;
-#else
-            const double pinv = recip(dk);
-#endif
-            const bool piv = (r == k);
-            // a[c] <- m a[c] + g (a[c] of lane k):  pivot row (m = 0, g = 1/dk): a[c]/dk;  other rows (m = 1,
-            // g = -a[k]/dk): a[c] - a[k] a_k[c] / dk
-            const double g = piv ? pinv : -a[k] * pinv;
-            const double m = piv ? 0.0 : 1.0;
-            // (column k is computed too and then replaced: the four-element groups stay uniform)
-            sfor<NX / 4>([&](auto ij) {
-                constexpr int c = 4 * decltype(ij)::v;
-                w.template gjrow4<k>(a[c], a[c + 1], a[c + 2], a[c + 3], m, g);
-            });
-            a[k] = g;
-        });
-#endif
         return ok;
     }
     MPCQP_HD static void ld(const double* p, int stride, Row& M) {
@@ -484,11 +447,7 @@ struct Solver {
     // diagonal block of the Hessian at stage s
     MPCQP_HD void base_block(int s, Row& Bs) {
         if (s > 0 && s < N) {
-#if MPCQP_MHE_BMID_LDS
             O::ld(L_Bmid(), WAVE, Bs);
-#else
-            O::ldo(w.uniform(cbase + cm.Bmid), coff, RL, Bs);      // once per stage and iteration: not worth LDS
-#endif
             return;
         }
         Row T;
@@ -625,9 +584,7 @@ struct Solver {
             Row T;
             O::ldo(w.uniform(cbase + cm.Oc), coff, RL, T); O::st(lds, WAVE, T);
             O::ldo(w.uniform(cbase + cm.OcT), coff, RL, T); O::st(lds + (size_t)NX * WAVE, WAVE, T);
-#if MPCQP_MHE_BMID_LDS
             O::ldo(w.uniform(cbase + cm.Bmid), coff, RL, T); O::st(lds + (size_t)2 * NX * WAVE, WAVE, T);
-#endif
         }
         auto bnd = [&](const double* p_, bool on, int n, double dflt) { return (on && p_ && r < n && !cL) ? p_[(size_t)b * RL + r] : dflt; };
         xlo = bnd(a.xmin, cX, nx, -BIG); xhi = bnd(a.xmax, cX, nx, BIG);
@@ -1167,7 +1124,8 @@ MPCQP_HD void step_body(W& w, const Dims& d, const Args& a, int wave_id, double*
     }
 }
 
-MPCQP_HD inline size_t step_lds_doubles(int NX) { return (size_t)(MPCQP_MHE_BMID_LDS ? 3 : 2) * NX * WAVE; }
+// LDS per wavefront: Oc, Oc' and the middle diagonal block of the Hessian
+MPCQP_HD inline size_t step_lds_doubles(int NX) { return (size_t)3 * NX * WAVE; }
 
 }  // namespace mhe
 }  // namespace mpcqp

@@ -64,22 +64,6 @@ struct MheDevWave : DevWave {
             : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3)
             : "v"(x), "v"(y0), "v"(y1), "v"(y2), "v"(y3), "n"(L0), "n"(L1), "n"(L2), "n"(L3));
     }
-    // Gauss-Jordan row update of four elements: a_i <- m a_i + g (a_i of lane K)
-    template <int K>
-    __device__ __forceinline__ void gjrow4(double& a0, double& a1, double& a2, double& a3, double m, double g) const {
-        double t0, t1, t2, t3;
-        asm("v_mul_f64 %0, %4, %8\n\t"
-            "v_mul_f64 %1, %5, %8\n\t"
-            "v_mul_f64 %2, %6, %8\n\t"
-            "v_mul_f64 %3, %7, %8\n\t"
-            "v_fmac_f64_dpp %0, %4, %9 row_newbcast:%10 row_mask:0xf bank_mask:0xf\n\t"
-            "v_fmac_f64_dpp %1, %5, %9 row_newbcast:%10 row_mask:0xf bank_mask:0xf\n\t"
-            "v_fmac_f64_dpp %2, %6, %9 row_newbcast:%10 row_mask:0xf bank_mask:0xf\n\t"
-            "v_fmac_f64_dpp %3, %7, %9 row_newbcast:%10 row_mask:0xf bank_mask:0xf"
-            : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
-            : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(m), "v"(g), "n"(K));
-        a0 = t0; a1 = t1; a2 = t2; a3 = t3;
-    }
     // acc -= sum_i (x_i of lane L_i of this lane's row) * y_i (the negation is the source modifier of the multiply-add)
     template <int L0, int L1, int L2, int L3>
     __device__ __forceinline__ void fmsbc4(double& acc, double x0, double x1, double x2, double x3, double y0, double y1,

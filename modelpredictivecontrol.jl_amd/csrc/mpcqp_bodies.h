@@ -59,36 +59,6 @@
 #ifndef MPCQP_POLISH_BUDGET
 #define MPCQP_POLISH_BUDGET 3     // no new polish attempt once this many polish factorisations are spent
 #endif
-// Timing experiments only (wrong results): MPCQP_FIXED_ITERS > 0 runs exactly that many interior-point iterations (no
-// convergence test, no polish); MPCQP_ABLATE is a mask of phases that are skipped (1 E'DE, 2 factorisation, 4 triangular
-// solves, 8 E v, 16 E'w, 32 row passes of the step rules, 64 structured part of G'DG).
-#ifndef MPCQP_FIXED_ITERS
-#define MPCQP_FIXED_ITERS 0
-#endif
-#ifndef MPCQP_ABLATE
-#define MPCQP_ABLATE 0
-#endif
-#ifndef MPCQP_CHOL_REDUNDANT
-#define MPCQP_CHOL_REDUNDANT 0    // 4 x 4 diagonal blocks of the factorisation factored redundantly by every lane (chol_static)
-#endif
-#ifndef MPCQP_CHOL_INVD
-#define MPCQP_CHOL_INVD 0         // how 1/L_kk reaches lane k: 0 select, 1 LDS vector written by lane 0, 2 by every lane
-#endif
-#ifndef MPCQP_CHOL_RMW_BATCH
-#define MPCQP_CHOL_RMW_BATCH 1    // read-modify-writes of the in-panel update / the U rows: all reads first, then all writes
-#endif
-#ifndef MPCQP_CHOL_DIAG
-#define MPCQP_CHOL_DIAG 1         // chol_static: pivot guard by a floor, 1/L_kk from the diagonal slot after the last column
-#endif
-#ifndef MPCQP_FOLD_H
-#define MPCQP_FOLD_H 1            // diagonal weights: the Newton matrix and H~ z are assembled without the packed H~ (Step::fold_H)
-#endif
-#ifndef MPCQP_CHOL_LDL
-#define MPCQP_CHOL_LDL 1          // chol_static / solve_static: Phi = M D M' with unit-triangular M (stored negated), no square roots, no per-solve scaling
-#endif
-#ifndef MPCQP_SOLVE_DPP
-#define MPCQP_SOLVE_DPP 1         // triangular solves of the specialised kernels blocked by DPP rows (Step::solve_static)
-#endif
 #ifndef MPCQP_POLISH_MU
 #define MPCQP_POLISH_MU 1e-7      // complementarity gap at which the first polish attempt is made (then every factor 100); C3, round 5: 1e-4 15.6 ms, 1e-5 15.25, 1e-6 15.05, 1e-7 14.9, 1e-8 14.9, never 15.55 (profiles/r5e)
 #endif
@@ -128,10 +98,7 @@
 // from the Sigma table once per assembly -- serves every tile of every pass: the K loops become a straight stream of v_mul /
 // v_mfma with the row factors d streaming in behind it (NK + NK + (eps row) LDS reads per assembly instead of one per tile
 // column and K step, no address arithmetic, no selects in the loop).  Shapes: ny a multiple of 4, nu a divisor of 16, default
-// move blocking, NK = Hp ny / 4 <= MPCQP_ETDE_VREG_MAX (2 VGPRs per entry).  0: operands from LDS at every K step (rounds 1-5).
-#ifndef MPCQP_ETDE_VREG
-#define MPCQP_ETDE_VREG 1
-#endif
+// move blocking, NK = Hp ny / 4 <= MPCQP_ETDE_VREG_MAX (2 VGPRs per entry).  Other shapes read the operands from LDS at every K step.
 #ifndef MPCQP_ETDE_VREG_MAX
 #define MPCQP_ETDE_VREG_MAX 32
 #endif
@@ -140,42 +107,12 @@
 #endif
 // chunks of four columns per unrolled pass of the several-rows-per-lane substitutions (solve_big_static): the factor entries
 // of a pass are requested together, so one LDS round trip is paid per pass (profiles/r6c: 86 cycles per column at 2)
-#ifndef MPCQP_SOLVEBIG_DPP
-#define MPCQP_SOLVEBIG_DPP 0       // several rows per lane: 1 = substitutions blocked by DPP rows (Step::solve_big_dpp), 0 = column at a time.
-                                   // Measured (profiles/r6u): nZ~ = 106 / 8192 19.30 -> 19.29 ms, nZ~ = 151 / 4096 29.74 -> 29.74 ms, same
-                                   // optima to 1e-10 -- no gain (the loads, the scaling by 1/L_ii and the ds_bpermute of a tile cost what the
-                                   // v_readlane chain did), so the simpler form stays the default
-#endif
 #ifndef MPCQP_SOLVEBIG_UNROLL
 #if defined(MPCQP_STEP_WAVES) && MPCQP_STEP_WAVES == 1
 #define MPCQP_SOLVEBIG_UNROLL 8
 #else
 #define MPCQP_SOLVEBIG_UNROLL 2
 #endif
-#endif
-// Issue priority of the wavefront by phase (s_setprio; two wavefronts share a SIMD's FP64 pipe, a 64-cycle v_mfma_f64 of one
-// holds up the other's next dependent instruction): bit 0 factorisation high, bit 1 triangular solves high, bit 2 everything
-// high except the matrix-core stream of E'DE.  0: no priority changes (rounds 1-5).
-#ifndef MPCQP_PRIO
-#define MPCQP_PRIO 0
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MPCQP_SETPRIO(bit, p) do { if ((MPCQP_PRIO) & (bit)) __builtin_amdgcn_s_setprio(p); } while (0)
-#else
-#define MPCQP_SETPRIO(bit, p) ((void)0)
-#endif
-// teams of three or more wavefronts: 0 keeps wavefront 0 (which carries the row state of the whole problem in registers) out of
-// the matrix-core shares (E'DE passes, panel updates): the helpers split them among themselves.  Measured at nZ~ = 151, four
-// wavefronts, 4096 controllers (profiles/r6h, after the spill of the substitution's relane site was repaired): 31.3 ms with
-// wavefront 0 in, 31.8 ms without
-#ifndef MPCQP_PANELROWS_RL
-#define MPCQP_PANELROWS_RL 0    // rows below a panel's diagonal block (chol_big_panel_rows): 1 = right-looking column steps (measured slower: 29.7 -> 30.4 ms at nZ~ = 151, 19.4 -> 19.5 ms at 106)
-#endif
-#ifndef MPCQP_TEAM_DIAG
-#define MPCQP_TEAM_DIAG 1       // teams of three or more: diagonal block of a panel in its DPP row (Step::chol_big_panel_diag)
-#endif
-#ifndef MPCQP_TEAM_MAIN_MFMA
-#define MPCQP_TEAM_MAIN_MFMA 1
 #endif
 #ifndef MPCQP_HZ_UNROLL
 #define MPCQP_HZ_UNROLL 4         // terms per unrolled pass of the two loops of H~ z (dual_residual)
@@ -195,11 +132,6 @@
 #ifndef MPCQP_ETAPPLY_NB
 #define MPCQP_ETAPPLY_NB 3        // steps per (double-buffered) batch of E'w
 #endif
-#ifndef MPCQP_RELANE_MASK
-#define MPCQP_RELANE_MASK 0x010u     // measured on C3: solve_into_dz only
-#endif
-// relane site i is active iff bit i of MPCQP_RELANE_MASK is set (see DevWave::relane)
-#define MPCQP_RELANE(i) do { if ((MPCQP_RELANE_MASK >> (i)) & 1u) w.relane(); } while (0)
 
 namespace mpcqp {
 
@@ -372,9 +304,6 @@ MPCQP_HD inline Carve make_carve(const DM& d) {
     Carve c{};
     int o = 0;
     auto take = [&](int n) { int r = o; o += (n + 1) & ~1; return r; };   // keep 16-B alignment
-#ifdef MPCQP_LDS_FRONT_PAD
-    (void)take(MPCQP_LDS_FRONT_PAD);      // (experiment of DESIGN 4 "out-of-line members": nothing within 4 KB of LDS offset 0)
-#endif
     c.S = take((d.Hp + zpad_S(d)) * stride_S(d));   // zero blocks first (StaticDims::zpad)
     c.Phi = take(d.npk);
     c.zero = take(6);                             // four zeros: where masked lanes of a chunk read point; [4]: trash slot
@@ -409,12 +338,11 @@ MPCQP_HD inline Carve make_carve(const DM& d) {
     return c;
 }
 
-// which wavefront of a team takes item `idx` of a matrix-core job (helpers first; see MPCQP_TEAM_MAIN_MFMA), and whether this
+// which wavefront of a team takes item `idx` of a matrix-core job (helpers first), and whether this
 // wavefront has any of `count` items
 template <class W>
 MPCQP_HD constexpr bool team_mine_mfma(int idx) {
     if (W::NTEAM == 1) return true;
-    if (W::NTEAM >= 3 && !MPCQP_TEAM_MAIN_MFMA) return W::WV != 0 && idx % (W::NTEAM - 1) == W::WV - 1;
     return (idx + 1) % W::NTEAM == W::WV;
 }
 template <class W>
@@ -607,7 +535,6 @@ struct Qp {
         if constexpr (W::NTEAM > 1) w.join();
     }
     MPCQP_HD void E_apply_share(const double* v, double* out) {
-        MPCQP_RELANE(0);
         const int ny = d.ny, nu = d.nu;
         if constexpr (DM::is_static) {
             if (W::NTEAM == 1 && DM::nu == 4 && DM::nY <= 2 * WAVE && DM::Hc <= MPCQP_EAPPLY44_HCMAX && d.default_nb) {
@@ -697,7 +624,6 @@ struct Qp {
         if constexpr (W::NTEAM > 1) w.join();
     }
     MPCQP_HD void Et_apply_share(const double* wv, double* out, double scale, int t_hi) {
-        MPCQP_RELANE(1);
         const int ny = d.ny, nu = d.nu;
         if (t_hi < 0) t_hi = d.Hp;          // only the steps t < t_hi contribute
         if constexpr (DM::is_static) {
@@ -842,15 +768,12 @@ struct Qp {
         if constexpr (W::NTEAM > 1) w.join();
         return e;
     }
+    // (a forwarding layer of its own: merged into EtDE_share_, the compiler schedules the E'DE assembly differently)
     __device__ __forceinline__ int EtDE_share(const double* dd, double* P, double scale, const double* tb, const double* Hg, bool ow, bool has_tb) {
-        MPCQP_SETPRIO(4, 0);
-        const int e = EtDE_share_(dd, P, scale, tb, Hg, ow, has_tb);
-        MPCQP_SETPRIO(4, 1);
-        return e;
+        return EtDE_share_(dd, P, scale, tb, Hg, ow, has_tb);
     }
     // (tb: a pointer into LDS also when there is no ϵ row to ride -- has_tb says so: a select with nullptr makes the pointer generic)
     __device__ __forceinline__ int EtDE_share_(const double* dd, double* P, double scale, const double* tb, const double* Hg, bool ow, bool has_tb) {
-        MPCQP_RELANE(2);
         ow = ow || Hg != nullptr;
         constexpr int NU = DM::nu, NY = DM::ny, NDU = DM::nDU, NYR = DM::nY, SP = DM::sp, RS = DM::rs;
         constexpr int NT = (NDU + 15) / 16, NK = (NYR + 3) / 4;
@@ -882,11 +805,11 @@ struct Qp {
             if ((4 * v) % NY != 0) v = 0;
             eps_t0 = (4 * v) / NY;
         }
-        // operands in registers (MPCQP_ETDE_VREG): V[k] = operand of tile column 0 at K step k = (t, a0): Sigma(t - li / nu)[a0 + row, li % nu]
+        // operands in registers: V[k] = operand of tile column 0 at K step k = (t, a0): Sigma(t - li / nu)[a0 + row, li % nu]
         // (zero blocks in front of the table for t < li / nu)
         constexpr int QK = NY % 4 == 0 ? NY / 4 : 1;                  // K steps per step of the horizon
         constexpr int DJ = (16 % NU == 0) ? QK * (16 / NU) : 1;       // K steps by which a tile column's operands lag those of the one before
-        constexpr bool VREG = MPCQP_ETDE_VREG && NY % 4 == 0 && 16 % NU == 0 && DM::zpad > 0 && DM::zpad >= 16 / NU - 1 &&
+        constexpr bool VREG = NY % 4 == 0 && 16 % NU == 0 && DM::zpad > 0 && DM::zpad >= 16 / NU - 1 &&
                               NK <= MPCQP_ETDE_VREG_MAX;
         double V[VREG ? NK : 1];
         if constexpr (VREG) {
@@ -1133,7 +1056,7 @@ struct Qp {
     // P[pk(i,i')] += scale * sum_r E[r,i] dd[r] E[r,i']   (i >= i' < nDU).  When `tb` is given
     // and the matrix-core path runs, the ϵ row P[pk(nDU, i')] += sum_r tb[r] E[r,i'] is added for the
     // rows of the steps t >= the returned value; the caller adds the rest (Et_apply_add; -1: all of it).
-    MPCQP_HD_ETDE int EtDE_add(const double* dd, double* P, double scale = 1.0, const double* tb = nullptr,
+    MPCQP_HD int EtDE_add(const double* dd, double* P, double scale = 1.0, const double* tb = nullptr,
                           const double* Hg = nullptr, bool ow = false) {
 #if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (DM::is_static) return EtDE_add_mfma(dd, P, scale, tb, Hg, ow);
@@ -1691,7 +1614,6 @@ struct Step {
     // fn(group, local index, Row&) for every row owned by this lane
     template <class Fn>
     MPCQP_HD void for_rows(Fn fn) {
-        MPCQP_RELANE(7);
         MPCQP_UNROLL
         for (int g = 0; g < NGROUP; ++g) {
             if (!qp.group_on(g)) continue;
@@ -2038,7 +1960,6 @@ struct Step {
         }
         MPCQP_TOCK(11, tic11_);
         MPCQP_TICK(tic12_);
-        if (!(MPCQP_ABLATE & 8))
         if (qp.pair_on(P_Y) || qp.pair_on(P_W)) qp.E_apply(v, sm + c.tA[P_Y]);
         MPCQP_TOCK(12, tic12_);
         if (qp.pair_on(P_X)) {
@@ -2077,7 +1998,6 @@ struct Step {
     // ---- fn(Row&, (G v)[row]) for every finite row -------------------------------------------
     template <class Fn>
     MPCQP_HD void apply_G(const double* v, Fn fn) {
-        MPCQP_RELANE(5);
         MPCQP_TIC();
         primitives(v);
         const double e = d.neps ? v[d.nZ - 1] : 0.0;
@@ -2093,7 +2013,6 @@ struct Step {
     // ---- gt = G' wv, wv(Row&) evaluated on finite rows ---------------------------------------
     template <class Fn>
     MPCQP_HD void apply_Gt(Fn wv) {
-        MPCQP_RELANE(6);
         MPCQP_TIC();
         MPCQP_TICK(tic_gt_);
         const int nu = d.nu;
@@ -2137,7 +2056,7 @@ struct Step {
         }
         MPCQP_TOCK(9, tic9_);
         MPCQP_TICK(tic10_);
-        if (useY && !(MPCQP_ABLATE & 16)) qp.Et_apply_add(sm + c.tA[P_Y], gt);   // same lane owns gt[k]
+        if (useY) qp.Et_apply_add(sm + c.tA[P_Y], gt);   // same lane owns gt[k]
         w.sync();
         MPCQP_TOCK(10, tic10_);
         MPCQP_TOC(1);
@@ -2184,7 +2103,7 @@ struct Step {
             MPCQP_UNROLL
             for (int q_ = 0; q_ < HWQ; ++q_) { const int r = w.lane + WAVE * q_; hwy_[q_] = r < d.nY ? hwy_[q_] : 0.0; }
         }
-        fold_H = MPCQP_FOLD_H && !m.Mblk && !m.Mfull && !m.Ndense && !m.Ldense && qp.pair_on(P_Y) && d.nDU <= WAVE &&
+        fold_H = !m.Mblk && !m.Mfull && !m.Ndense && !m.Ldense && qp.pair_on(P_Y) && d.nDU <= WAVE &&
                  (qp.pair_on(P_U) || !h_Lnz);
         if (fold_H) {           // pads of the packed layout hold zero from here on (load_H used to bring them)
             for (int i = w.lane; i < d.npk; i += WAVE) Phi[i] = 0.0;
@@ -2219,7 +2138,6 @@ struct Step {
 
     // ---- Phi <- H̃ (global -> LDS) ------------------------------------------------------------
     MPCQP_HD void load_H() {
-        MPCQP_RELANE(11);
         if constexpr (W::NTEAM > 1) w.post(TJ_LOADH);
         load_H_share();
         if constexpr (W::NTEAM > 1) w.join();
@@ -2306,7 +2224,6 @@ struct Step {
     // ---- Phi (+)= G' diag(dd) G, dd(Row&) evaluated on finite rows (see phi_direct) ---------------
     template <class Fn>
     MPCQP_HD void add_GtDG(Fn dd) {
-        MPCQP_RELANE(3);
         MPCQP_TIC();
         const int nu = d.nu, nDU = d.nDU, nZ = d.nZ;
         double ee = 0.0;
@@ -2343,7 +2260,6 @@ struct Step {
         int eps_t0 = -1;          // first step whose Ŷ rows the matrix-core path put into the ϵ row
         if (qp.pair_on(P_Y)) {
             MPCQP_TIC();
-            if (!(MPCQP_ABLATE & 1))
             eps_t0 = qp.EtDE_add(sm + c.tA[P_Y], Phi, 1.0, d.neps ? sm + c.tB[P_Y] : nullptr,
                                  (phi_direct() && !fold_H) ? m.Hpk + (size_t)b * d.npk : nullptr, fold_H && etde_overwrites());
             w.sync();      // the MFMA write-back uses its own entry->lane map
@@ -2352,7 +2268,7 @@ struct Step {
         MPCQP_TICK(tic5_);
         // U rows: Pu' dU Pu has entry ((j,c),(j',c)) = sum_{jj >= max(j,j')} dU[jj,c]: lane (j,c)
         // forms its suffix sum once and adds it along its own row of the lower triangle
-        if (qp.pair_on(P_U) && nDU <= WAVE && !(MPCQP_ABLATE & 64)) {
+        if (qp.pair_on(P_U) && nDU <= WAVE) {
             // one row per lane: suffix sum by log steps, then unconditional read-modify-writes along
             // the lane's row (block columns right of the diagonal go to the trash slot)
             const double* tU = sm + c.tA[P_U];
@@ -2362,7 +2278,6 @@ struct Step {
             double* const trash = sm + c.zero + 4;
             double* const row = Phi + pk(k, cc);
             if constexpr (DM::is_static) {
-#if MPCQP_CHOL_RMW_BATCH
                 // all reads, then all writes (entry by entry the trash slot's possible aliasing serialises Hc LDS round trips)
                 double* q_[DM::Hc];
                 double old_[DM::Hc];
@@ -2373,13 +2288,6 @@ struct Step {
                 }
                 MPCQP_UNROLL
                 for (int j2 = 0; j2 < DM::Hc; ++j2) *q_[j2] = old_[j2] + suf;
-#else
-                MPCQP_UNROLL
-                for (int j2 = 0; j2 < d.Hc; ++j2) {
-                    double* const q_ = (j2 <= j && w.lane < nDU) ? row + j2 * nu : trash;
-                    *q_ += suf;
-                }
-#endif
             } else {
                 for (int j2 = 0; j2 < d.Hc; ++j2) {
                     double* const q_ = (j2 <= j && w.lane < nDU) ? row + j2 * nu : trash;
@@ -2510,7 +2418,7 @@ struct Step {
                 const double bb = X[P][4 * kk];
                 // (one row per lane, M D M' form: one operand carries d of its column, the d vector sits in gt; the
                 //  several-rows-per-lane factorisation that shares this function is LL')
-                const double bs = (MPCQP_CHOL_LDL && !MPCQP_CHOL_REDUNDANT && one_row_per_lane<DM>()) ? bb * gt[4 * kk + lk] : bb;
+                const double bs = one_row_per_lane<DM>() ? bb * gt[4 * kk + lk] : bb;
                 if (mine(P)) acc[P] = __builtin_amdgcn_mfma_f64_16x16x4f64(bb, bs, acc[P], 0, 0, 0);
                 MPCQP_UNROLL
                 for (int I = P + 1; I < NT; ++I)
@@ -2568,9 +2476,8 @@ struct Step {
             const int row = 16 * T + li < n ? 16 * T + li : n - 1;
             x[T] = Phi[pk(row, 0) + K0 + lk];
         }
-        const double xPs = (MPCQP_CHOL_LDL && !MPCQP_CHOL_REDUNDANT && one_row_per_lane<DM>()) ? x[P] * gt[K0 + lk] : x[P];   // (M D M': d of the block's columns, written by chol_static)
+        const double xPs = one_row_per_lane<DM>() ? x[P] * gt[K0 + lk] : x[P];   // (M D M': d of the block's columns, written by chol_static)
         double* const trash = sm + c.zero + 4;
-#if MPCQP_CHOL_RMW_BATCH
         // Every entry to be updated is requested BEFORE the matrix-core instructions are issued and written after them:
         // written as `*q -= acc[r]` entry by entry, the possible aliasing of the trash slot made each read-modify-write
         // wait for the one before it (ds_read, s_waitcnt lgkmcnt(0), v_add, ds_write: 49 dependent LDS round trips per
@@ -2596,30 +2503,17 @@ struct Step {
                 *q_[T][r] = old_[T][r] - acc[r];
             }
         }
-#else
-        MPCQP_UNROLL
-        for (int T = P; T < NT; ++T) {
-            const v4d_ acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xPs, x[T], v4d_{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
-            MPCQP_UNROLL
-            for (int r = Bk + 1; r < 4; ++r) {
-                if (16 * P + 4 * r >= n) continue;
-                const int row = 16 * T + li, col = 16 * P + 4 * r + lk;
-                double* const q_ = (row < n && col <= row) ? Phi + pk(row, col) : trash;
-                *q_ -= acc[r];
-            }
-        }
-#endif
         w.sync();
     }
 
     // One block of four columns of the compile-time-dims factorisation (see cholesky()); the recursion
     // over K0 unrolls the whole factorisation: every row offset, lane index and panel step is a constant.
-    // MPCQP_CHOL_REDUNDANT: the 4 x 4 diagonal block is read by EVERY lane (wave-uniform LDS addresses: broadcast reads,
-    // issued together with the lane's own four entries) and factored redundantly in registers; a lane then finishes its
-    // own row with the block's uniform entries as plain operands.  Same operations in the same order as "every lane
-    // takes the reciprocal square root of its own entry, lane k's is broadcast" (bit-identical factor), but no
-    // v_readlane (and no hazard nops) on the column-to-column dependency: the chain is four rsq + a few FMAs per block.
-    // The pivot thresholds of the block's rows come from an LDS vector (dz, free during a factorisation).
+    // Phi = M D M' with unit lower-triangular M, stored NEGATED (m_ik = -a_ik / d_k: the substitution chains of
+    // solve_static add), no square root: the pivot chain is v_rcp_f64 + two multiply-adds per column (LL': floor,
+    // v_rsq_f64 + three), and -- the point -- the sweeps of solve_static use the stored entries as they are: no scaling of
+    // the factor by 1/L_ii in every solve (176 multiplications per interior-point iteration).  A column's 1/d_k is known
+    // when its entries are stored, which is what a row scaling of L never is.  No guard on the chain: a pivot <= thr
+    // (or NaN) is told from d afterwards and the factor discarded (Step::run).
     template <int K0>
     __device__ __forceinline__ void chol_static(double thr) {
         constexpr int n = DM::nZ, CB = 4, P = K0 / 16, Bk = (K0 % 16) / 4;
@@ -2630,56 +2524,6 @@ struct Step {
         const bool mine = act && i >= K0;
         double v[CB], lk[CB];
         load4(mine ? Phi + rowi + K0 : sm + c.zero, v);
-#if MPCQP_CHOL_REDUNDANT
-        constexpr int NC = (n - K0 < CB) ? n - K0 : CB;              // columns of this block that exist
-        double A[NC][CB], th[CB], d_[NC], L[NC][NC];
-        MPCQP_UNROLL
-        for (int r = 0; r < NC; ++r) load4(Phi + pk(K0, 0) + r * (K0 + CB) + K0, A[r]);   // rows K0..K0+3 share a stride
-        load4(dz + K0, th);                                          // thresholds of rows K0..K0+3 (written by cholesky())
-        MPCQP_UNROLL
-        for (int cc = 0; cc < NC; ++cc) {
-            double t = A[cc][cc];
-            MPCQP_UNROLL
-            for (int k = 0; k < cc; ++k) t = fma(-L[cc][k], L[cc][k], t);
-            d_[cc] = (t > th[cc]) ? rsqrt_(t) : 0.0;                 // 0: pivot below its threshold (zero column)
-            MPCQP_UNROLL
-            for (int r = cc + 1; r < NC; ++r) {
-                double x = A[r][cc];
-                MPCQP_UNROLL
-                for (int k = 0; k < cc; ++k) x = fma(-L[r][k], L[cc][k], x);
-                L[r][cc] = x * d_[cc];
-            }
-        }
-        MPCQP_UNROLL
-        for (int cc = 0; cc < CB; ++cc) {
-            if (cc < NC) {
-                double x = v[cc];
-                MPCQP_UNROLL
-                for (int k = 0; k < cc; ++k) x = fma(-lk[k], L[cc][k], x);
-                lk[cc] = x * d_[cc];
-            } else {
-                lk[cc] = 0.0;                                        // a column k >= n does not exist
-            }
-        }
-#if MPCQP_CHOL_INVD == 0
-        MPCQP_UNROLL
-        for (int cc = 0; cc < NC; ++cc) myinvd = (i == K0 + cc) ? d_[cc] : myinvd;
-#elif MPCQP_CHOL_INVD == 1
-        if (i == 0) {
-            MPCQP_UNROLL
-            for (int cc = 0; cc < NC; ++cc) gt[K0 + cc] = d_[cc];
-        }
-#else
-        MPCQP_UNROLL
-        for (int cc = 0; cc < NC; ++cc) gt[K0 + cc] = d_[cc];        // every lane, same value, same address
-#endif
-#elif MPCQP_CHOL_LDL
-        // Phi = M D M' with unit lower-triangular M, stored NEGATED (m_ik = -a_ik / d_k: the substitution chains of
-        // solve_static add), no square root: the pivot chain is v_rcp_f64 + two multiply-adds per column (LL': floor,
-        // v_rsq_f64 + three), and -- the point -- the sweeps of solve_static use the stored entries as they are: no scaling of
-        // the factor by 1/L_ii in every solve (176 multiplications per interior-point iteration).  A column's 1/d_k is known
-        // when its entries are stored, which is what a row scaling of L never is.  No guard on the chain: a pivot <= thr
-        // (or NaN) is told from d afterwards and the factor discarded (Step::run).
         constexpr int NCL = (n - K0 < CB) ? n - K0 : CB;             // columns of this block that exist
         MPCQP_UNROLL
         for (int cc = 0; cc < CB; ++cc) {
@@ -2693,35 +2537,7 @@ struct Step {
                 lk[cc] = 0.0;
             }
         }
-#elif MPCQP_CHOL_DIAG
-        // The pivot guard is a floor (v_max with the lane's threshold: one instruction on the pivot chain instead of a
-        // compare and two selects after it) and L_kk = v_k / sqrt(v_k) stays in the diagonal slot: cholesky() turns it
-        // into 1/L_kk -- and tells a floored pivot by L_kk^2 <= thr -- once, after the last column (one LDS read, one
-        // reciprocal, one store per lane instead of a three-instruction select per column).  A factor with a floored
-        // pivot is finite garbage: Step::run discards it (larger dual regularisation, no step taken).
-        MPCQP_UNROLL
-        for (int cc = 0; cc < CB; ++cc) {
-            const int k = K0 + cc;                       // k <= 63; a column k >= n only sees zeros
-            const double idl = rsqrt_(fmx(v[cc], thr));  // (only lane k's value is used)
-            const double idb = w.bcast(idl, k);
-            lk[cc] = v[cc] * idb;
-            MPCQP_UNROLL
-            for (int c2 = cc + 1; c2 < CB; ++c2) v[c2] -= lk[cc] * w.bcast(lk[cc], K0 + c2);
-        }
-#else
-        MPCQP_UNROLL
-        for (int cc = 0; cc < CB; ++cc) {
-            const int k = K0 + cc;                       // k <= 63; a column k >= n only sees zeros
-            const double idl = (v[cc] > thr) ? rsqrt_(v[cc]) : 0.0;
-            const double idb = w.bcast(idl, k);
-            lk[cc] = v[cc] * idb;
-            myinvd = (i == k) ? idl : myinvd;
-            MPCQP_UNROLL
-            for (int c2 = cc + 1; c2 < CB; ++c2) v[c2] -= lk[cc] * w.bcast(lk[cc], K0 + c2);
-        }
-#endif
         if (mine) {
-#if MPCQP_CHOL_LDL && !MPCQP_CHOL_REDUNDANT
             // lane K0 + a still holds its pivot in v[a] (a column's entry is not touched after its own step); the lanes
             // beyond the block pick up a meaningless value here and the right one in their own block, the last one
             // they take part in.  gt doubles as the d vector the matrix-core updates scale one operand with.
@@ -2730,10 +2546,6 @@ struct Step {
             gt[i] = myd_;
             MPCQP_UNROLL
             for (int cc = 0; cc < CB; ++cc) lk[cc] = (i > K0 + cc) ? lk[cc] : 0.0;
-#else
-            MPCQP_UNROLL
-            for (int cc = 0; cc < CB; ++cc) lk[cc] = (MPCQP_CHOL_DIAG && !MPCQP_CHOL_REDUNDANT ? i >= K0 + cc : i > K0 + cc) ? lk[cc] : 0.0;
-#endif
             store4(Phi + rowi + K0, lk);
         }
         w.sync();
@@ -2755,14 +2567,12 @@ struct Step {
     // a row are (re)written as zeros and 1/L[k][k] stays in a register of lane k (myinvd).
     // Pivot guard: a non-positive pivot (float64 breakdown of the normal equations) freezes that
     // coordinate for this Newton step (zero column, 1/L = 1e-32) instead of poisoning the factor.
-    MPCQP_HD_CHOL void cholesky() {
+    // Compile-time dims on the device take the M D M' form instead (chol_static; myinvd = 1/d[lane]).
+    MPCQP_HD void cholesky() {
         if (d.nZ > WAVE) { cholesky_big(); return; }      // (a compile-time branch with compile-time dims)
-        MPCQP_SETPRIO(1, 1);
-        cholesky_();
-        MPCQP_SETPRIO(1, 0);
+        cholesky_();        // (a function of its own: merged into this one, the compiler lays out the runtime-dims loops differently)
     }
-    MPCQP_HD_CHOL void cholesky_() {
-        MPCQP_RELANE(8);
+    MPCQP_HD void cholesky_() {
         MPCQP_TIC();
         const int n = d.nZ;
         const int i = w.lane;
@@ -2775,37 +2585,10 @@ struct Step {
         constexpr int CB = 4;
 #if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (one_row_per_lane<DM>()) {
-#if MPCQP_CHOL_REDUNDANT
-            if (act) dz[i] = thr;                 // read back four at a time by chol_static (dz is free here)
-            w.sync();
-#endif
             chol_static<0>(thr);
-#if MPCQP_CHOL_REDUNDANT && MPCQP_CHOL_INVD != 0
-            myinvd = act ? gt[i] : 0.0;           // (gt is free during a factorisation)
+            chol_broke = w.any(act && !(myd_ > thr));            // a pivot at or below its threshold, or NaN
+            myinvd = act ? rcp(myd_) : 0.0;
             w.sync();
-#endif
-#if MPCQP_CHOL_LDL && !MPCQP_CHOL_REDUNDANT
-            {
-                chol_broke = w.any(act && !(myd_ > thr));            // a pivot at or below its threshold, or NaN
-                myinvd = act ? rcp(myd_) : 0.0;
-                w.sync();
-                MPCQP_TOC(6);
-                return;
-            }
-#elif MPCQP_CHOL_DIAG && !MPCQP_CHOL_REDUNDANT
-            {
-                // L_ii from the diagonal slot -> 1/L_ii in the lane's register, zero in the slot (what the sweeps expect)
-                const double Ld = act ? Phi[rowi + i] : 1.0;
-                if (act) Phi[rowi + i] = 0.0;
-                chol_broke = w.any(act && !(Ld * Ld > thr));         // a floored (or NaN) pivot
-                myinvd = act ? rcp(Ld) : 0.0;
-                w.sync();
-                MPCQP_TOC(6);
-                return;
-            }
-#endif
-            myinvd = fmx(myinvd, 1e-32);
-            chol_broke = w.any(act && myinvd <= 1e-32);
             MPCQP_TOC(6);
             return;
         }
@@ -2813,25 +2596,16 @@ struct Step {
         MPCQP_NOUNROLL
         for (int k0 = 0; k0 < n; k0 += CB) {
             const bool mine = act && i >= k0;
-            int j0 = 0;                                  // first column the sweep below has to cover
-#if defined(__HIP_DEVICE_COMPILE__)
-            if constexpr (one_row_per_lane<DM>()) {
-                if (k0 == 16) chol_panel_update<1>();
-                else if (k0 == 32) chol_panel_update<2>();
-                else if (k0 == 48) chol_panel_update<3>();
-                j0 = k0 & ~15;                           // columns < 16P are already accounted for
-            }
-#endif
             double v[CB];
             load4(mine ? Phi + rowi + k0 : zero4, v);     // entries right of the diagonal are pads = 0
-            if (mine && k0 > j0) {
+            if (mine && k0 > 0) {
                 const double* Li = Phi + rowi;
                 const int rb = pk(k0, 0), rs = k0 + CB;   // rows k0..k0+3 share the stride k0+4
                 const double* Lk[CB];
                 MPCQP_UNROLL
                 for (int cc = 0; cc < CB; ++cc) Lk[cc] = Phi + rb + (k0 + cc < n ? cc : n - 1 - k0) * rs;
                 _Pragma("unroll 2")
-                for (int j = j0; j < k0; j += 2) {       // j0, k0 multiples of CB: pairs are aligned
+                for (int j = 0; j < k0; j += 2) {        // k0 a multiple of CB: pairs are aligned
                     const double a0 = Li[j], a1 = Li[j + 1];
                     MPCQP_UNROLL
                     for (int cc = 0; cc < CB; ++cc) {
@@ -2879,8 +2653,8 @@ struct Step {
     // the row mask keeps the other rows out, no v_readlane / scalar operand / hazard nops of a cross-wave broadcast.
     // The finished tile is then copied to every row (one ds_bpermute pair) and the rows still to come (forward: below,
     // backward: above) take their whole 16-column update from that copy, again with the row broadcast in the
-    // multiply-add and two independent accumulators.  Same arithmetic per unknown as the column sweeps of
-    // solve_into_dz (sums in a different order).  c: the lane's own factor entries times -1/L_ii.
+    // multiply-add and two independent accumulators.  c: the lane's own factor entries, used as stored (chol_static keeps
+    // M of Phi = M D M' negated).
     // raw factor entries of tile T for the forward sweep: the lane's own row, columns 16T.. (zeros on and right of the
     // diagonal; rows above the tile read the zero slot)
     template <int T>
@@ -2908,7 +2682,7 @@ struct Step {
         }
     }
     template <int T>
-    __device__ __forceinline__ void solve_fwd_tile(double& r, double (*cf)[4], const int rowi, const bool act, const double nm) {
+    __device__ __forceinline__ void solve_fwd_tile(double& r, double (*cf)[4], const int rowi, const bool act) {
         constexpr int n = DM::nZ, NT = (n + 15) / 16, K0 = 16 * T, KT = (n - K0 < 16) ? n - K0 : 16, NC = (KT + 3) / 4;
         double nx[4][4];                                    // the next tile (or the first one of the backward sweep), in flight
         if constexpr (T + 1 < NT) solve_fwd_load<T + 1>(nx, rowi, act);
@@ -2923,21 +2697,14 @@ struct Step {
             for (int u = 0; u < NC; ++u) rows_sw<0xf & ~((2 << T) - 1)>(u, (u & 1) ? a1 : a0, y, cf[u]);
             r += a0 + a1;
             MPCQP_SCHED_FENCE();
-            if constexpr (!solve_unscaled()) {
-                MPCQP_UNROLL
-                for (int u = 0; u < 4; ++u) {
-                    MPCQP_UNROLL
-                    for (int e = 0; e < 4; ++e) nx[u][e] *= nm;
-                }
-            }
-            solve_fwd_tile<T + 1>(r, nx, rowi, act, nm);
+            solve_fwd_tile<T + 1>(r, nx, rowi, act);
         } else {
-            r *= myinvd;                                    // L'x = y
-            solve_bwd_tile<NT - 1>(r, nx, act, nm);
+            r *= myinvd;                                    // D^-1, then M'x = y
+            solve_bwd_tile<NT - 1>(r, nx, act);
         }
     }
     template <int T>
-    __device__ __forceinline__ void solve_bwd_tile(double& r, double (*cb)[4], const bool act, const double nm) {
+    __device__ __forceinline__ void solve_bwd_tile(double& r, double (*cb)[4], const bool act) {
         constexpr int n = DM::nZ, K0 = 16 * T, KT = (n - K0 < 16) ? n - K0 : 16, NC = (KT + 3) / 4;
         const int i = w.lane;
         double nx[4][4];
@@ -2946,7 +2713,7 @@ struct Step {
         if constexpr (!solve_zero_region()) {
             MPCQP_UNROLL
             for (int u = 0; u < NC; ++u) {
-                const double sc = (act && i < K0 + 4 * u + 4) ? (solve_unscaled() ? 1.0 : nm) : 0.0;
+                const double sc = (act && i < K0 + 4 * u + 4) ? 1.0 : 0.0;
                 MPCQP_UNROLL
                 for (int e = 0; e < 4; ++e) cb[u][e] *= sc;
             }
@@ -2959,7 +2726,7 @@ struct Step {
             MPCQP_UNROLL
             for (int u = 0; u < NC; ++u) rows_sw<(1 << T) - 1>(u, (u & 1) ? a1 : a0, x, cb[u]);
             r += a0 + a1;
-            solve_bwd_tile<T - 1>(r, nx, act, nm);
+            solve_bwd_tile<T - 1>(r, nx, act);
         }
     }
     // (the DPP lane is an immediate: one instantiation per chunk of four, selected by the unrolled loop index)
@@ -2981,30 +2748,18 @@ struct Step {
             default: W::template fmabc4<12, ROWS>(a, x, cc[0], cc[1], cc[2], cc[3]); break;
         }
     }
-    // the factor is M D M' with the negated unit-triangular M stored (chol_static, MPCQP_CHOL_LDL): the sweeps use its entries
-    // as they are.  Needs zeros at the strided offsets of solve_bwd_load, i.e. enough zero blocks in front of the Sigma table.
-    static constexpr bool solve_unscaled() { return MPCQP_CHOL_LDL && !MPCQP_CHOL_REDUNDANT; }
-    // ... and the lanes beyond a chunk's rows of the backward sweep read zeros from the zero blocks in front of the Sigma
-    // table (enough of them for the strided offsets e (k0 + 4)); otherwise their entries are multiplied by zero
-    static constexpr bool solve_zero_region() { return solve_unscaled() && DM::zpad * DM::sp >= 3 * (DM::nZ + 3) + 4; }
+    // the lanes beyond a chunk's rows of the backward sweep read zeros from the zero blocks in front of the Sigma table
+    // (enough of them for the strided offsets e (k0 + 4)); otherwise their entries are multiplied by zero
+    static constexpr bool solve_zero_region() { return DM::zpad * DM::sp >= 3 * (DM::nZ + 3) + 4; }
     __device__ __forceinline__ void solve_static() {
         constexpr int n = DM::nZ;
         const int i = w.lane;
         const bool act = i < n;
         const int rowi = pk(act ? i : 0, 0);
-        const double nm = act ? -myinvd : 0.0;
         double r = act ? gt[i] : 0.0;
-        if constexpr (!(MPCQP_CHOL_LDL && !MPCQP_CHOL_REDUNDANT)) r *= myinvd;      // LL': L y = r in the variable scaled by 1/L_ii
         double cf[4][4];
         solve_fwd_load<0>(cf, rowi, act);
-        if constexpr (!solve_unscaled()) {
-            MPCQP_UNROLL
-            for (int u = 0; u < 4; ++u) {
-                MPCQP_UNROLL
-                for (int e = 0; e < 4; ++e) cf[u][e] *= nm;
-            }
-        }
-        solve_fwd_tile<0>(r, cf, rowi, act, nm);            // (runs on into the backward sweep)
+        solve_fwd_tile<0>(r, cf, rowi, act);                // (runs on into the backward sweep)
         if (act) dz[i] = r;
         w.sync();
     }
@@ -3016,15 +2771,10 @@ struct Step {
     // block the zero diagonal slot / pad entries do the masking.  The chunk of the next group is fetched ahead of the dependent chain, which is then
     // v_mul -> v_readlane -> v_fma per column.
     MPCQP_HD void solve_into_dz() {
-        MPCQP_RELANE(4);          // (in front of the several-rows-per-lane form too: without it the nZ~ = 106 kernel spills 748 registers instead of 6)
+        w.relane();               // (in front of the several-rows-per-lane form too: without it the nZ~ = 106 kernel spills 748 registers instead of 6)
         if (d.nZ > WAVE) { solve_big(); return; }
-        MPCQP_SETPRIO(2, 1);
-        solve_into_dz_();
-        MPCQP_SETPRIO(2, 0);
-    }
-    MPCQP_HD void solve_into_dz_() {
         MPCQP_TIC();
-#if defined(__HIP_DEVICE_COMPILE__) && MPCQP_SOLVE_DPP
+#if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (one_row_per_lane<DM>()) {
             solve_static();
             MPCQP_TOC(7);
@@ -3174,7 +2924,7 @@ struct Step {
             const double* dinv = sm + c.dinv;
             auto lk = [&](int r, int cc) { return Phi[pk(K0 + r, 0) + K0 + cc]; };      // L[K0 + r][K0 + cc], wave-uniform
             // (diagonal-block form: the pivot slot's rows below the block are rows like any other, chol_big_panel_diag)
-            constexpr int s0 = (MPCQP_TEAM_DIAG && W::NTEAM >= 3) ? so : so + 1;
+            constexpr int s0 = W::NTEAM >= 3 ? so : so + 1;
             MPCQP_UNROLL
             for (int s_ = s0; s_ < NS; ++s_) {
                 if ((s_ - s0 + 1) % W::NTEAM != W::WV) continue;         // (first slot to wavefront 1, ..: wavefront 0 last)
@@ -3184,26 +2934,6 @@ struct Step {
                 double x[16];
                 MPCQP_UNROLL
                 for (int u = 0; u < 4; ++u) load4(mine ? row + 4 * u : sm + c.zero, &x[4 * u]);
-#if MPCQP_PANELROWS_RL
-                // right-looking, one column per scheduling region: the 15 - cc updates of a column are independent
-                // multiply-adds (the compiler otherwise orders the work by target column: 120 multiply-adds in chains on one
-                // accumulator each); the block's next column is requested while the current one is applied
-                double lc[16], ln[16];
-                MPCQP_UNROLL
-                for (int c2 = 1; c2 < 16; ++c2) lc[c2] = lk(c2, 0);
-                MPCQP_UNROLL
-                for (int cc = 0; cc < 16; ++cc) {
-                    MPCQP_UNROLL
-                    for (int c2 = cc + 2; c2 < 16; ++c2) ln[c2] = lk(c2, cc + 1);
-                    const double dv = dinv[K0 + cc];
-                    x[cc] *= dv > 1e-32 ? dv : 0.0;                   // (a pivot below its threshold: zero column, as in the pivot slot)
-                    MPCQP_UNROLL
-                    for (int c2 = cc + 1; c2 < 16; ++c2) x[c2] = fma(-x[cc], lc[c2], x[c2]);
-                    MPCQP_SCHED_FENCE();
-                    MPCQP_UNROLL
-                    for (int c2 = cc + 2; c2 < 16; ++c2) lc[c2] = ln[c2];
-                }
-#else
                 MPCQP_UNROLL
                 for (int cc = 0; cc < 16; ++cc) {
                     const double dv = dinv[K0 + cc];
@@ -3212,7 +2942,6 @@ struct Step {
                     for (int c2 = cc + 1; c2 < 16; ++c2) x[c2] = fma(-x[cc], lk(c2, cc), x[c2]);
                     if (cc % 4 == 3) MPCQP_SCHED_FENCE();            // (bounds the broadcast reads in flight: registers)
                 }
-#endif
                 if (mine) {
                     MPCQP_UNROLL
                     for (int u = 0; u < 4; ++u) store4(row + 4 * u, &x[4 * u]);
@@ -3287,11 +3016,11 @@ struct Step {
             // three or more wavefronts: the diagonal block alone on wavefront 0, every other row through the team's triangular
             // solves; two: the whole pivot slot on wavefront 0, the slots below on the team (measured, profiles/r6j: nZ~ = 151,
             // four wavefronts 31.3 -> 29.7 ms per 4096 with the diagonal-block form; nZ~ = 106, two wavefronts 19.3 -> 20.0 ms)
-            constexpr bool DIAG = MPCQP_TEAM_DIAG && W::NTEAM >= 3;
+            constexpr bool DIAG = W::NTEAM >= 3;
             if constexpr (DM::nZ - 16 * P >= 16) {
                 if constexpr (DIAG) chol_big_panel_diag<P, NS>(thr, broke);                 // (ends with a wave fence: its stores are issued)
                 else chol_big_panel_slots<P, NS, (so_ + 1 < NS ? so_ + 1 : NS)>(thr, broke);
-                if constexpr ((DIAG ? DM::nZ - 16 * P > 16 : so_ + 1 < NS) && !(MPCQP_ABLATE & 1024)) {
+                if constexpr (DIAG ? DM::nZ - 16 * P > 16 : so_ + 1 < NS) {
                     w.post(TJ_PANELROWS, P);
                     chol_big_panel_rows<P, NS>();
                     w.join();
@@ -3359,8 +3088,8 @@ struct Step {
     __device__ __forceinline__ void chol_big_panels(const double (&thr)[NS], bool& broke) {
         constexpr int n = DM::nZ, K0 = 16 * P;
         if constexpr (K0 < n) {
-            if constexpr (P > 0) { if (!(MPCQP_ABLATE & 256)) chol_panel_update<P>(); }
-            if (!(MPCQP_ABLATE & 512)) chol_big_panel_reg<P, NS>(thr, broke);
+            if constexpr (P > 0) chol_panel_update<P>();
+            chol_big_panel_reg<P, NS>(thr, broke);
             chol_big_panels<P + 1, NS>(thr, broke);
         }
     }
@@ -3467,133 +3196,11 @@ struct Step {
         w.sync();
     }
 #endif
-#if defined(__HIP_DEVICE_COMPILE__)
-    // Round 6: the same substitutions blocked by the 16-lane DPP rows, like solve_static's (one row per lane): unknown
-    // i = lane + 64 s sits in DPP row (lane >> 4) of slot s, i.e. tile (s, T) of 16 unknowns is one DPP row of register r[s].
-    // Inside a tile the substitution is a chain of v_fmac_f64_dpp row_newbcast (the broadcast is the multiply-add's own
-    // modifier: one instruction and two wait states per unknown); the finished tile is copied to every row (one ds_bpermute
-    // pair) and all unknowns still to come take their 16-column update from the copy, again with the row broadcast in the
-    // multiply-add.  The column-at-a-time form above pays two v_readlane, their scalar-operand hazards and a multiply-add on
-    // the dependent chain of EVERY unknown: 80 cycles per unknown and sweep measured at nZ~ = 151 (profiles/r6i).
-    template <int NS, int SO, int T>
-    __device__ __forceinline__ void sbd_fwd(double (&r)[NS], const double (&ndi)[NS], const int (&rowo)[NS], const bool (&act)[NS]) {
-        constexpr int n = DM::nZ, K0 = WAVE * SO + 16 * T;
-        if constexpr (K0 < n) {
-            constexpr int KT = (n - K0 < 16) ? n - K0 : 16, NC = (KT + 3) / 4;
-            const double* zero4 = sm + c.zero;
-            double cf[NS][4][4];
-            MPCQP_UNROLL
-            for (int s_ = SO; s_ < NS; ++s_) {
-                const int i = w.lane + WAVE * s_;
-                MPCQP_UNROLL
-                for (int u = 0; u < NC; ++u) {
-                    load4((act[s_] && i >= K0 + 4 * u) ? Phi + rowo[s_] + K0 + 4 * u : zero4, cf[s_][u]);
-                    MPCQP_UNROLL
-                    for (int e = 0; e < 4; ++e) cf[s_][u][e] *= ndi[s_];
-                }
-            }
-            MPCQP_UNROLL
-            for (int u = 0; u < NC; ++u) chain_sw<1 << T, false>(u, r[SO], cf[SO][u]);
-            if constexpr (K0 + 16 < n) {
-                const double y = w.fetch(r[SO], 16 * T + (w.lane & 15));
-                if constexpr (T < 3 && WAVE * SO + 16 * (T + 1) < n) {
-                    double a0 = 0.0, a1 = 0.0;
-                    MPCQP_UNROLL
-                    for (int u = 0; u < NC; ++u) rows_sw<0xf & ~((2 << T) - 1)>(u, (u & 1) ? a1 : a0, y, cf[SO][u]);
-                    r[SO] += a0 + a1;
-                }
-                MPCQP_UNROLL
-                for (int s_ = SO + 1; s_ < NS; ++s_) {
-                    double a0 = 0.0, a1 = 0.0;
-                    MPCQP_UNROLL
-                    for (int u = 0; u < NC; ++u) rows_sw<0xf>(u, (u & 1) ? a1 : a0, y, cf[s_][u]);
-                    r[s_] += a0 + a1;
-                }
-            }
-            MPCQP_SCHED_FENCE();
-            if constexpr (T < 3) sbd_fwd<NS, SO, T + 1>(r, ndi, rowo, act);
-            else sbd_fwd<NS, SO + 1, 0>(r, ndi, rowo, act);
-        }
-    }
-    template <int NS, int SO, int T>
-    __device__ __forceinline__ void sbd_bwd(double (&r)[NS], const double (&ndi)[NS], const bool (&act)[NS]) {
-        constexpr int n = DM::nZ, K0 = WAVE * SO + 16 * T;
-        if constexpr (K0 < n) {
-            constexpr int KT = (n - K0 < 16) ? n - K0 : 16, NC = (KT + 3) / 4;
-            // column entries L[k0 + e][i] of the rows k0 .. k0 + 3 of a chunk (they share the stride k0 + 4; zeros on and right
-            // of the diagonal), for the lane's unknown of every slot up to SO; a lane whose unknown lies beyond the chunk's rows
-            // reads column 0 and scales it by zero
-            double cb[NS][4][4];
-            MPCQP_UNROLL
-            for (int s_ = 0; s_ <= SO; ++s_) {
-                const int i = w.lane + WAVE * s_;
-                MPCQP_UNROLL
-                for (int u = 0; u < NC; ++u) {
-                    const int k0 = K0 + 4 * u;
-                    const bool on = act[s_] && i < k0 + 4;
-                    const double sc = on ? ndi[s_] : 0.0;
-                    const double* p_ = Phi + pk(k0, 0) + (i < k0 + 4 ? i : 0);
-                    MPCQP_UNROLL
-                    for (int e = 0; e < 4; ++e) cb[s_][u][e] = (k0 + e < n) ? p_[e * (k0 + 4)] * sc : 0.0;
-                }
-            }
-            MPCQP_UNROLL
-            for (int u = NC - 1; u >= 0; --u) chain_sw<1 << T, true>(u, r[SO], cb[SO][u]);
-            if constexpr (K0 > 0) {
-                const double x = w.fetch(r[SO], 16 * T + (w.lane & 15));
-                if constexpr (T > 0) {
-                    double a0 = 0.0, a1 = 0.0;
-                    MPCQP_UNROLL
-                    for (int u = 0; u < NC; ++u) rows_sw<(1 << T) - 1>(u, (u & 1) ? a1 : a0, x, cb[SO][u]);
-                    r[SO] += a0 + a1;
-                }
-                MPCQP_UNROLL
-                for (int s_ = 0; s_ < SO; ++s_) {
-                    double a0 = 0.0, a1 = 0.0;
-                    MPCQP_UNROLL
-                    for (int u = 0; u < NC; ++u) rows_sw<0xf>(u, (u & 1) ? a1 : a0, x, cb[s_][u]);
-                    r[s_] += a0 + a1;
-                }
-            }
-            MPCQP_SCHED_FENCE();
-        }
-        if constexpr (T > 0) sbd_bwd<NS, SO, T - 1>(r, ndi, act);
-        else if constexpr (SO > 0) sbd_bwd<NS, SO - 1, 3>(r, ndi, act);
-    }
-    __device__ __forceinline__ void solve_big_dpp() {
-        constexpr int n = DM::nZ, NS = (n + WAVE - 1) / WAVE;
-        const double* dinv = sm + c.dinv;
-        double r[NS], di[NS], ndi[NS];
-        int rowo[NS];
-        bool act[NS];
-        MPCQP_UNROLL
-        for (int s_ = 0; s_ < NS; ++s_) {
-            const int i = w.lane + WAVE * s_;
-            act[s_] = i < n;
-            rowo[s_] = pk(act[s_] ? i : 0, 0);
-            di[s_] = act[s_] ? dinv[i] : 0.0;
-            ndi[s_] = -di[s_];
-            r[s_] = (act[s_] ? gt[i] : 0.0) * di[s_];            // L y = r in the variable scaled by 1/L_ii
-        }
-        sbd_fwd<NS, 0, 0>(r, ndi, rowo, act);
-        MPCQP_UNROLL
-        for (int s_ = 0; s_ < NS; ++s_) r[s_] *= di[s_];          // L'x = y
-        sbd_bwd<NS, NS - 1, 3>(r, ndi, act);
-        MPCQP_UNROLL
-        for (int s_ = 0; s_ < NS; ++s_)
-            if (act[s_]) dz[w.lane + WAVE * s_] = r[s_];
-        w.sync();
-    }
-#endif
     MPCQP_HD void solve_big() {
         MPCQP_TIC();
 #if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (DM::is_static) {
-#if MPCQP_SOLVEBIG_DPP
-            solve_big_dpp();
-#else
             solve_big_static();
-#endif
             MPCQP_TOC(7);
             return;
         }
@@ -3893,7 +3500,7 @@ struct Step {
         });
         for (int k = w.lane; k < d.nZ; k += WAVE) gt[k] -= rd[k];
         w.sync();
-        if (!(MPCQP_ABLATE & 4)) solve_into_dz();
+        solve_into_dz();
         apply_G(dz, [&](Row& r, double g) { r.gd = g; rowfn(r); });
     }
 
@@ -3977,7 +3584,7 @@ struct Step {
         int npolish = 0;
         bool polished = false;
         double rpn_last = 1e300;
-        while (it < (MPCQP_FIXED_ITERS ? MPCQP_FIXED_ITERS : d.max_iter)) {
+        while (it < d.max_iter) {
             // A pivot below its threshold in the last factorisation means Phi = H̃ + G'D~G left
             // float64's range (rows held at D~ = 1/δ stack up to 1e14 on the diagonal of long
             // horizons).  The guarded factor kept that step finite (and the step-length rules kept
@@ -3985,7 +3592,7 @@ struct Step {
             // twice), which caps D~ lower and biases nothing -- δ multiplies the multiplier step,
             // which vanishes at the optimum -- and the residuals are re-evaluated exactly.  (Not met
             // on the BASELINE configs; about one family in 20 at nZ~ ~ 100.)
-            if (chol_broke && delta < 1e-8 && !MPCQP_FIXED_ITERS) {
+            if (chol_broke && delta < 1e-8) {
                 delta *= 100.0;
                 exact = true;
                 chol_broke = false;
@@ -4017,7 +3624,6 @@ struct Step {
                 rp_stalled = rpn >= 0.5 * rpn_last && rdscale_c <= 0.1 && rpn <= 1e-9 * nh;
                 rpn_last = rpn;
             }
-#if !MPCQP_FIXED_ITERS
             if (!(mu == mu) || !(rdn == rdn) || !(rpn == rpn)) { status = ST_ERROR; break; }
             // Converged: gap and residuals below their targets AND the last Newton step no longer moves
             // the inputs, alpha |dU|_inf <= 1e-6 max(1, |dU|_inf).  (Residual targets alone leave 1e-6-size
@@ -4045,15 +3651,14 @@ struct Step {
                 exact = true;                      // Phi, rd, gt were used: start over from exact residuals
                 continue;
             }
-#endif
             MPCQP_MTOC("looptop");
             if (!verified && !phi_direct()) load_H();
             add_GtDG([&](Row& r) {
                 return r.lam * row_wi_fresh(r);             // D~ = D / (1 + δ D)
             });
-            if (!(MPCQP_ABLATE & 2)) cholesky();
-#if (MPCQP_CHOL_DIAG || MPCQP_CHOL_LDL) && !MPCQP_FIXED_ITERS && defined(__HIP_DEVICE_COMPILE__)
-            // (chol_static's floored pivots leave a finite but meaningless factor: no step is taken with it -- the loop top
+            cholesky();
+#if defined(__HIP_DEVICE_COMPILE__)
+            // (a pivot of chol_static at or below its threshold leaves a meaningless factor: no step is taken with it -- the loop top
             //  raises the dual regularisation and re-evaluates the residuals; with the regularisation at its cap the solve
             //  has failed.  The runtime-dimension factorisation freezes the coordinate instead and goes on as before.)
             if constexpr (one_row_per_lane<DM>()) {
@@ -4075,7 +3680,6 @@ struct Step {
                 tmax = pass ? 1e-300 : 1.0;       // 1 / (largest step that keeps s, lam >= 0), capped at 1 for the predictor
                 newton([&](Row& r) { return fma(cpp, r.pp, fma(r.s, r.lam, -r.wt * smu)); },
                 [&](Row& r) {
-                    if (MPCQP_ABLATE & 32) return;
                     double ds, dl;
                     row_step(r, fma(cpp, r.pp, fma(r.s, r.lam, -r.wt * smu)), ds, dl);
                     // step to the boundary as 1 / max(-ds/s, -dl/lam): no compare, no select; raw reciprocals
@@ -4106,7 +3710,6 @@ struct Step {
             amin = rcp(w.maxv(tmax));
             const double ahi = fmin(1.0, 0.9999 * amin);
             double pmin = 1e300, psum = 0.0;
-            if (!(MPCQP_ABLATE & 32))
             for_rows([&](int, int, Row& r) {
                 if (!fin(r)) return;
                 const double p = (r.s + ahi * r.pp) * (r.lam + ahi * r.gd);
@@ -4117,7 +3720,6 @@ struct Step {
             psum = w.sum(psum);
             const double alpha = (pmin * wsum >= 0.01 * psum) ? ahi : fmin(1.0, 0.99 * amin);
             musum_c = 0.0; rpmax_c = 0.0; rdscale_c = 1.0 - alpha;
-            if (!(MPCQP_ABLATE & 32))
             for_rows([&](int, int, Row& r) {
                 if (!fin(r)) return;
                 r.s += alpha * r.pp;
@@ -4167,12 +3769,6 @@ struct Step {
 
 template <class W, class DM>
 MPCQP_HD void step_body(W& w, const DM& d, const Model& m, const StepIO& io, int b, double* sm) {
-    MPCQP_SETPRIO(4, 1);
-#ifdef MPCQP_TEAM_PINGTEST      // (measurement only: the cost of a job hand-off -- that many empty jobs in front of the step)
-    if constexpr (W::NTEAM > 1) {
-        for (int i_ = 0; i_ < MPCQP_TEAM_PINGTEST; ++i_) { w.post(99); w.join(); }
-    }
-#endif
     const long long t_in_ = Step<W, DM>::clock64_();
     Qp<W, DM> qp(w, d, m, b, sm);
     qp.load_tables();

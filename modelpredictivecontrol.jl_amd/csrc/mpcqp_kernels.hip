@@ -30,9 +30,6 @@ extern char** environ;      // (the specialisation compiler inherits the environ
 
 namespace mpcqp {
 
-#ifndef MPCQP_K1_MFMA
-#define MPCQP_K1_MFMA 1           // 0: the LDS loops for every shape (timing experiments)
-#endif
 #ifndef MPCQP_K1_MFMA_MIN_NX
 #define MPCQP_K1_MFMA_MIN_NX 10   // below, the 16-wide tiles are mostly padding and the LDS loops are faster (C2, nx̂ = 6: 0.55 vs 0.66 ms)
 #endif
@@ -41,7 +38,7 @@ static bool predmat_on_mfma(const Dims& d) {
         const char* e = getenv("MPCQP_K1_MFMA_MIN_NX");
         return e && atoi(e) > 0 ? atoi(e) : MPCQP_K1_MFMA_MIN_NX;
     }();
-    return MPCQP_K1_MFMA && predmat_mfma_ok(d) && d.nxh >= min_nx;
+    return predmat_mfma_ok(d) && d.nxh >= min_nx;
 }
 __global__ __launch_bounds__(64) void k_predmat(Dims d, Model m, int terminal) {
     DevWave w{(int)threadIdx.x};

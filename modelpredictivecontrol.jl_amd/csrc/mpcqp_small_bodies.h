@@ -25,18 +25,6 @@
 #include "mhe_bodies.h"
 #include "mpcqp_types.h"
 
-#ifndef MPCQP_SMALL_POLISH
-#define MPCQP_SMALL_POLISH 1      // active-set polish of the interior-point iterate, one attempt per wavefront (step_small_body<.., POL = true>):
-                                  // C2, 65536 controllers: 13.7 -> 9.9 factorisations, 1.09 -> 0.98 ms.  Not in the one-wave-per-SIMD variant: a launch of
-                                  // <= 4096 controllers lasts as long as its slowest wavefront, and that one pays for failed attempts on top of its
-                                  // interior-point passes (1024 controllers: 0.088 ms without, 0.109 ms with polish)
-#endif
-#ifndef MPCQP_SMALL_POLISH_WAIT
-#define MPCQP_SMALL_POLISH_WAIT 0  // passes a ready controller waits for the others of its wavefront before the attempt is made without them (0: for ever)
-#endif
-#ifndef MPCQP_SMALL_POLISH_Y
-#define MPCQP_SMALL_POLISH_Y 0     // ... of the variant with dense rows: measured slower (C2 shapes with soft ymax, 65536: 4.55 -> 5.09 ms although 12.4 -> 10.7 iterations: a round costs two passes over the dense rows in LDS)
-#endif
 #ifndef MPCQP_POLISH_MU
 #define MPCQP_POLISH_MU 1e-7
 #endif
@@ -62,8 +50,10 @@ MPCQP_HD inline size_t small_group_doubles(const Dims& d, bool hasy) {
 MPCQP_HD inline size_t small_lds_doubles(const Dims& d, bool hasy = false) { return (size_t)SMALL_GPW * small_group_doubles(d, hasy); }
 
 // KYS: Y-row slots per lane (0: the variant without output-bound rows; 2, 3, 4: nY <= 16 KYS)
-// POL: with the active-set polish (the throughput variant k_step_small; the grids of at most one wavefront per SIMD and the dense-row
-// variant run without it, see MPCQP_SMALL_POLISH)
+// POL: with the active-set polish, one attempt per wavefront (the throughput variant k_step_small; C2, 65536 controllers: 13.7 -> 9.9
+// factorisations, 1.09 -> 0.98 ms).  Not in the one-wave-per-SIMD variant: a launch of <= 4096 controllers lasts as long as its slowest
+// wavefront, and that one pays for failed attempts on top of its interior-point passes (1024 controllers: 0.088 ms without, 0.109 ms
+// with polish).  Not in the variant with dense rows either: measured slower there ("Variants measured and removed").
 template <class W, int NX, int KYS = 0, bool POL = false>
 MPCQP_HD void step_small_body(W& w, const Dims& d, const Model& m, const StepIO& io, int wg, double* smem) {
     constexpr bool HASY = KYS > 0;
@@ -383,7 +373,7 @@ MPCQP_HD void step_small_body(W& w, const Dims& d, const Model& m, const StepIO&
         }
     }
     const double delta = d.dual_reg;
-    int st = 1, it = 0, npol = 0, waited = 0;
+    int st = 1, it = 0, npol = 0;
     bool done = false;
     double polmu_next = MPCQP_POLISH_MU, polished = 0.0;
     double laststep = 1e300, rdn_prev = 1e300, rpn_prev = 1e300, lastscale = 1.0, rpn = 0.0;
@@ -506,7 +496,6 @@ MPCQP_HD void step_small_body(W& w, const Dims& d, const Model& m, const StepIO&
                 laststep <= 1e-6) { st = 0; done = true; }
         }
         if (!w.any(!done)) break;
-#if MPCQP_SMALL_POLISH
         // ---- active-set polish (Step::polish of mpcqp_bodies.h, oracle/linmpc_ref.c): once the gap is below MPCQP_POLISH_MU the rows
         // with λ > s are taken as the active set A and the equality-constrained QP on A is solved by Newton steps on its
         // augmented Lagrangian (ρ = 1e10, exact residuals every round); the point is accepted with the KKT conditions of the
@@ -514,8 +503,8 @@ MPCQP_HD void step_small_body(W& w, const Dims& d, const Model& m, const StepIO&
         // unfinished one is ready for it (a ready controller iterates on while it waits: measured on C2, an attempt costs two
         // passes, so a wavefront should pay for one attempt, not for one per controller).
         {
-            const bool want = POL && (MPCQP_SMALL_POLISH_Y || !HASY) && !done && !norows && !(d.flags & 16u) && mu <= polmu_next && rpn <= MPCQP_POLISH_RP * nh && npol < 4;
-            if (w.any(want) && (!w.any(!done && !want) || (MPCQP_SMALL_POLISH_WAIT > 0 && w.any(want && ++waited >= MPCQP_SMALL_POLISH_WAIT)))) {
+            const bool want = POL && !HASY && !done && !norows && !(d.flags & 16u) && mu <= polmu_next && rpn <= MPCQP_POLISH_RP * nh && npol < 4;
+            if (w.any(want) && !w.any(!done && !want)) {
                 constexpr double rho = 1e10;
                 const bool A0 = want && p0 && l0 > s0, A1 = want && p1 && l1 > s1, A2 = want && p2 && l2 > s2, A3 = want && p3 && l3 > s3;
                 bool yA0[KYM], yA1[KYM];
@@ -597,12 +586,11 @@ MPCQP_HD void step_small_body(W& w, const Dims& d, const Model& m, const StepIO&
                     const bool anybad = w.rmax(bad ? 1.0 : 0.0) > 0.0;
                     okp = okp && !anybad;
                 }
-                if (want) { ++npol; polmu_next = 1e-2 * mu; waited = 0; }
+                if (want) { ++npol; polmu_next = 1e-2 * mu; }
                 if (okp) { z = zp; st = 0; done = true; it = pass + npol; polished = 1.0; }
                 if (!w.any(!done)) break;
             }
         }
-#endif
         // ---- Φ = H̃ + Gᵀ D̃ G, Φ⁻¹
         const RowD d0 = rowd(p0, s0, l0), d1 = rowd(p1, s1, l1), d2 = rowd(p2, s2, l2), d3 = rowd(p3, s3, l3);
         Row Phi;

@@ -22,17 +22,6 @@
 // profiles/r3/outline_rocgdb.txt; tests/test_gpu_parity.py::test_families_near_wave_limit).  The inliner's size
 // heuristics had left cholesky() / EtDE_add() out of line in the larger specialisations (nZ~ > 48).
 #define MPCQP_HD __host__ __device__ __attribute__((always_inline))
-// (investigation of that miscompilation only: -DMPCQP_OUTLINE=1 puts cholesky(), =2 EtDE_add(), =3 both out of line)
-#if defined(__HIP_DEVICE_COMPILE__) && defined(MPCQP_OUTLINE) && (MPCQP_OUTLINE & 1)
-#define MPCQP_HD_CHOL __host__ __device__ __attribute__((noinline))
-#else
-#define MPCQP_HD_CHOL MPCQP_HD
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && defined(MPCQP_OUTLINE) && (MPCQP_OUTLINE & 2)
-#define MPCQP_HD_ETDE __host__ __device__ __attribute__((noinline))
-#else
-#define MPCQP_HD_ETDE MPCQP_HD
-#endif
 #define MPCQP_UNROLL _Pragma("unroll")
 #define MPCQP_UNROLL4 _Pragma("unroll 4")
 #define MPCQP_NOUNROLL _Pragma("nounroll")
@@ -46,8 +35,6 @@
 #else
 #define MPCQP_SCHED_FENCE() ((void)0)
 #define MPCQP_HD
-#define MPCQP_HD_CHOL
-#define MPCQP_HD_ETDE
 #define MPCQP_UNROLL
 #define MPCQP_UNROLL4
 #define MPCQP_NOUNROLL
@@ -55,7 +42,7 @@
 
 // Revision of the kernel sources / device structs: part of the name of cached on-demand
 // specialisations, so that objects built from older sources are never loaded.
-#define MPCQP_KERNEL_REV 12       // 12: matrix-core operands of E'DE in registers (MPCQP_ETDE_VREG); 11: on-demand objects compiled with the pragma-unroll threshold lifted (no scratch arrays / flat accesses from eight tile rows on); 10: the row eps >= 0 rides in a Ŷ group (eps_host_group); 9: a blocked step (alpha < 1/2) no longer passes the last-step test; 8: MPCQP_FLAG_KEEP_ITERATE
+#define MPCQP_KERNEL_REV 12       // 12: matrix-core operands of E'DE in registers (EtDE_add_mfma, register-operand form); 11: on-demand objects compiled with the pragma-unroll threshold lifted (no scratch arrays / flat accesses from eight tile rows on); 10: the row eps >= 0 rides in a Ŷ group (eps_host_group); 9: a blocked step (alpha < 1/2) no longer passes the last-step test; 8: MPCQP_FLAG_KEEP_ITERATE
 
 namespace mpcqp {
 

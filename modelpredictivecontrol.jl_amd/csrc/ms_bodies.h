@@ -52,12 +52,6 @@
 #define MPCQP_MS_LDS_SHARE (40 * 1024)   // horizon-long data stay in LDS up to this many bytes per wavefront (160 KB / 4: measured
                                          // on C2 shapes, 24 KB: 29 ms in LDS against 70 ms through the HBM scratch for 8192 controllers)
 #endif
-#ifndef MPCQP_MS_ADAPT_DELTA
-#define MPCQP_MS_ADAPT_DELTA 0      // (experiment: delta / 10 when r_p stalls at small mu -- fewer flagged solves on C3, but randomised family 1 then wanders at mu < 1e-13: off)
-#endif
-#ifndef MPCQP_MS_POLISH
-#define MPCQP_MS_POLISH 1         // active-set polish of the interior-point iterate (MsStep::polish)
-#endif
 #ifndef MPCQP_MS_POLISH_RHO
 #define MPCQP_MS_POLISH_RHO 1e8   // penalty of the polish's method of multipliers.  (Step::polish uses 1e10 on the condensed Phi; the cost-to-go of
                                   // the Riccati sweep sums the penalty over the stages and Lam = R + B'P B hides the O(0.04) curvature of a free move
@@ -72,9 +66,6 @@
 #endif
 #ifndef MPCQP_MS_POLISH_RD
 #define MPCQP_MS_POLISH_RD 1e-13  // relative dual residual the polished point is accepted at
-#endif
-#ifndef MPCQP_MS_REFINE
-#define MPCQP_MS_REFINE 0         // steps of iterative refinement per Newton solve (MsStep::newton; measured: no gain, see there)
 #endif
 
 namespace mpcqp {
@@ -102,7 +93,7 @@ struct MsCarve {
     int gX, gV, gDU;                    // gradient of the current solve
     int fX, fV, fDU;                    // border column phi
     int cX, cV;                         // defects c_t
-    int eX, eV, eDU, mX, mV, hDU;       // correction of a Newton solve (iterative refinement), its nu; the solve's own g_u
+    int eX, eV, eDU, mX, mV, hDU;       // (unused, zero-sized: dropping them changes the kernels' scratch layout)
     int gv;                             // g_t (x part), [Hp][nx]
     int ry, ru;                         // targets: C^ x - ry[t] with ry = R^y - D^d d^ (nY); u - ru (nU)
     int QY, QV, RD;                     // stage Hessian diagonals: output weight 2M + D_Y (nY), 2L + D_U (nU), 2N + D_dU (nDU)
@@ -183,7 +174,7 @@ MPCQP_HD inline MsCarve make_ms_carve(const Dims& d, const Model& m) {
     c.gX = take(nX); c.gV = take(nV); c.gDU = take(nDU);
     c.fX = take(nX); c.fV = take(nV); c.fDU = take(nDU);
     c.cX = take(nX); c.cV = take(nV);
-    { const int R_ = MPCQP_MS_REFINE ? 1 : 0; c.eX = take(R_ * nX); c.eV = take(R_ * nV); c.eDU = take(R_ * nDU); c.mX = take(R_ * nX); c.mV = take(R_ * nV); c.hDU = take(R_ * nDU); }
+    c.eX = c.eV = c.eDU = c.mX = c.mV = c.hDU = o;
     c.gv = take(nX);
     c.ry = take(nY); c.ru = take(nV);
     c.QY = take(nY); c.QV = take(nV); c.RD = take(nDU);
@@ -792,7 +783,9 @@ struct MsStep {
                 }
                 w.sync_lds();
                 // one refinement step of the gain: K -= Lam^-1 (S_u. + Lam K)  (the explicit inverse of a Lam with 1/delta-size
-                // entries next to O(0.1) ones leaves eps cond(Lam) in K; a row held at D~ = 1/delta multiplies that by 1e12)
+                // entries next to O(0.1) ones leaves eps cond(Lam) in K; a row held at D~ = 1/delta multiplies that by 1e12.
+                // Without it the control rows of the Newton system kept an O(1) residual as mu -> 0 and the iterates wandered
+                // at mu < 1e-13; with it (and k refined the same way) the dual residual reaches 1e-14)
                 for (int idx = w.lane; idx < nu * ns; idx += WAVE) {
                     const int a = idx / ns, col = idx - a * ns;
                     double acc = S[a * ns + col];
@@ -1210,68 +1203,24 @@ struct MsStep {
     // One Newton solve with the current factor: rc(row) given; on return dX, dV, dDU, deps hold the step, nX, nV the
     // multipliers nu+, rgd[row] = (G dz)[row].
     template <class Fn>
-    MPCQP_HD void newton(Fn rc, double schur, double phiee) {
+    MPCQP_HD void newton(Fn rc, double schur) {
         // g^ = cost gradient + G'(lam + D~ rp - wi rc)
         const double ge0 = Gt_apply([&](int r) { return rl[r] + rwi[r] * (rl[r] * rrp[r] - rc(r)); }, bg + c.gX, bg + c.gV, bg + c.gDU, true);
-        solve(ge0, schur, phiee);
+        solve(ge0, schur);
     }
 
     // the Newton system solved for the gradient in gX, gV, gDU, ge0 (defects of the iterate in cX, cV) with the current factor
     // and psi: dX, dV, dDU, deps <- the step, nX, nV <- the multipliers nu+, rgd[row] <- (G dz)[row]
-    MPCQP_HD void solve(double ge0, double schur, double phiee) {
+    MPCQP_HD void solve(double ge0, double schur) {
         sweep(bg + c.gX, bg + c.gV, bg + c.gDU, use_defect, bg + c.dX, bg + c.dV, bg + c.dDU, bg + c.nX, bg + c.nV);
-        if (MPCQP_MS_REFINE) for (int i = w.lane; i < nDU; i += WAVE) bg[c.hDU + i] = bg[c.gDU + i];
         deps = 0.0;
-        const double ge_keep = d.neps ? 2.0 * m.Cwt[b] * eps + ge0 : 0.0;
         if (d.neps) {
-            const double ge = ge_keep;
+            const double ge = 2.0 * m.Cwt[b] * eps + ge0;
             const double fy = dot_z(bg + c.fX, bg + c.fV, bg + c.fDU, bg + c.dX, bg + c.dV, bg + c.dDU);
             deps = -(ge + fy) / schur;
             for (int i = w.lane; i < nXt; i += WAVE) { bg[c.dX + i] += deps * bg[c.pX + i]; bg[c.nX + i] += deps * bg[c.qX + i]; }
             for (int i = w.lane; i < nVt; i += WAVE) { bg[c.dV + i] += deps * bg[c.pV + i]; bg[c.nV + i] += deps * bg[c.qV + i]; }
             for (int i = w.lane; i < nDU; i += WAVE) bg[c.dDU + i] += deps * bg[c.pDU + i];
-            w.sync();
-        }
-        // Optional iterative refinement of the whole Newton solve (MPCQP_MS_REFINE, off: not needed once the gains are
-        // refined, see factor()).  History: with K = -Lam^-1 S_u. from the explicit inverse alone, the control rows of the
-        // Newton system were left with an O(1) residual as mu -> 0 (0.99 against terms of 6.6 at mu = 1e-9) -- eps cond(Lam)
-        // of relative error in K, times the 1e-5-size state step, times the 1e12 of a row held at D~ = 1/delta -- the dual
-        // residual grew instead of shrinking and the iterates wandered at mu < 1e-13.  One refinement step of K and k
-        // against the stored Lam brings that residual to 1e-10 .. 1e-14 and the dual residual to 1e-14 (quadratic
-        // convergence to the end).  The state rows hold by construction (adjoint nu+), so what is left lives in the control
-        // rows and the slack row:
-        //     r_u = R du + g_u + Bbar' nu+ + phi_u deps,     r_e = g_e + phi'dz + Phi_ee deps
-        // and the correction solves the same system for it (one more sweep with the same factor).
-        for (int pass = 0; pass < MPCQP_MS_REFINE; ++pass) {
-            for (int i = w.lane; i < nXt; i += WAVE) bg[c.gX + i] = 0.0;
-            for (int i = w.lane; i < nVt; i += WAVE) bg[c.gV + i] = 0.0;
-            double mxr = 0.0;
-            for (int i = w.lane; i < nDU; i += WAVE) {
-                const int j = i / nu, cc = i - j * nu, t = jlt[j];
-                double an = bg[c.nV + t * nu + cc];
-                for (int k = 0; k < nx; ++k) an += Bu[k + nx * cc] * bg[c.nX + t * nx + k];
-                const double r = bg[c.RD + i] * bg[c.dDU + i] + bg[c.hDU + i] + an + bg[c.fDU + i] * deps;
-                bg[c.eDU + i] = r;
-                mxr = fmax(mxr, fabs(r));
-            }
-            w.sync();
-            for (int i = w.lane; i < nDU; i += WAVE) bg[c.gDU + i] = bg[c.eDU + i];
-            double re = 0.0;
-            if (d.neps) re = ge_keep + dot_z(bg + c.fX, bg + c.fV, bg + c.fDU, bg + c.dX, bg + c.dV, bg + c.dDU) + phiee * deps;
-            w.sync();
-#if !defined(__HIP_DEVICE_COMPILE__) && defined(MPCQP_DEBUG_MS)
-            { mxr = w.maxv(mxr); if (w.lane == 0 && b == MPCQP_DEBUG_MS) printf("      newton control-row residual %.3e slack row %.3e deps %.3e\n", mxr, re, deps); }
-#endif
-            sweep(bg + c.gX, bg + c.gV, bg + c.gDU, false, bg + c.eX, bg + c.eV, bg + c.eDU, bg + c.mX, bg + c.mV);
-            double de = 0.0;
-            if (d.neps) {
-                const double fy = dot_z(bg + c.fX, bg + c.fV, bg + c.fDU, bg + c.eX, bg + c.eV, bg + c.eDU);
-                de = -(re + fy) / schur;
-            }
-            for (int i = w.lane; i < nXt; i += WAVE) { bg[c.dX + i] += bg[c.eX + i] + de * bg[c.pX + i]; bg[c.nX + i] += bg[c.mX + i] + de * bg[c.qX + i]; }
-            for (int i = w.lane; i < nVt; i += WAVE) { bg[c.dV + i] += bg[c.eV + i] + de * bg[c.pV + i]; bg[c.nV + i] += bg[c.mV + i] + de * bg[c.qV + i]; }
-            for (int i = w.lane; i < nDU; i += WAVE) bg[c.dDU + i] += bg[c.eDU + i] + de * bg[c.pDU + i];
-            deps += de;
             w.sync();
         }
         G_dz();
@@ -1444,7 +1393,7 @@ struct MsStep {
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(MPCQP_DEBUG_MS)
                 if (w.lane == 0 && b == MPCQP_DEBUG_MS) printf("  [ms] polish set %d round %d rpa %.3e cn %.3e\n", fact, round, rpa, cn);
 #endif
-                solve(ge, schur, phiee);
+                solve(ge, schur);
                 ++nsteps;
                 for (int k = w.lane; k < nDU; k += WAVE) DU[k] += bg[c.dDU + k];
                 for (int i = w.lane; i < nXt; i += WAVE) X[i] += bg[c.dX + i];
@@ -1507,7 +1456,7 @@ struct MsStep {
             rl[r] = 10.0 / rs[r];
         });
         w.sync();
-        double step_c = 1e300, zabs_c = 0.0, rd_prev = 1e300, rp_prev = 1e300, alpha_prev = 0.0, rd_best = 1e300;
+        double step_c = 1e300, zabs_c = 0.0, rd_prev = 1e300, alpha_prev = 0.0, rd_best = 1e300;
         int rd_flat = 0, npolish = 0;
         double polmu_next = 1e-6;
         const int max_iter = mact ? d.max_iter : 1;
@@ -1529,14 +1478,6 @@ struct MsStep {
             //  with the iteration limit, not returned as optimal)
             const bool rd_stalled = ((rdn >= 0.5 * rd_prev && alpha_prev >= 0.9) || rd_flat >= 3) && rdn <= 1e-5 * ndd;
             rd_prev = rdn;
-            // The primal residual of a dual-regularised iteration follows r_p <- (1 - alpha) r_p + alpha delta dlam: once the
-            // gap is small and r_p no longer shrinks although the steps are long, it sits on delta dlam -- rows whose
-            // multipliers still have a long way to go (soft rows, 2 Cwt eps ~ 1e5) -- and the iteration has become a method
-            // of multipliers with penalty 1/delta: a ten times smaller delta makes it ten times faster (down to 1e-12; a
-            // factorisation that breaks raises it again, below).
-            if (MPCQP_MS_ADAPT_DELTA && mu <= 1e-6 && rpn > 10.0 * d.res_tol * nh && rpn >= 0.5 * rp_prev && alpha_prev >= 0.5 && delta > 1e-12)
-                delta *= 0.1;
-            rp_prev = rpn;
             const bool conv = mu <= d.gap_tol && (rdn <= d.res_tol * ndd || rd_stalled) && rpn <= 10.0 * d.res_tol * nh &&
                               cn <= d.res_tol * xs && step_c <= 1e-6 * fmax(1.0, zabs_c);
             if (conv && mact) { status = ST_OPTIMAL; break; }
@@ -1544,7 +1485,7 @@ struct MsStep {
             if (!mact && it > 0) { status = ST_OPTIMAL; it = 0; break; }
             if (it >= max_iter) break;
             // Active-set polish once the gap is small: first at mu <= 1e-6, again after every further factor 100 (Step::run)
-            if (MPCQP_MS_POLISH && mact && mu <= polmu_next && rpn <= 1e-6 * nh && cn <= 1e-6 * xs && npolish < MPCQP_MS_POLISH_BUDGET && !(d.flags & 16u)) {
+            if (mact && mu <= polmu_next && rpn <= 1e-6 * nh && cn <= 1e-6 * xs && npolish < MPCQP_MS_POLISH_BUDGET && !(d.flags & 16u)) {
                 polmu_next = 1e-2 * mu;
                 const long long t6_ = clk();
                 const bool pok_ = polish(xs, npolish);
@@ -1582,7 +1523,7 @@ struct MsStep {
                 const double cpp = pass ? 1.0 : 0.0;
                 if (pass == 0) for_rows([&](int, int, int r) { rpp[r] = 0.0; });
                 w.sync();
-                newton([&](int r) { return fma(cpp, rpp[r], fma(rs[r], rl[r], -smu)); }, schur, phiee);
+                newton([&](int r) { return fma(cpp, rpp[r], fma(rs[r], rl[r], -smu)); }, schur);
                 double ppsum = 0.0;
                 tmax = pass ? 1e-300 : 1.0;
                 for_rows([&](int, int, int r) {

@@ -108,7 +108,7 @@ def test_slack_row_of_shapes_with_nDU_a_multiple_of_16(name, hiplib):
 @pytest.mark.parametrize("name,pattern", [("4,1,1,16,16", "c3"), ("6,2,3,32,31", "c3"), ("6,3,3,21,21", "all"), ("6,2,2,40,32", "yband"),
                                           ("8,4,4,24,20", "c3"), ("8,3,2,45,42", "all"), ("8,5,4,20,16", "box"),
                                           ("12,3,3,50,50", "c3"), ("12,2,2,70,70", "all"),
-                                          # (round 6: the register-operand form of E'DE, MPCQP_ETDE_VREG, on every nu that divides 16 and
+                                          # (round 6: the register-operand form of EtDE_add_mfma, on every nu that divides 16 and
                                           #  on ny = 8 -- the BASELINE shapes and the random families only have nu = ny = 4 of these)
                                           ("6,2,4,20,12", "all"), ("8,8,4,10,8", "c3"), ("6,2,8,12,10", "all"), ("16,16,4,6,3", "c3"),
                                           ("6,1,4,20,20", "c3")])
@@ -716,7 +716,7 @@ def test_families_beyond_two_rows_per_lane(seed, hiplib):
 @pytest.mark.parametrize("seed", [5001, 5005, 5006, 5007, 5010, 5011])
 def test_random_families_with_four_outputs(seed, hiplib):
     """Round 6: E'DE takes its matrix-core operands from registers when ny is a multiple of 4 and nu divides 16
-    (MPCQP_ETDE_VREG) -- shapes the other random families never draw (ny <= 3).  Families with ny = 4, nu in {1, 2, 4}, default move
+    (EtDE_add_mfma, register-operand form) -- shapes the other random families never draw (ny <= 3).  Families with ny = 4, nu in {1, 2, 4}, default move
     blocking or a blocking vector (the latter keeps the operands-from-LDS form), every bound pattern, against the independent oracle."""
     from tests.parity_util import run_random_case
     kinds = []
