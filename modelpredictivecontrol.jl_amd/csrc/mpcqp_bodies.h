@@ -530,7 +530,7 @@ struct Qp {
     // out[r] = sum_k E[r,k] v[k]   (r < nY; v has >= nDU entries)
     // (a team of wavefronts splits the row slots of the zero-padded form: W::NTEAM, mpcqp_devwave.h)
     MPCQP_HD void E_apply(const double* v, double* out) {
-        if constexpr (W::NTEAM > 1) w.post(TJ_EV, (int)(v - sm), (int)(out - sm));
+        if constexpr (W::NTEAM > 1) { static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_EV, (int)(v - sm), (int)(out - sm)); }
         E_apply_share(v, out);
         if constexpr (W::NTEAM > 1) w.join();
     }
@@ -619,7 +619,7 @@ struct Qp {
     // later block columns just start contributing later), so wv[t,a] is a broadcast LDS read and
     // there is no divergent branch in the loop.
     MPCQP_HD void Et_apply_add(const double* wv, double* out, double scale = 1.0, int t_hi = -1) {
-        if constexpr (W::NTEAM > 1) w.post(TJ_ETW, (int)(wv - sm), (int)(out - sm), t_hi, 0, scale);
+        if constexpr (W::NTEAM > 1) { static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_ETW, (int)(wv - sm), (int)(out - sm), t_hi, 0, scale); }
         Et_apply_share(wv, out, scale, t_hi);
         if constexpr (W::NTEAM > 1) w.join();
     }
@@ -763,7 +763,7 @@ struct Qp {
     __device__ __forceinline__ int EtDE_add_mfma(const double* dd, double* P, double scale, const double* tb,
                                                  const double* Hg = nullptr, bool ow = false) {
         // (a team of wavefronts splits the passes over the tile rows: W::NTEAM, mpcqp_devwave.h)
-        if constexpr (W::NTEAM > 1) w.post(TJ_ETDE, (int)(dd - sm), (int)(P - sm), tb ? (int)(tb - sm) : 0, (ow ? 1 : 0) | (Hg ? 2 : 0) | (tb ? 4 : 0), scale);
+        if constexpr (W::NTEAM > 1) { static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_ETDE, (int)(dd - sm), (int)(P - sm), tb ? (int)(tb - sm) : 0, (ow ? 1 : 0) | (Hg ? 2 : 0) | (tb ? 4 : 0), scale); }
         const int e = EtDE_share(dd, P, scale, tb ? tb : dd, Hg, ow, tb != nullptr);
         if constexpr (W::NTEAM > 1) w.join();
         return e;
@@ -2138,7 +2138,7 @@ struct Step {
 
     // ---- Phi <- H̃ (global -> LDS) ------------------------------------------------------------
     MPCQP_HD void load_H() {
-        if constexpr (W::NTEAM > 1) w.post(TJ_LOADH);
+        if constexpr (W::NTEAM > 1) { static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_LOADH); }
         load_H_share();
         if constexpr (W::NTEAM > 1) w.join();
         w.sync();
@@ -2298,20 +2298,20 @@ struct Step {
             double* tU = sm + c.tA[P_U];
             w.sync();
             block_scan(tU, tU, true);              // (nothing reads the per-block sums after this point: in place)
-            if constexpr (W::NTEAM > 1) w.post(TJ_UROWS);
+            if constexpr (W::NTEAM > 1) { static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_UROWS); }
             GtDG_urows_share();
             if constexpr (W::NTEAM > 1) w.join();
         }
         if (qp.pair_on(P_X)) {
             w.sync();
-            if constexpr (W::NTEAM > 1) w.post(TJ_XROWS);
+            if constexpr (W::NTEAM > 1) { static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_XROWS); }
             GtDG_xrows_share();
             if constexpr (W::NTEAM > 1) w.join();
         }
         if constexpr (has_w<DM>()) {
             if (qp.pair_on(P_W)) {        // E_w' dW E_w, rows formed on the fly (set-up-grade path)
                 w.sync();
-                if constexpr (W::NTEAM > 1) w.post(TJ_WROWS);
+                if constexpr (W::NTEAM > 1) { static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_WROWS); }
                 GtDG_wrows_share();
                 if constexpr (W::NTEAM > 1) w.join();
             }
@@ -2393,7 +2393,7 @@ struct Step {
     template <int P>
     __device__ __forceinline__ void chol_panel_update() {
         // (a team of wavefronts splits the row tiles below the panel: W::NTEAM, mpcqp_devwave.h)
-        if constexpr (W::NTEAM > 1) w.post(TJ_PANEL, P);
+        if constexpr (W::NTEAM > 1) { static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_PANEL, P); }
         chol_panel_share<P>();
         if constexpr (W::NTEAM > 1) w.join();
     }
@@ -3021,7 +3021,7 @@ struct Step {
                 if constexpr (DIAG) chol_big_panel_diag<P, NS>(thr, broke);                 // (ends with a wave fence: its stores are issued)
                 else chol_big_panel_slots<P, NS, (so_ + 1 < NS ? so_ + 1 : NS)>(thr, broke);
                 if constexpr (DIAG ? DM::nZ - 16 * P > 16 : so_ + 1 < NS) {
-                    w.post(TJ_PANELROWS, P);
+                    static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_PANELROWS, P);
                     chol_big_panel_rows<P, NS>();
                     w.join();
                 }
@@ -3255,7 +3255,7 @@ struct Step {
         double mx = 0.0, sc = 0.0;
         if constexpr (W::NTEAM > 1) {
             if (Hp_) {                  // the rows of H̃ z over the team, then the rest as if rd held H̃ z already
-                w.post(TJ_HZ, Hp_ == Phi ? 1 : 0);
+                static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_HZ, Hp_ == Phi ? 1 : 0);
                 if (Hp_ == Phi) Hz_rows_share(Phi);
                 else Hz_rows_share(m.Hpk + (size_t)b * d.npk);          // (the only other caller's argument: polish)
                 w.join();

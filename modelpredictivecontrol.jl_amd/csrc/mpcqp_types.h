@@ -48,6 +48,9 @@ namespace mpcqp {
 
 // jobs a team's wavefront 0 hands to its helpers (DevWaveT, mpcqp_devwave.h; W::NTEAM == 1: never posted)
 enum TeamJob { TJ_EXIT = 0, TJ_ETDE = 1, TJ_PANEL = 2, TJ_EV = 3, TJ_ETW = 4, TJ_UROWS = 5, TJ_WROWS = 6, TJ_XROWS = 7, TJ_PANELROWS = 8, TJ_LOADH = 9, TJ_HZ = 10 };
+// every call that posts a job asserts W::WV == 0 at compile time: a posting call reached from a helper's share (team_helper ->
+// *_share on W::WV != 0) would wait at the barrier of post() for a wavefront 0 that is waiting for the helper
+#define MPCQP_POST_WV0 "only wavefront 0 of a team posts jobs: a helper that reached this call would wait at the barrier for ever"
 
 
 enum { P_BOX = 0, P_U = 1, P_DU = 2, P_Y = 3, P_X = 4, P_W = 5, NPAIR = 6, NGROUP = 12 };

@@ -246,11 +246,16 @@ def run_custom_constraint_cases(lib=None, B=2, Hp=50, which=(0, 1, 2, 3)):
     return worst
 
 
-def run_soft_custom_constraints(lib=None, B=2, seed=4, kinds=None, Hp=8, Hc=(1, 2, 2), terminal=False, periods=3):
+def run_soft_custom_constraints(lib=None, B=2, seed=4, kinds=None, Hp=8, Hc=(1, 2, 2), terminal=False, periods=3,
+                                distinct_x0=False, oracle=True, record=None):
     """Two soft custom rows mixing outputs, inputs, a measured disturbance and the set point, on top
     of ordinary u / y constraints, against the oracle (exercises the ϵ row of the custom block).
     Hp, Hc: the horizons (round 6: Hp = Hc = 60, nZ̃ = 121 puts the handle on a team of wavefronts, whose helpers take the
-    custom-row and terminal-row parts of the Newton matrix); terminal: a soft bound on one terminal state on top."""
+    custom-row and terminal-row parts of the Newton matrix); terminal: a soft bound on one terminal state on top.
+    distinct_x0: every member starts from a state of its own (member 0 keeps the family's; the others draw from generators of
+    their own, so the family's draws stay what they were) and EVERY member is compared with an oracle of its own, not only
+    member B - 1.  oracle=False: no oracle at all, the loop is closed with the controller's own inputs (returns None);
+    record: a list that receives `record_period(gpu)` of every period (tests/team_util.py)."""
     from oracle import estim as es
     rng = np.random.default_rng(seed)
     A = np.diag([0.85, 0.6, 0.3]); Bu = rng.standard_normal((3, 2)); C = rng.standard_normal((2, 3))
@@ -262,29 +267,61 @@ def run_soft_custom_constraints(lib=None, B=2, seed=4, kinds=None, Hp=8, Hc=(1, 
     kw = dict(Hp=Hp, Hc=list(Hc) if not np.isscalar(Hc) else int(Hc), Lwt=[0.05, 0.02], uop=model.uop, yop=model.yop, dop=model.dop,
               xhop=kf.xhop, fhop=kf.fhop, Wy=Wy, Wu=Wu, Wd=Wd, Wr=Wr)
     rep = lambda a: np.broadcast_to(a, (B,) + a.shape).copy()
-    orc = cd.LinMPCOracle(kf.Ah, kf.Bhu, kf.Ch, kf.Bhd, kf.Dhd, **kw)
+    nor = (B if distinct_x0 else 1) if oracle else 0           # oracles: one per member, or one for the shared state
+    orcs = [cd.LinMPCOracle(kf.Ah, kf.Bhu, kf.Ch, kf.Bhd, kf.Dhd, **kw) for _ in range(nor)]
     gpu = mpcqp.BatchLinMPC(rep(kf.Ah), rep(kf.Bhu), rep(kf.Ch), rep(kf.Bhd), rep(kf.Dhd), lib=lib, **kw)
     con = dict(umin=[-0.6, -1.0], umax=[1.4, 0.9], ymax=[2.6, 1.8], wmin=[0.2, -np.inf], wmax=[1.5, 0.9],
                c_wmin=[0.7, 1.0], c_wmax=[1.3, 0.4])
     if terminal:
         xm = np.full(kf.nxh, np.inf); xm[0] = 0.4
         con["xhatmax"] = kf.xhop + xm
-    orc.setconstraint(**con); gpu.setconstraint(**{("x̂max" if k == "xhatmax" else k): v for k, v in con.items()})
+    for orc in orcs:
+        orc.setconstraint(**con)
+    gpu.setconstraint(**{("x̂max" if k == "xhatmax" else k): v for k, v in con.items()})
     x0 = 0.3 * rng.standard_normal(kf.nxh)
-    gpu.initstate([0.6, 0.0]); orc.lastu0 = np.array([0.6, 0.0]) - model.uop
+    X0 = np.tile(x0, (B, 1))
+    if distinct_x0:
+        for i in range(1, B):
+            X0[i] = 0.3 * np.random.default_rng([seed, 90210, i]).standard_normal(kf.nxh)
+    gpu.initstate([0.6, 0.0])
+    for orc in orcs:
+        orc.lastu0 = np.array([0.6, 0.0]) - model.uop
+    members = list(range(B)) if distinct_x0 else [B - 1]         # member compared with orcs[j]
     worst = 0.0
     for k in range(periods):
         ry, d = [2.5 + 0.2 * k, 0.4], [0.5 - 0.1 * k]
-        ug = gpu.moveinput(np.tile(x0, (B, 1)), ry, d, want_info=True)
-        uo = orc.moveinput(x0, ry, d)
+        ug = gpu.moveinput(X0, ry, d, want_info=True)
         assert np.all(gpu.status == 0)
-        ig, io = gpu.getinfo(), orc.getinfo()
-        worst = max(worst, np.abs(gpu.Z[B - 1] - orc.Zt).max() / max(1.0, np.abs(orc.Zt).max()),
-                    np.abs(ug[B - 1] - uo).max(), np.abs(ig["W"][B - 1] - io["W"]).max())
-        x0 = kf.Ah @ x0 + kf.Bhu @ (uo - model.uop) * 0.5
+        if record is not None:
+            record.append(record_period(gpu))
+        if not oracle:
+            X0 = X0 @ kf.Ah.T + (ug - model.uop) @ kf.Bhu.T * 0.5
+            continue
+        ig = gpu.getinfo()
+        Xn = X0.copy()
+        for orc, i in zip(orcs, members):
+            uo = orc.moveinput(X0[i], ry, d)
+            io = orc.getinfo()
+            worst = max(worst, np.abs(gpu.Z[i] - orc.Zt).max() / max(1.0, np.abs(orc.Zt).max()),
+                        np.abs(ug[i] - uo).max(), np.abs(ig["W"][i] - io["W"]).max())
+            xn = kf.Ah @ X0[i] + kf.Bhu @ (uo - model.uop) * 0.5
+            if distinct_x0:
+                Xn[i] = xn
+            else:
+                Xn[:] = xn
+        X0 = Xn
     if kinds is not None:
         kinds.append(gpu.hd.kernel_kind())
-    return worst
+    return worst if oracle else None
+
+
+def record_period(mpc):
+    """Everything one period of a BatchLinMPC left behind, for bit-for-bit comparisons between kernel variants
+    (tests/team_util.py): Z̃, u0, status, iterations, Ŷ and J of getinfo (moveinput(..., want_info=True)) and the
+    MPCQP_GET_AUDIT block."""
+    info = mpc.getinfo()
+    return {"Z": mpc.Z.copy(), "u0": mpc.lastu0.copy(), "status": mpc.status.copy(), "iters": mpc.iters.copy(),
+            "Yhat": np.array(info["Ŷ"]), "J": np.array(info["J"]), "audit": mpc.hd.get(mpcqp.api.GET_AUDIT)}
 
 
 def closed_loop_pair(cfg, bt, steps, lib=None, noise=0.02, seed=1, **kw):
@@ -311,7 +348,8 @@ def closed_loop_pair(cfg, bt, steps, lib=None, noise=0.02, seed=1, **kw):
 EXTRA_KW = None      # (experiments: extra BatchLinMPC keywords for run_random_case)
 
 
-def run_random_case(seed, lib=None, B=3, small=False, large=False, huge=False, kinds=None, transcription="SingleShooting", huge2=False, ny4=False):
+def run_random_case(seed, lib=None, B=3, small=False, large=False, huge=False, kinds=None, transcription="SingleShooting", huge2=False, ny4=False,
+                    custom=False, certs=None, oracle_only=False):
     """One randomly drawn controller family (dimensions, move blocking, which bounds exist, hard /
     soft mix, terminal bounds, measured disturbance, Cwt finite or Inf) as a batch of B DIFFERENT
     controllers of that family -- every member has its own model, weights, operating points, bound
@@ -319,7 +357,12 @@ def run_random_case(seed, lib=None, B=3, small=False, large=False, huge=False, k
     C-ABI and, member by member, through the oracle.  Returns the worst relative ΔU error over all
     members and steps whose oracle optimum carries an exact certificate (None if none did).
     Member 0 is drawn from the family's own generator (the instances the earlier single-controller
-    form of this test compared), the others from generators of their own."""
+    form of this test compared), the others from generators of their own.
+    custom: one or two custom linear constraint rows per step on top (Wy / Wu / Wd / Wr, bounds around the rows' operating
+    value with -Inf holes, soft when the family is soft), drawn from generators of their own ([4242, seed] and
+    [4242, seed, member]): no other draw of any family changes.  certs: a list that receives one bool per member and
+    step the oracle solved -- True when its optimum carries the active-set certificate.  oracle_only: the oracle's half
+    alone, no library and no device (to choose seeds whose every member and step is certified)."""
     from oracle import estim as es
     rng = np.random.default_rng(1000 + seed)
     nx = int(rng.integers(2, 4 if small else 7)); nu = int(rng.integers(1, 3 if small else 5))
@@ -344,6 +387,7 @@ def run_random_case(seed, lib=None, B=3, small=False, large=False, huge=False, k
             if sum(parts) > Hp:
                 parts[-1] -= sum(parts) - Hp
         Hc = [p for p in parts if p > 0] or 1
+    nw = int(np.random.default_rng([4242, seed]).integers(1, 3)) if custom else 0
     fam = {}                                # structural decisions of the family, set by member 0
 
     def decide(key, value):                 # member 0 decides, the others follow
@@ -370,6 +414,19 @@ def run_random_case(seed, lib=None, B=3, small=False, large=False, huge=False, k
         cw = 10 ** rg.uniform(3, 5.5)
         kw = dict(Hp=Hp, Hc=Hc, Mwt=Mw, Nwt=Nw, Lwt=Lw, Cwt=cw if soft else np.inf,
                   uop=model.uop, yop=model.yop, dop=model.dop, xhop=kf.xhop, fhop=kf.fhop)
+        wcon = {}
+        if custom:
+            rc = np.random.default_rng([4242, seed, idx])
+            kw.update(Wy=rc.standard_normal((nw, ny)), Wu=rc.standard_normal((nw, nu)), Wr=0.3 * rc.standard_normal((nw, ny)))
+            w_op = kw["Wy"] @ model.yop + kw["Wu"] @ model.uop + kw["Wr"] @ model.yop
+            if nd:
+                kw["Wd"] = rc.standard_normal((nw, nd))
+                w_op = w_op + kw["Wd"] @ model.dop
+            wcon["wmin"] = np.where(rc.random(nw) < 0.3, -np.inf, w_op - rc.uniform(0.5, 2.0, nw))
+            wcon["wmax"] = w_op + rc.uniform(0.5, 2.0, nw)
+            if soft:
+                wcon["c_wmin"] = rc.uniform(0.3, 1.5, nw)
+                wcon["c_wmax"] = rc.uniform(0.3, 1.5, nw)
         orc = cd.LinMPCOracle(kf.Ah, kf.Bhu, kf.Ch, kf.Bhd, kf.Dhd, **kw)
         inf_some = lambda v: np.where(rg.random(v.shape) < 0.25, np.inf * np.sign(v), v)
         con = {}
@@ -390,6 +447,7 @@ def run_random_case(seed, lib=None, B=3, small=False, large=False, huge=False, k
                             ("c_ymin", ny), ("c_ymax", ny)):
                 if base[2:] in con and decide(base, bool(rg.random() < 0.5)):
                     con[base] = rg.uniform(0.2, 1.5, n) * (rg.random(n) < 0.6 if base[2] != "y" else 1.0)
+        con.update(wcon)
         orc.setconstraint(**con)
         x0 = 0.5 * rg.standard_normal(kf.nxh)
         u_prev = model.uop + 0.2 * rg.standard_normal(nu)
@@ -399,27 +457,30 @@ def run_random_case(seed, lib=None, B=3, small=False, large=False, huge=False, k
     mem = [member(rng)] + [member(np.random.default_rng([1000 + seed, i]), i) for i in range(1, B)]
     st = lambda f: np.stack([f(m) for m in mem])
     nxh = mem[0]["kf"].nxh
-    gpu = mpcqp.BatchLinMPC(st(lambda m: m["kf"].Ah), st(lambda m: m["kf"].Bhu), st(lambda m: m["kf"].Ch),
+    wkw = {k: st(lambda m: m["kw"][k]) for k in ("Wy", "Wu", "Wd", "Wr") if k in mem[0]["kw"]}
+    gpu = None if oracle_only else mpcqp.BatchLinMPC(st(lambda m: m["kf"].Ah), st(lambda m: m["kf"].Bhu), st(lambda m: m["kf"].Ch),
                             st(lambda m: m["kf"].Bhd) if nd else None, st(lambda m: m["kf"].Dhd) if nd else None,
                             lib=lib, Hp=Hp, Hc=Hc, Mwt=st(lambda m: m["kw"]["Mwt"]), Nwt=st(lambda m: m["kw"]["Nwt"]),
                             Lwt=st(lambda m: m["kw"]["Lwt"]), Cwt=st(lambda m: m["kw"]["Cwt"]),
                             uop=st(lambda m: m["model"].uop), yop=st(lambda m: m["model"].yop),
                             dop=st(lambda m: m["model"].dop), xhop=st(lambda m: m["kf"].xhop),
-                            fhop=st(lambda m: m["kf"].fhop), transcription=transcription, **(EXTRA_KW or {}))
+                            fhop=st(lambda m: m["kf"].fhop), transcription=transcription, **wkw, **(EXTRA_KW or {}))
     gname = dict(dumin="Δumin", dumax="Δumax", c_dumin="c_Δumin", c_dumax="c_Δumax", xhatmax="x̂max")
-    gpu.setconstraint(**{gname.get(k, k): st(lambda m: m["con"][k]) for k in mem[0]["con"]})
-    gpu.initstate(st(lambda m: m["u_prev"]))
+    if gpu is not None:
+        gpu.setconstraint(**{gname.get(k, k): st(lambda m: m["con"][k]) for k in mem[0]["con"]})
+        gpu.initstate(st(lambda m: m["u_prev"]))
     worst = None
     for k in range(2):
-        if kinds is not None and k == 1:          # (the first moveinput prepared the kernel of the handle)
+        if kinds is not None and k == 1 and gpu is not None:          # (the first moveinput prepared the kernel of the handle)
             kinds.append((gpu.hd.kernel_kind(), gpu.hd.nZ))
         for m in mem:
             rg, model = m["rg"], m["model"]
             m["ry"] = model.yop + rg.standard_normal(ny) * (1.5 if k == 0 else 0.5)
             m["d"] = model.dop + 0.3 * rg.standard_normal(nd) if nd else None
             m["Dhat"] = (np.tile(m["d"], Hp) + 0.05 * rg.standard_normal(nd * Hp)) if nd else None
-        gpu.moveinput(st(lambda m: m["x0"]), st(lambda m: m["ry"]), st(lambda m: m["d"]) if nd else None,
-                      Dhat=st(lambda m: m["Dhat"]) if nd else None)
+        if gpu is not None:
+            gpu.moveinput(st(lambda m: m["x0"]), st(lambda m: m["ry"]), st(lambda m: m["d"]) if nd else None,
+                          Dhat=st(lambda m: m["Dhat"]) if nd else None)
         stop = False
         for i, m in enumerate(mem):
             orc, model = m["orc"], m["model"]
@@ -428,8 +489,13 @@ def run_random_case(seed, lib=None, B=3, small=False, large=False, huge=False, k
             if sto != 0:                  # the oracle gave up on this one (it would take its error
                 stop = True               # branch and the two loops would no longer see the same inputs)
                 break
-            assert gpu.status[i] == 0, (seed, i, gpu.status)
-            e = rel_err(gpu.Z[i:i + 1], z[None, :], orc.nDU).max()
+            if certs is not None:
+                certs.append(info["certificate"] == "active-set")
+            if gpu is None:
+                e = 0.0
+            else:
+                assert gpu.status[i] == 0, (seed, i, gpu.status)
+                e = rel_err(gpu.Z[i:i + 1], z[None, :], orc.nDU).max()
             if info["certificate"] == "active-set":
                 worst = e if worst is None else max(worst, e)
             elif e > 1e-4:                # uncertified oracle point that differs: nobody to compare
@@ -685,11 +751,14 @@ def multiple_shooting_known_answers(lib=None, B=2, Hp=1000):
     return out
 
 
-def dense_weight_case(lib=None, B=3, which=("M", "N", "L"), seed=0):
+def dense_weight_case(lib=None, B=3, which=("M", "N", "L"), seed=0, cfg=None, periods=1, oracle=True, record=None):
     """Full Hermitian weight matrices (M_Hp coupling prediction steps, N_Hc coupling moves, L_Hp coupling
     inputs/steps: construct.jl:45-93, 837-845) against the oracle, with input bounds active and a soft output
-    bound, a time-varying R̂u, different plants per controller.  Returns (worst rel ΔU error, kernel kind)."""
-    cfg = synth.Config("dense-w", nx=3, nu=2, ny=2, Hp=7, Hc=3, umin=-0.7, umax=0.7, ymax=0.9)
+    bound, a time-varying R̂u, different plants per controller.  Returns (worst rel ΔU error, kernel kind).
+    cfg: another shape than the nZ̃ = 7 one (same draws in the same order; the default keeps the shape and the draws of the
+    earlier form of this case); periods > 1: further periods from the shifted warm start, the plants driven by the
+    controller's inputs; oracle=False: no comparison (the error returned is None); record: see record_period."""
+    cfg = cfg or synth.Config("dense-w", nx=3, nu=2, ny=2, Hp=7, Hc=3, umin=-0.7, umax=0.7, ymax=0.9)
     bt = synth.make_batch(cfg, B, seed=30 + seed)
     rng = np.random.default_rng(seed)
     nY, nDU, nU = cfg.ny * cfg.Hp, cfg.nu * cfg.Hc, cfg.nu * cfg.Hp
@@ -708,21 +777,31 @@ def dense_weight_case(lib=None, B=3, which=("M", "N", "L"), seed=0):
     mpc = mpcqp.BatchLinMPC(bt["Ahat"], bt["Bhu"], bt["Chat"], Hp=cfg.Hp, Hc=cfg.Hc, Cwt=cfg.Cwt, lib=lib, **kw)
     mpc.setconstraint(**constraint_kwargs(cfg))
     mpc.lastu0 = bt["lastu0"].copy()
-    Ru = 0.3 * rng.standard_normal((B, nU))
-    mpc.moveinput(bt["xhat0"], bt["ry"], Rhatu=Ru, want_info=True)
-    info = mpc.getinfo()
-    assert np.all(mpc.status == 0), mpc.status
-    worst = 0.0
-    for i in range(B):
+    ors = []
+    for i in range(B if oracle else 0):
         m = cd.LinMPCOracle(bt["Ahat"][i], bt["Bhu"][i], bt["Chat"][i], Hp=cfg.Hp, Hc=cfg.Hc, Cwt=cfg.Cwt, **kw)
         m.setconstraint(**constraint_kwargs(cfg, oracle=True))
-        m.initpred(bt["xhat0"][i], bt["lastu0"][i], bt["ry"][i], Rhatu=Ru[i])
-        m.linconstraint()
-        z, st, oinfo = qp.solve_qp(*m.qp_data(), m.warmstart(), return_info=True)
-        assert st == 0
-        worst = max(worst, np.abs(mpc.Z[i, :nDU] - z[:nDU]).max() / max(1.0, np.abs(z[:nDU]).max()))
-        Jo = 0.5 * z @ m.Ht @ z + m.qt @ z + m.r
-        assert abs(info["J"][i] - Jo) <= 1e-6 * max(1.0, abs(Jo)), (info["J"][i], Jo)
+        ors.append(m)
+    x, lu = bt["xhat0"], bt["lastu0"].copy()
+    worst = 0.0 if oracle else None
+    for k in range(periods):
+        Ru = 0.3 * rng.standard_normal((B, nU))
+        u = mpc.moveinput(x, bt["ry"], Rhatu=Ru, want_info=True)
+        info = mpc.getinfo()
+        assert np.all(mpc.status == 0), mpc.status
+        if record is not None:
+            record.append(record_period(mpc))
+        for i, m in enumerate(ors):
+            m.initpred(x[i], lu[i], bt["ry"][i], Rhatu=Ru[i])
+            m.linconstraint()
+            z, st, oinfo = qp.solve_qp(*m.qp_data(), m.warmstart(), return_info=True)
+            assert st == 0
+            m.Zt = z
+            worst = max(worst, np.abs(mpc.Z[i, :nDU] - z[:nDU]).max() / max(1.0, np.abs(z[:nDU]).max()))
+            Jo = 0.5 * z @ m.Ht @ z + m.qt @ z + m.r
+            assert abs(info["J"][i] - Jo) <= 1e-6 * max(1.0, abs(Jo)), (info["J"][i], Jo)
+        lu = mpc.lastu0.copy()
+        x = np.einsum("bij,bj->bi", bt["Ahat"], x) + np.einsum("bij,bj->bi", bt["Bhu"], u)
     return worst, mpc.hd.kernel_kind()
 
 

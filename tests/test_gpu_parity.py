@@ -612,21 +612,51 @@ def test_custom_linear_constraints_on_gpu(hiplib):
     assert run_custom_constraint_cases(B=5) <= TOL
 
 
-def test_team_kernel_with_custom_rows_and_terminal_bound(hiplib):
+def team_of_cached_object(pattern, tmp_path):
+    """Team size of the step kernel in the on-demand object whose file name matches `pattern` (read from the symbol table of its
+    gfx950 code object, tests/team_util.py): 1 for k_step_s, T for k_step_team<..., T>."""
+    from tests import team_util as tu
+    objs = tu.find_cached_objects(pattern)
+    assert len(objs) == 1, (pattern, objs)
+    return tu.team_of_symbols(tu.kernel_symbols(objs[0], str(tmp_path / "syms")))
+
+
+def test_team_kernel_with_custom_rows_and_terminal_bound(hiplib, tmp_path):
     """Round 6: beyond one row per lane the on-demand kernels run a TEAM of wavefronts per controller (k_step_team); the
     helpers also take the custom-row, terminal-row and input-row parts of the Newton matrix.  nZ̃ = 121 (nu = 2, Hp = Hc = 60)
-    with two soft custom rows per step, a soft terminal bound, u / y bounds and a measured disturbance, against the oracle."""
+    with two soft custom rows per step, a soft terminal bound, u / y bounds and a measured disturbance, against the oracle:
+    EVERY member from a state of its own against an oracle of its own."""
     from tests.parity_util import run_soft_custom_constraints
     kinds = []
-    e = run_soft_custom_constraints(B=5, kinds=kinds, Hp=60, Hc=60, terminal=True, periods=2)
+    e = run_soft_custom_constraints(B=5, kinds=kinds, Hp=60, Hc=60, terminal=True, periods=2, distinct_x0=True)
     assert kinds == [mpcqp.api.KERNEL_ONDEMAND], kinds
     assert e <= 1e-6, e
+    assert team_of_cached_object("spec_r*_2_2_*_60_60_1_*_9.so", tmp_path / "a") == 2
     # ... and with a move-blocking vector (60 intervals over Hp = 70: no zero blocks in front of the Sigma table, so the Toeplitz
     # products take their general forms on wavefront 0 alone while the matrix-core passes are still split over the team)
     kinds = []
-    e = run_soft_custom_constraints(B=3, kinds=kinds, Hp=70, Hc=[1] * 55 + [3] * 5, terminal=True, periods=2)
+    e = run_soft_custom_constraints(B=3, kinds=kinds, Hp=70, Hc=[1] * 55 + [3] * 5, terminal=True, periods=2, distinct_x0=True)
     assert kinds == [mpcqp.api.KERNEL_ONDEMAND], kinds
     assert e <= 1e-6, e
+    # ... and at Hp = Hc = 70 (nZ̃ = 141, three rows per lane): the custom-row and terminal-row shares on a team of FOUR
+    kinds = []
+    e = run_soft_custom_constraints(B=6, kinds=kinds, Hp=70, Hc=70, terminal=True, periods=2, distinct_x0=True)
+    assert kinds == [mpcqp.api.KERNEL_ONDEMAND], kinds
+    assert e <= 1e-6, e
+    assert team_of_cached_object("spec_r*_2_2_*_70_70_1_*_9.so", tmp_path / "b") == 4
+
+
+def test_dense_weight_matrices_on_a_team_of_four(hiplib, tmp_path):
+    """Dense M_Hp, N_Hc and L_Hp together at nZ̃ = 131 (nu = ny = 2, Hp = 70, Hc = 65: nY = nU = 140): the dense gradient products
+    of the -DMPCQP_SPEC_DENSE variant on a team of four wavefronts (the nZ̃ = 7 case above is all they ran at before), every
+    member against the independent oracle, ΔU and J."""
+    from tests.parity_util import dense_weight_case
+    cfg = synth.Config("dense-team", nx=4, nu=2, ny=2, Hp=70, Hc=65, umin=-0.7, umax=0.7, ymax=0.9)
+    assert cfg.nu * cfg.Hc + 1 >= 131
+    worst, kind = dense_weight_case(B=6, cfg=cfg)
+    assert worst <= TOL, worst
+    assert kind == mpcqp.api.KERNEL_ONDEMAND
+    assert team_of_cached_object("spec_r*_2_2_6_70_65_1_*_3.so", tmp_path) == 4
 
 
 def test_dual_warm_start_closed_loop_on_gpu(hiplib):
@@ -708,6 +738,33 @@ def test_families_beyond_two_rows_per_lane(seed, hiplib):
     from tests.parity_util import run_random_case
     kinds = []
     e = run_random_case(seed, B=3, huge2=True, kinds=kinds)
+    assert kinds and kinds[0][1] > 130, kinds
+    assert e is not None and e <= TOL, e
+    assert_specialised(kinds)
+
+
+@pytest.mark.parametrize("seed", [3000, 3001, 3004, 3005])
+def test_families_beyond_one_row_per_lane_with_custom_rows(seed, hiplib):
+    """The `huge` families (64 < nZ̃ <= ~130, teams of two) with one or two custom linear constraint rows per step on top
+    (run_random_case(custom=True): Wy / Wu / Wd / Wr, bounds with -Inf holes, soft in soft families).  The seeds were chosen
+    with the oracle alone (oracle_only=True, no device) so that EVERY member of BOTH steps carries the active-set certificate;
+    the test asserts that, so the bound holds for all of them and not merely for "some"."""
+    from tests.parity_util import run_random_case
+    kinds, certs = [], []
+    e = run_random_case(seed, B=3, huge=True, custom=True, kinds=kinds, certs=certs)
+    assert len(certs) == 2 * 3 and all(certs), certs
+    assert kinds and 64 < kinds[0][1] <= 130, kinds
+    assert e is not None and e <= TOL, e
+    assert_specialised(kinds)
+
+
+@pytest.mark.parametrize("seed", [4000, 4001, 4003, 4004])
+def test_families_beyond_two_rows_per_lane_with_custom_rows(seed, hiplib):
+    """The `huge2` families (130 < nZ̃ <= 165, teams of four) with custom rows: as above, all members of both steps certified."""
+    from tests.parity_util import run_random_case
+    kinds, certs = [], []
+    e = run_random_case(seed, B=3, huge2=True, custom=True, kinds=kinds, certs=certs)
+    assert len(certs) == 2 * 3 and all(certs), certs
     assert kinds and kinds[0][1] > 130, kinds
     assert e is not None and e <= TOL, e
     assert_specialised(kinds)
