@@ -14,7 +14,9 @@
  * operating points, exactly as the reference's estimator fields do.  "(n,B)" means a Julia array of
  * that shape, i.e. estimator b's n values are contiguous; matrices are column-major inside an estimator.
  *
- * Supported: nx̂ <= 16, nym <= 16 (one estimator per 16-lane DPP row), any nu, nd, He; both forms
+ * Supported: nx̂ <= 32, nym <= 32, any nu, nd, He (max(nx̂, nym) <= 16: one estimator per 16-lane DPP row, four per
+ * wavefront; 17 .. 32: one estimator per wavefront on the wide kernels, mpcqp_mhe_lanes_per_estimator; beyond 32
+ * mpcqp_mhe_create returns MPCQP_ERR_UNSUPPORTED); both forms
  * (direct = true/false); growing and moving windows; hard bounds on x̂ (arrival state and window), ŵ, v̂
  * given per channel, hard (Cwt = Inf, the reference's default) or relaxed by one slack variable ε (finite Cwt and
  * softness c per channel, mpcqp_mhe_set_softness, or per channel and stage, mpcqp_mhe_set_softness_window).  Bounds that
@@ -37,7 +39,7 @@ typedef struct mpcqp_mhe_s* mpcqp_mhe;
 
 typedef struct {
     int32_t batch;      /* B                                                                     */
-    int32_t nxhat;      /* states of the augmented model (nx + integrators), <= 16               */
+    int32_t nxhat;      /* states of the augmented model (nx + integrators), <= 32 (as nym)      */
     int32_t nu, nym, nd;
     int32_t He;         /* estimation horizon                                                    */
     int32_t direct;     /* 1: current form (default of the reference), 0: predictor form         */
@@ -131,7 +133,9 @@ int mpcqp_mhe_get(mpcqp_mhe h, int what, void* out);
 void* mpcqp_mhe_device_ptr(mpcqp_mhe h, int what);
 int mpcqp_mhe_nk(mpcqp_mhe h);                 /* current window length Nk                           */
 double mpcqp_mhe_last_ms(mpcqp_mhe h);          /* device time of the last solve kernel (HIP events)  */
-int mpcqp_mhe_register_columns(mpcqp_mhe h);    /* NX: register columns of the kernel that runs       */
+int mpcqp_mhe_register_columns(mpcqp_mhe h);    /* NX: register columns of the kernel that runs: max(nx̂, nym) rounded up
+                                                 * to a multiple of 4 (<= 16) or, above 16, of 8 (24, 32)            */
+int mpcqp_mhe_lanes_per_estimator(mpcqp_mhe h); /* 16: one estimator per DPP row; 64: one per wavefront (NX > 16)   */
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,7 @@
 #include <math.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "mhe_types.h"
 
@@ -71,11 +72,85 @@ MPCQP_HD void sfor(F&& f) {
     }
 }
 
-// Row-lane linear algebra of one 16-lane group: every lane holds ITS row of each operand.
+// Geometry of the wave interface: lanes per estimator and estimators per wavefront.  An interface that defines neither
+// (the 16-lane-row ones: MheDevWave, the CPU emulator's) has RL / GPW of mhe_types.h; the wide one defines GL = 64, GPW = 1.
+template <class W, class = void>
+struct WaveGeom { static constexpr int GL = mhe::RL, GPW = mhe::GPW; };
+template <class W>
+struct WaveGeom<W, std::void_t<decltype(W::GL), decltype(W::GPW)>> { static constexpr int GL = W::GL, GPW = W::GPW; };
+
+// A wave interface with a member `stage` (LDS of stage_doubles() doubles, wide family) runs the NX x NX x NX products of
+// Ops on the matrix cores, staged through that buffer (Ops::mm_staged); every other interface keeps the row-broadcast form.
+template <class W, class = void>
+struct WaveStaged : std::false_type {};
+template <class W>
+struct WaveStaged<W, std::void_t<decltype(std::declval<W&>().stage)>> : std::true_type {};
+constexpr int STAGE_LD = 33;                      // leading dimension of a staged 32 x 32 operand (odd: rows spread over the banks)
+MPCQP_HD constexpr size_t stage_doubles() { return (size_t)2 * 32 * STAGE_LD; }
+
+// Row-lane linear algebra of one group of lanes: every lane holds ITS row of each operand.
 template <class W, int NX>
 struct Ops {
     W& w;
     using Row = double[NX];
+    static constexpr bool STAGED = WaveStaged<W>::value;
+    enum { P_SET, P_ADD, P_SUBT, P_ACCT };       // C = X Y | C += X Y | C -= X Y' | C += sign X Y'
+
+    // One product of two row-lane operands (16 < NX <= 32, one estimator per wavefront) through LDS: the lanes write their
+    // rows of X and Y, the wavefront multiplies 2 x 2 tiles of 16 x 16 over NX / 4 steps of v_mfma_f64_16x16x4
+    // (A[i = lane & 15][k = lane >> 4], B[k][j = lane & 15], D[row = (lane >> 4) + 4 reg][col = lane & 15]), the tiles
+    // go back through the first operand's place and every lane reads its row.  Rows / columns NX .. 31 of the staged
+    // operands hold whatever the idle lanes and the LDS held: they only reach results that nobody reads.  A lane
+    // l >= 32 receives the row of lane l - 32 (idle either way; the same on the CPU side, which multiplies plainly).
+    template <int MODE>
+    MPCQP_HD void mm_staged(const Row& X, const Row& Y, Row& C, double sign) const {
+        static_assert(NX > 16 && NX <= 32 && NX % 4 == 0, "staged products: two tiles of 16 per side");
+        constexpr int LD = STAGE_LD;
+        constexpr bool TR = MODE == P_SUBT || MODE == P_ACCT;
+        double* const SX = w.stage;
+        double* const SY = w.stage + 32 * LD;
+        const int lane = w.lane, rr = lane & 31;
+        if (lane < 32)
+            sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; SX[lane * LD + c] = X[c]; SY[lane * LD + c] = Y[c]; });
+        w.sync();
+        Row T;
+#if defined(__HIP_DEVICE_COMPILE__)
+        typedef double v4d_ __attribute__((ext_vector_type(4)));
+        const int li = lane & 15, lk = lane >> 4;
+        v4d_ acc[2][2] = {{{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}};
+        sfor<NX / 4>([&](auto ik) {
+            constexpr int k0 = 4 * decltype(ik)::v;
+            const int k = k0 + lk;
+            const double a0 = SX[li * LD + k], a1 = SX[(16 + li) * LD + k];
+            const double b0 = TR ? SY[li * LD + k] : SY[k * LD + li], b1 = TR ? SY[(16 + li) * LD + k] : SY[k * LD + 16 + li];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+        });
+        w.sync();                                  // every operand is read before the tiles take X's place
+        sfor<2>([&](auto ii) {
+            sfor<2>([&](auto ij) {
+                constexpr int I = decltype(ii)::v, J = decltype(ij)::v;
+                sfor<4>([&](auto ir) { constexpr int q = decltype(ir)::v; SX[(16 * I + lk + 4 * q) * LD + 16 * J + li] = acc[I][J][q]; });
+            });
+        });
+        w.sync();
+        sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; T[c] = SX[rr * LD + c]; });
+#else
+        sfor<NX>([&](auto ic) {
+            constexpr int c = decltype(ic)::v;
+            double acc = 0.0;
+            for (int k = 0; k < NX; ++k) acc = fma(SX[rr * LD + k], TR ? SY[c * LD + k] : SY[k * LD + c], acc);
+            T[c] = acc;
+        });
+#endif
+        sfor<NX>([&](auto ic) {
+            constexpr int c = decltype(ic)::v;
+            C[c] = MODE == P_SET ? T[c] : MODE == P_ADD ? C[c] + T[c] : MODE == P_SUBT ? C[c] - T[c] : fma(sign, T[c], C[c]);
+        });
+        w.sync();                                  // the rows are read before the next product is staged
+    }
 
     // w.fmabc4<L0,L1,L2,L3>(acc, x0..x3, y0..y3): acc += sum_i (x_i of lane L_i of this row) * y_i -- four
     // v_fmac_f64_dpp on gfx950 (the row broadcast is the DPP modifier of the multiply-add itself)
@@ -88,6 +163,7 @@ struct Ops {
         return acc;
     }
     MPCQP_HD void mm(const Row& X, const Row& Y, Row& C) const {  // C = X Y
+        if constexpr (STAGED) { mm_staged<P_SET>(X, Y, C, 1.0); return; }
         sfor<NX>([&](auto ic) {
             constexpr int c = decltype(ic)::v;
             double acc = 0.0;
@@ -98,7 +174,18 @@ struct Ops {
             C[c] = acc;
         });
     }
+    // C += X Y
+    MPCQP_HD void mm_add(const Row& X, const Row& Y, Row& C) const {
+        if constexpr (STAGED) { mm_staged<P_ADD>(X, Y, C, 1.0); return; }
+        sfor<NX>([&](auto ic) {
+            constexpr int c = decltype(ic)::v;
+            double acc = 0.0;
+            sfor<NX / 4>([&](auto ij) { constexpr int k = 4 * decltype(ij)::v; w.template fmabc4<k, k + 1, k + 2, k + 3>(acc, Y[c], Y[c], Y[c], Y[c], X[k], X[k + 1], X[k + 2], X[k + 3]); });
+            C[c] += acc;
+        });
+    }
     MPCQP_HD void mmt_sub(const Row& X, const Row& Y, Row& C) const {   // C -= X Y', accumulated in place
+        if constexpr (STAGED) { mm_staged<P_SUBT>(X, Y, C, 1.0); return; }
         sfor<NX>([&](auto ic) {
             constexpr int c = decltype(ic)::v;
             sfor<NX / 4>([&](auto ij) {
@@ -108,6 +195,7 @@ struct Ops {
         });
     }
     MPCQP_HD void mmt_acc(const Row& X, const Row& Y, Row& C, double sign) const {   // C += sign X Y'
+        if constexpr (STAGED) { mm_staged<P_ACCT>(X, Y, C, sign); return; }
         sfor<NX>([&](auto ic) {
             constexpr int c = decltype(ic)::v;
             double acc = 0.0;
@@ -179,9 +267,10 @@ template <class W, int NX>
 MPCQP_HD void setup_body(W& w, const Dims& d, const Raw& in, double* cst_all, int wave_id) {
     using O = Ops<W, NX>;
     typename O::Row A, At, Qi, Cm, Ct, Ri, T, U;
+    constexpr int RL = WaveGeom<W>::GL, GPW = WaveGeom<W>::GPW;      // (shadow the 16-lane constants of mhe_types.h)
     O op{w};
-    const int lane = w.lane, r = lane & (RL - 1), g = lane >> 4;
-    const CstMap cm = cst_map(NX, d.nu, d.nd);
+    const int lane = w.lane, r = lane & (RL - 1), g = lane / RL;
+    const CstMap cm = cst_map(NX, d.nu, d.nd, RL);
     const int nx = d.nx, nym = d.nym, nu = d.nu, nd = d.nd;
     for (int wg = wave_id; wg * GPW < d.B; wg += d.nwaves) {
         const int bq = wg * GPW + g;
@@ -244,9 +333,10 @@ template <class W, int NX>
 MPCQP_HD void cov_body(W& w, const Dims& d, const Args& a, int mode, const double* P0, double* Pout, int wave_id) {
     using O = Ops<W, NX>;
     typename O::Row P, A, Cm, X, Y, M;
+    constexpr int RL = WaveGeom<W>::GL, GPW = WaveGeom<W>::GPW;      // (shadow the 16-lane constants of mhe_types.h)
     O op{w};
-    const int lane = w.lane, r = lane & (RL - 1), g = lane >> 4;
-    const CstMap cm = cst_map(NX, d.nu, d.nd);
+    const int lane = w.lane, r = lane & (RL - 1), g = lane / RL;
+    const CstMap cm = cst_map(NX, d.nu, d.nd, RL);
     const int nx = d.nx;
     for (int wg = wave_id; wg * GPW < d.B; wg += d.nwaves) {
         const int bq = wg * GPW + g;
@@ -334,6 +424,7 @@ template <class W, int NX, unsigned CM = 7u>
 struct Solver {
     using O = Ops<W, NX>;
     using Row = typename O::Row;
+    static constexpr int RL = WaveGeom<W>::GL, GPW = WaveGeom<W>::GPW;      // (shadow the 16-lane constants of mhe_types.h)
     W& w;
     const Dims& d;
     const Args& a;
@@ -346,7 +437,7 @@ struct Solver {
     const double* cbase;   // constant blocks of this wavefront's first estimator (wave-uniform)
     int coff;           // this lane's offset into them: (b - first) * stride + r
     double* sb;      // scratch of this wavefront (wave-uniform base)
-    // A slot holds one double per ACTIVE lane: the NX lanes of each of the four groups, packed (SW = 4 NX doubles;
+    // A slot holds one double per ACTIVE lane: the NX lanes of each of the GPW groups, packed (16-lane rows: SW = 4 NX doubles;
     // 384 B instead of 512 B for NX = 12 -- a quarter of the HBM traffic of the sweeps would be padding).
     static constexpr int SW = GPW * NX;
     typename W::Buf sbuf;     // buffer resource over this wavefront's scratch
@@ -363,10 +454,10 @@ struct Solver {
     double cx0, cx1, cw0, cw1, cv0, cv1;       // softness of this lane's rows (0: hard)
 
     MPCQP_HD Solver(W& w_, const Dims& d_, const Args& a_, double* smem, int wave_id)
-        : w(w_), d(d_), a(a_), op{w_}, lane(w_.lane), r(w_.lane & (RL - 1)), g(w_.lane >> 4),
-          cm(cst_map(NX, d_.nu, d_.nd)), sm(slot_map(NX, d_.He, d_.cls)) {
-        sb = a.scratch + (size_t)wave_id * wave_scratch_doubles(NX, d.nslot);
-        sbuf = w.make_buf(sb, wave_scratch_doubles(NX, d.nslot) * sizeof(double));
+        : w(w_), d(d_), a(a_), op{w_}, lane(w_.lane), r(w_.lane & (RL - 1)), g(w_.lane / RL),
+          cm(cst_map(NX, d_.nu, d_.nd, RL)), sm(slot_map(NX, d_.He, d_.cls)) {
+        sb = a.scratch + (size_t)wave_id * wave_scratch_doubles(NX, d.nslot, GPW);
+        sbuf = w.make_buf(sb, wave_scratch_doubles(NX, d.nslot, GPW) * sizeof(double));
         lvo = r < NX ? (unsigned)((g * NX + r) * 8) : W::BUF_OOB;
         lds = smem + lane;
         N = d.N;
@@ -807,24 +898,14 @@ struct Solver {
                                 Row At;
                                 O::ldo(w.uniform(cbase + cm.At), coff, RL, At);
                                 sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; U[c] = Dtw * A[c]; });
-                                sfor<NX>([&](auto ic) {
-                                    constexpr int c = decltype(ic)::v;
-                                    double acc = 0.0;
-                                    sfor<NX / 4>([&](auto ij) { constexpr int k = 4 * decltype(ij)::v; w.template fmabc4<k, k + 1, k + 2, k + 3>(acc, U[c], U[c], U[c], U[c], At[k], At[k + 1], At[k + 2], At[k + 3]); });
-                                    Bs[c] += acc;
-                                });
+                                op.mm_add(At, U, Bs);
                             }
                             if (cV && im >= 0) {          // + Ĉm' D̃v Ĉm
                                 Row Cm, Ct;
                                 O::ldo(w.uniform(cbase + cm.Cm), coff, RL, Cm);
                                 O::ldo(w.uniform(cbase + cm.Ct), coff, RL, Ct);
                                 sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; U[c] = Dtv * Cm[c]; });
-                                sfor<NX>([&](auto ic) {
-                                    constexpr int c = decltype(ic)::v;
-                                    double acc = 0.0;
-                                    sfor<NX / 4>([&](auto ij) { constexpr int k = 4 * decltype(ij)::v; w.template fmabc4<k, k + 1, k + 2, k + 3>(acc, U[c], U[c], U[c], U[c], Ct[k], Ct[k + 1], Ct[k + 2], Ct[k + 3]); });
-                                    Bs[c] += acc;
-                                });
+                                op.mm_add(Ct, U, Bs);
                             }
                             if (s > 0) {
                                 op.mm(Oprev, Si, U);
@@ -1110,8 +1191,9 @@ struct Solver {
 
 template <class W, int NX, unsigned CM = 7u>
 MPCQP_HD void step_body(W& w, const Dims& d, const Args& a, int wave_id, double* smem) {
+    constexpr int RL = WaveGeom<W>::GL, GPW = WaveGeom<W>::GPW;
     Solver<W, NX, CM> sv(w, d, a, smem, wave_id);
-    const CstMap cm = cst_map(NX, d.nu, d.nd);
+    const CstMap cm = cst_map(NX, d.nu, d.nd, RL);
     for (int wg = wave_id; wg * GPW < d.B; wg += d.nwaves) {
         const int bq = wg * GPW + sv.g;
         sv.live = bq < d.B;

@@ -11,6 +11,7 @@
 
 #include "../../include/mpcqp_mhe.h"
 #include "mhe_launch.h"
+#include "mhe_wide_launch.h"
 #include "mpcqp_hostutil.h"
 
 using namespace mpcqp;
@@ -37,7 +38,22 @@ struct mpcqp_mhe_s {
     bool soft = false;       // finite Cwt: a slack variable exists
     double *s_y = nullptr, *s_u = nullptr, *s_d = nullptr;      // staging of the host-pointer entry points
     size_t scratch_bytes = 0;
+    // geometry of the kernel family serving the handle: lane stride of every row-lane array ([..][rl]) and estimators
+    // per wavefront -- 16 / 4 (one DPP row per estimator) or 64 / 1 (wide family, NX > 16)
+    int rl = mhe::RL, gpw = mhe::GPW;
+    bool wide = false;
 };
+
+// the kernel family of the handle (the wide entry points are weak: mhe_wide_launch.h)
+static hipError_t do_setup(mpcqp_mhe h) {
+    return h->wide ? mhe::launch_wide_setup(h->d, h->raw, h->a.cst, h->stream) : mhe::launch_setup(h->d, h->raw, h->a.cst, h->stream);
+}
+static hipError_t do_cov(mpcqp_mhe h, int mode, const double* P0, double* Pout) {
+    return h->wide ? mhe::launch_wide_cov(h->d, h->a, mode, P0, Pout, h->stream) : mhe::launch_cov(h->d, h->a, mode, P0, Pout, h->stream);
+}
+static hipError_t do_step(mpcqp_mhe h, const mhe::Args& a) {
+    return h->wide ? mhe::launch_wide_step(h->d, a, h->stream) : mhe::launch_step(h->d, a, h->stream);
+}
 
 static int dalloc(mpcqp_mhe h, void** p, size_t bytes) {
     if (bytes == 0) bytes = 8;
@@ -60,7 +76,7 @@ static int up(mpcqp_mhe h, double* dst, const double* src, size_t n) {
 static int ensure_scratch(mpcqp_mhe h) {
     const mhe::SlotMap sm = mhe::slot_map(h->d.NX, h->d.He, h->d.cls);
     h->d.nslot = sm.total;
-    const size_t need = (size_t)h->d.nwaves * mhe::wave_scratch_doubles(h->d.NX, sm.total) * sizeof(double);
+    const size_t need = (size_t)h->d.nwaves * mhe::wave_scratch_doubles(h->d.NX, sm.total, h->gpw) * sizeof(double);
     if (need <= h->scratch_bytes) return MPCQP_OK;
     void* p = nullptr;
     int rc = dalloc(h, &p, need);
@@ -85,13 +101,13 @@ static int solve_period(mpcqp_mhe h, const double* y_dev, const double* d_dev, c
     d.N = h->Nk;
     int rc = ensure_scratch(h);
     if (rc) return rc;
-    if (d.direct && moving) HIPCHK(mhe::launch_cov(d, h->a, 1, nullptr, nullptr, h->stream));
+    if (d.direct && moving) HIPCHK(do_cov(h, 1, nullptr, nullptr));
     mhe::Args a = h->a;
     a.y0m_new = y_dev;
     a.d0_new = d_dev;
     a.u0_new = u_dev;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    HIPCHK(mhe::launch_step(d, a, h->stream));
+    HIPCHK(do_step(h, a));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     return MPCQP_OK;
@@ -113,7 +129,10 @@ int mpcqp_mhe_create(const mpcqp_mhe_dims* in, mpcqp_mhe* out) {
     *out = nullptr;
     if (in->batch < 1 || in->nxhat < 1 || in->nu < 0 || in->nym < 1 || in->nd < 0 || in->He < 1) return MPCQP_ERR_DIMS;
     if (in->flags & ~MPCQP_MHE_KEEP_WINDOWS) return MPCQP_ERR_ARG;
-    if (in->nxhat > mhe::RL || in->nym > mhe::RL) return MPCQP_ERR_UNSUPPORTED;
+    const int nmax = in->nxhat > in->nym ? in->nxhat : in->nym;
+    if (nmax > mhe::NX_MAX) return MPCQP_ERR_UNSUPPORTED;
+    const bool wide = nmax > mhe::RL;
+    if (wide && !mhe::wide_available()) return MPCQP_ERR_UNSUPPORTED;        // (a library without mhe_wide_kernels.hip)
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
     if (in->device < 0 || in->device >= ndev) return MPCQP_ERR_ARG;
@@ -124,8 +143,10 @@ int mpcqp_mhe_create(const mpcqp_mhe_dims* in, mpcqp_mhe* out) {
     mhe::Dims& d = h->d;
     d.B = in->batch; d.nx = in->nxhat; d.nu = in->nu; d.nym = in->nym; d.nd = in->nd; d.He = in->He;
     d.direct = in->direct ? 1 : 0;
-    const int nmax = in->nxhat > in->nym ? in->nxhat : in->nym;
-    d.NX = 4 * ((nmax + 3) / 4);
+    d.NX = mhe::register_columns_for(nmax);
+    h->wide = wide;
+    h->rl = wide ? mhe::WIDE_RL : mhe::RL;
+    h->gpw = wide ? mhe::WIDE_GPW : mhe::GPW;
     d.N = 0; d.hy = 0; d.hd = 0; d.cls = 0;
     d.max_iter = in->max_iter > 0 ? in->max_iter : 80;
     d.gap_tol = in->gap_tol > 0 ? in->gap_tol : 1e-12;
@@ -133,8 +154,8 @@ int mpcqp_mhe_create(const mpcqp_mhe_dims* in, mpcqp_mhe* out) {
     // (dual regularisation: rows held at D~ = 1/δ; 1e-10 -- two soft-bound families of the randomised sweeps sat on the noise floor of
     // the block recursion with 1e-12, errors 1e-5..7e-5 -- δ vanishes from the converged solution)
     d.dual_reg = in->dual_reg > 0 ? in->dual_reg : 1e-10;
-    d.nwaves = mhe::waves_for(in->device, d.B, d.NX);
-    d.cst_stride = mhe::cst_map(d.NX, d.nu, d.nd).stride;
+    d.nwaves = wide ? mhe::wide_waves_for(in->device, d.B, d.NX) : mhe::waves_for(in->device, d.B, d.NX);
+    d.cst_stride = mhe::cst_map(d.NX, d.nu, d.nd, h->rl).stride;
     d.opt = getenv("MPCQP_MHE_OPT") ? (uint32_t)atoi(getenv("MPCQP_MHE_OPT")) : 0u;
     h->device = in->device;
     h->flags = in->flags;
@@ -146,8 +167,8 @@ int mpcqp_mhe_create(const mpcqp_mhe_dims* in, mpcqp_mhe* out) {
     const size_t B = d.B, nx = d.nx, nu = d.nu, nym = d.nym, nd = d.nd, He = d.He;
     auto mk = [&](double** p, size_t n) { if (!rc) rc = dalloc_t(h, p, n); };
     mk(&h->a.cst, B * d.cst_stride);
-    mk(&h->a.P, B * d.NX * mhe::RL);
-    mk(&h->a.Pi2, B * d.NX * mhe::RL);
+    mk(&h->a.P, B * d.NX * h->rl);
+    mk(&h->a.Pi2, B * d.NX * h->rl);
     mk(&h->a.Y0m, B * He * nym); mk(&h->a.U0, B * He * nu); mk(&h->a.D0, B * (He + 1) * nd); mk(&h->a.X0old, B * He * nx);
     mk(&h->a.xhat0, B * nx);
     mk(&h->a.Zt, B * (nx + He * nx));
@@ -194,7 +215,7 @@ int mpcqp_mhe_set_model(mpcqp_mhe h, const double* Ahat, const double* Bhu, cons
     put(&h->raw.Bd, Bhd, B * nx * nd); put(&h->raw.Ddm, Dhdm, B * nym * nd); put(&h->raw.fx, fx, B * nx);
     put(&h->raw.Q, Qhat, B * nx * nx); put(&h->raw.R, Rhat, B * nym * nym);
     if (rc) return rc;
-    HIPCHK(mhe::launch_setup(d, h->raw, h->a.cst, h->stream));
+    HIPCHK(do_setup(h));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_model = true;
     return MPCQP_OK;
@@ -205,21 +226,22 @@ int mpcqp_mhe_set_bounds(mpcqp_mhe h, const double* xmin, const double* xmax, co
     if (!h) return MPCQP_ERR_NULL;
     ON_DEVICE(h);
     mhe::Dims& d = h->d;
+    const int RL = h->rl;          // lane stride of the handle's row-lane arrays
     const double* src[6] = {xmin, xmax, wmin, wmax, vmin, vmax};
     const int n[6] = {d.nx, d.nx, d.nx, d.nx, d.nym, d.nym};
     const uint32_t bit[6] = {mhe::CLS_X, mhe::CLS_X, mhe::CLS_W, mhe::CLS_W, mhe::CLS_V, mhe::CLS_V};
     const double** dst[6] = {&h->a.xmin, &h->a.xmax, &h->a.wmin, &h->a.wmax, &h->a.vmin, &h->a.vmax};
     uint32_t cls = 0;
-    std::vector<double> buf((size_t)d.B * mhe::RL);
+    std::vector<double> buf((size_t)d.B * RL);
     for (int k = 0; k < 6; ++k) {
         const bool lower = (k % 2) == 0;
         bool any = false;
         for (size_t b = 0; b < (size_t)d.B; ++b)
-            for (int r = 0; r < mhe::RL; ++r) {
+            for (int r = 0; r < RL; ++r) {
                 double v = (src[k] && r < n[k]) ? src[k][b * n[k] + r] : (lower ? -INFINITY : INFINITY);
                 if (v != v) return MPCQP_ERR_ARG;
                 if (std::isinf(v) || std::fabs(v) >= BIG) v = lower ? -BIG : BIG; else any = true;
-                buf[b * mhe::RL + r] = v;
+                buf[b * RL + r] = v;
             }
         if (any) {
             if (!h->bnd[k]) { int rc = dalloc_t(h, &h->bnd[k], buf.size()); if (rc) return rc; }
@@ -241,6 +263,7 @@ int mpcqp_mhe_set_bounds_window(mpcqp_mhe h, const double* Xmin, const double* X
     if (!h) return MPCQP_ERR_NULL;
     ON_DEVICE(h);
     mhe::Dims& d = h->d;
+    const int RL = h->rl;          // lane stride of the handle's row-lane arrays
     const double* src[6] = {Xmin, Xmax, Wmin, Wmax, Vmin, Vmax};
     const int n[6] = {d.nx, d.nx, d.nx, d.nx, d.nym, d.nym};
     const int nblk[6] = {d.He + 1, d.He + 1, d.He, d.He, d.He, d.He};
@@ -250,14 +273,14 @@ int mpcqp_mhe_set_bounds_window(mpcqp_mhe h, const double* Xmin, const double* X
     for (int k = 0; k < 6; ++k) {
         const bool lower = (k % 2) == 0;
         bool any = false;
-        std::vector<double> buf((size_t)d.B * nblk[k] * mhe::RL);
+        std::vector<double> buf((size_t)d.B * nblk[k] * RL);
         for (size_t b = 0; b < (size_t)d.B; ++b)
             for (int j = 0; j < nblk[k]; ++j)
-                for (int r = 0; r < mhe::RL; ++r) {
+                for (int r = 0; r < RL; ++r) {
                     double v = (src[k] && r < n[k]) ? src[k][(b * nblk[k] + j) * n[k] + r] : (lower ? -INFINITY : INFINITY);
                     if (v != v) return MPCQP_ERR_ARG;
                     if (std::isinf(v) || std::fabs(v) >= BIG) v = lower ? -BIG : BIG; else any = true;
-                    buf[(b * nblk[k] + j) * mhe::RL + r] = v;
+                    buf[(b * nblk[k] + j) * RL + r] = v;
                 }
         if (any) {
             if (!h->bndw[k]) { int rc = dalloc_t(h, &h->bndw[k], buf.size()); if (rc) return rc; }
@@ -292,6 +315,7 @@ int mpcqp_mhe_set_softness(mpcqp_mhe h, const double* Cwt, const double* c_xmin,
     if (!h) return MPCQP_ERR_NULL;
     ON_DEVICE(h);
     mhe::Dims& d = h->d;
+    const int RL = h->rl;          // lane stride of the handle's row-lane arrays
     const double* src[6] = {c_xmin, c_xmax, c_wmin, c_wmax, c_vmin, c_vmax};
     const int n[6] = {d.nx, d.nx, d.nx, d.nx, d.nym, d.nym};
     const double** dst[6] = {&h->a.cxmin, &h->a.cxmax, &h->a.cwmin, &h->a.cwmax, &h->a.cvmin, &h->a.cvmax};
@@ -311,11 +335,11 @@ int mpcqp_mhe_set_softness(mpcqp_mhe h, const double* Cwt, const double* c_xmin,
     }
     int rc = set_cwt(h, Cwt);
     if (rc) return rc;
-    std::vector<double> buf((size_t)d.B * mhe::RL);
+    std::vector<double> buf((size_t)d.B * RL);
     for (int k = 0; k < 6; ++k) {
         if (!src[k]) { *dst[k] = nullptr; continue; }
         for (size_t b = 0; b < (size_t)d.B; ++b)
-            for (int r = 0; r < mhe::RL; ++r) buf[b * mhe::RL + r] = r < n[k] ? src[k][b * n[k] + r] : 0.0;
+            for (int r = 0; r < RL; ++r) buf[b * RL + r] = r < n[k] ? src[k][b * n[k] + r] : 0.0;
         if (!h->sft[k]) { rc = dalloc_t(h, &h->sft[k], buf.size()); if (rc) return rc; }
         rc = up(h, h->sft[k], buf.data(), buf.size());
         if (rc) return rc;
@@ -334,6 +358,7 @@ int mpcqp_mhe_set_softness_window(mpcqp_mhe h, const double* Cwt, const double* 
     if (!Cwt) return MPCQP_ERR_ARG;          // (the reference: "Cwt must be finite to set softness parameters")
     ON_DEVICE(h);
     mhe::Dims& d = h->d;
+    const int RL = h->rl;          // lane stride of the handle's row-lane arrays
     const double* src[6] = {C_xmin, C_xmax, C_wmin, C_wmax, C_vmin, C_vmax};
     const int n[6] = {d.nx, d.nx, d.nx, d.nx, d.nym, d.nym};
     const int nblk[6] = {d.He + 1, d.He + 1, d.He, d.He, d.He, d.He};
@@ -346,11 +371,11 @@ int mpcqp_mhe_set_softness_window(mpcqp_mhe h, const double* Cwt, const double* 
     if (rc) return rc;
     for (int k = 0; k < 6; ++k) {
         if (!src[k]) { *dst[k] = nullptr; continue; }
-        std::vector<double> buf((size_t)d.B * nblk[k] * mhe::RL);
+        std::vector<double> buf((size_t)d.B * nblk[k] * RL);
         for (size_t b = 0; b < (size_t)d.B; ++b)
             for (int j = 0; j < nblk[k]; ++j)
-                for (int r = 0; r < mhe::RL; ++r)
-                    buf[(b * nblk[k] + j) * mhe::RL + r] = r < n[k] ? src[k][(b * nblk[k] + j) * n[k] + r] : 0.0;
+                for (int r = 0; r < RL; ++r)
+                    buf[(b * nblk[k] + j) * RL + r] = r < n[k] ? src[k][(b * nblk[k] + j) * n[k] + r] : 0.0;
         if (!h->sftw[k]) { rc = dalloc_t(h, &h->sftw[k], buf.size()); if (rc) return rc; }
         rc = up(h, h->sftw[k], buf.data(), buf.size());
         if (rc) return rc;
@@ -384,7 +409,7 @@ int mpcqp_mhe_init(mpcqp_mhe h, const double* xhat0, const double* P0, const dou
     if (rc) return rc;
     d.hy = d.hd = 0;
     h->Nk = 0;
-    HIPCHK(mhe::launch_cov(d, h->a, 4, h->P0, nullptr, h->stream));
+    HIPCHK(do_cov(h, 4, h->P0, nullptr));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_init = true;
     return MPCQP_OK;
@@ -456,7 +481,7 @@ int mpcqp_mhe_update_device(mpcqp_mhe h, const double* u0_dev, const double* y0m
     }
     // update_cov! (execute.jl:755-781): once the window is full, the arrival covariance advances by one
     // KalmanFilter period (prediction only in the current form: it was corrected in preparestate!)
-    if (h->Nk == d.He) HIPCHK(mhe::launch_cov(d, h->a, d.direct ? 2 : 3, nullptr, nullptr, h->stream));
+    if (h->Nk == d.He) HIPCHK(do_cov(h, d.direct ? 2 : 3, nullptr, nullptr));
     if (d.nu > 0)
         HIPCHK(hipMemcpyAsync(h->lastu, u0_dev, (size_t)d.B * d.nu * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return MPCQP_OK;
@@ -530,7 +555,7 @@ int mpcqp_mhe_get(mpcqp_mhe h, int what, void* out) {
         case MPCQP_MHE_EPSILON: src = h->a.eps_out; bytes = B * 8; break;
         case MPCQP_MHE_PBAR: {
             // the row-lane array back to (nx̂,nx̂,B): a covariance launch with no update writes the ABI copy
-            HIPCHK(mhe::launch_cov(d, h->a, 0, nullptr, h->Pout, h->stream));
+            HIPCHK(do_cov(h, 0, nullptr, h->Pout));
             src = h->Pout; bytes = B * nx * nx * 8; break;
         }
         default: return MPCQP_ERR_ARG;
@@ -553,5 +578,7 @@ double mpcqp_mhe_last_ms(mpcqp_mhe h) {
 }
 
 int mpcqp_mhe_register_columns(mpcqp_mhe h) { return h ? h->d.NX : MPCQP_ERR_NULL; }
+
+int mpcqp_mhe_lanes_per_estimator(mpcqp_mhe h) { return h ? h->rl : MPCQP_ERR_NULL; }
 
 }  // extern "C"

@@ -19,6 +19,12 @@ namespace mhe {
 
 constexpr int RL = 16;    // lanes per estimator: one DPP row
 constexpr int GPW = 4;    // estimators per wavefront
+// The wide kernel family (mhe_wide_devwave.h, 16 < max(nx̂, nym) <= 32) gives one estimator the whole wavefront: its wave
+// interface carries GL = 64 lanes per estimator and GPW = 1, and every row-lane array below is laid out with that lane
+// stride instead of RL (the `rl` / `gpw` arguments; the bodies take both from their wave interface, the host from the handle).
+constexpr int WIDE_RL = 64;
+constexpr int WIDE_GPW = 1;
+constexpr int NX_MAX = 32;     // register columns of the largest kernel
 enum { CLS_X = 1u, CLS_W = 2u, CLS_V = 4u, CLS_S = 8u, CLS_L = 16u, CLS_C = 32u };   // bound classes; CLS_S: a slack variable ε relaxes some rows;
                                                                         // CLS_L: the bound arrays are window-long (one row per stage);
                                                                         // CLS_C: the softness arrays are window-long (C_x̂min ... C_v̂max)
@@ -26,7 +32,8 @@ enum { CLS_X = 1u, CLS_W = 2u, CLS_V = 4u, CLS_S = 8u, CLS_L = 16u, CLS_C = 32u 
 struct Dims {
     int B, nx, nu, nym, nd, He;
     int direct;        // 1: current form (p = 0), 0: predictor form (p = 1)
-    int NX;            // register columns: max(nx, nym) rounded up to a multiple of four (<= 16)
+    int NX;            // register columns: max(nx, nym) rounded up to a multiple of four (<= 16: one DPP row per
+                       // estimator) or, above 16, of eight (24, 32: the wide kernels, one wavefront per estimator)
     int N;             // window length Nk of this period (1..He)
     int hy, hd;        // ring heads: window entry i of Y0m/U0/X0old lives in slot (hy + i) % He,
                        // entry i of D0 (He + 1 entries) in slot (hd + i) % (He + 1)
@@ -44,10 +51,10 @@ struct Dims {
 struct CstMap {
     int A, At, Oc, OcT, T1, T2, T3, Bmid, Cm, Ct, CR, Q, R, Bu, Bd, Ddm, fx, stride;
 };
-MPCQP_HD inline CstMap cst_map(int NX, int nu, int nd) {
+MPCQP_HD inline CstMap cst_map(int NX, int nu, int nd, int rl = RL) {
     CstMap m{};
     int o = 0;
-    auto take = [&](int n) { int p = o; o += n * RL; return p; };
+    auto take = [&](int n) { int p = o; o += n * rl; return p; };
     m.A = take(NX); m.At = take(NX); m.Oc = take(NX); m.OcT = take(NX);
     m.T1 = take(NX); m.T2 = take(NX); m.T3 = take(NX); m.Bmid = take(NX);
     m.Cm = take(NX); m.Ct = take(NX); m.CR = take(NX); m.Q = take(NX); m.R = take(NX);
@@ -79,7 +86,7 @@ MPCQP_HD inline SlotMap slot_map(int NX, int He, uint32_t cls) {
 }
 
 // doubles of scratch per wavefront: nslot packed slots (one double per active lane)
-MPCQP_HD inline size_t wave_scratch_doubles(int NX, int nslot) { return (size_t)nslot * GPW * NX + WAVE; }
+MPCQP_HD inline size_t wave_scratch_doubles(int NX, int nslot, int gpw = GPW) { return (size_t)nslot * gpw * NX + WAVE; }
 
 struct Raw {               // inputs of mpcqp_mhe_set_model (ABI layout: column-major inside an estimator)
     const double *Ahat, *Bu, *Cm, *Bd, *Ddm, *fx;    // [B][nx*nx] [B][nx*nu] [B][nym*nx] [B][nx*nd] [B][nym*nd] [B][nx] (fx may be null)

@@ -22,7 +22,7 @@ from .api import MpcqpError, _chk, _f64, _ptr, colmajor
 EXPORTS = ("mpcqp_mhe_create", "mpcqp_mhe_destroy", "mpcqp_mhe_set_model", "mpcqp_mhe_set_bounds", "mpcqp_mhe_set_bounds_window", "mpcqp_mhe_set_softness", "mpcqp_mhe_set_softness_window", "mpcqp_mhe_init", "mpcqp_mhe_set_state", "mpcqp_mhe_shift_windows",
            "mpcqp_mhe_prepare", "mpcqp_mhe_update", "mpcqp_mhe_prepare_device", "mpcqp_mhe_update_device",
            "mpcqp_mhe_sync", "mpcqp_mhe_get", "mpcqp_mhe_device_ptr", "mpcqp_mhe_nk", "mpcqp_mhe_last_ms",
-           "mpcqp_mhe_register_columns")
+           "mpcqp_mhe_register_columns", "mpcqp_mhe_lanes_per_estimator")
 KEEP_WINDOWS = 1
 GET_XHAT0, GET_ZTILDE, GET_STATUS, GET_ITERS, GET_PBAR, GET_VHAT, GET_XHATWIN, GET_EPSILON = range(8)
 
@@ -59,6 +59,7 @@ def _bind(lib):
     lib.mpcqp_mhe_last_ms.restype = C.c_double
     lib.mpcqp_mhe_last_ms.argtypes = [C.c_void_p]
     lib.mpcqp_mhe_register_columns.argtypes = [C.c_void_p]
+    lib.mpcqp_mhe_lanes_per_estimator.argtypes = [C.c_void_p]
     lib._mhe_bound = True
     return lib
 
@@ -169,6 +170,10 @@ class MheHandle:
 
     def register_columns(self):
         return self.lib.mpcqp_mhe_register_columns(self._h)
+
+    def lanes_per_estimator(self):
+        """16: one estimator per DPP row (max(nx̂, nym) <= 16); 64: one per wavefront (the wide kernels, up to 32)."""
+        return self.lib.mpcqp_mhe_lanes_per_estimator(self._h)
 
 
 def _diag_cov(sig, B, n, name):
