@@ -345,6 +345,11 @@ int mpcqp_prepare(mpcqp_handle h);
 int mpcqp_lds_bytes(mpcqp_handle h);
 int mpcqp_kernel_kind(mpcqp_handle h);
 int mpcqp_row_groups(mpcqp_handle h, uint32_t* row_groups);
+/* How often the handle has built its block of step constants so far (per move-blocking interval and input channel the
+ * tightest U0min / U0max and the sum of the L weights; built before the first step or in mpcqp_prepare, and again after a
+ * setter changed the model, the weights or the bounds).  0 for a handle whose steps form these values themselves
+ * (dense L_Hp, MultipleShooting). */
+int mpcqp_step_consts_builds(mpcqp_handle h);
 int mpcqp_prebuild(const mpcqp_dims* dims, uint32_t row_groups);
 const char* mpcqp_last_build_error(void);
 

@@ -353,6 +353,116 @@ MPCQP_HD constexpr bool team_any_mfma(int count) {
 }
 
 // ------------------------------------------------------------------------------------------
+// One load phase for the set-up of a step (compile-time dims).  The set-up is ~15 kflop behind a chain of global loads:
+// written as "load, store to LDS, fence, next table" every phase sits out a memory latency of its own (round 5 measured
+// ~10 round trips, 25.7k cycles in Step::build() alone at C3).  None of the addresses depends on loaded data, so every
+// load is requested here, at the top of step_body, into registers (index clamped instead of a conditional, like
+// Qp::stage; 67 doubles per lane at C3 of the ~200 registers that are free before the iteration starts), and
+// load_tables / build / init_fold_H / run consume the registers in the order of the requests: one latency instead of
+// ten for a handle like C3.  Still behind the phase, as dependent loads of their own: the softness arrays of soft_init (C_umin /
+// C_umax / C_ymin / C_ymax / c_x0*) and exT where a handle has them, and the second read of Mdiag in init_fold_H (a cache hit).
+// The values and the arithmetic on them are the ones of the loops they replace, entry by entry.
+// Shapes: one Newton row per lane, at most four Ŷ rows per lane, a Σ table of at most 16 entries per lane; the K rows of
+// the free response (QY nx̂ doubles) join while they are at most 48 -- beyond, they keep their batches of eight behind x̂0
+// (a second latency).  Runtime dims, custom rows and the dense-weight variants keep their loops.
+// ------------------------------------------------------------------------------------------
+template <class DM>
+MPCQP_HD constexpr bool setup_prefetch() {
+    if constexpr (DM::is_static) {
+        return DM::nZ <= WAVE && DM::Hc < WAVE && DM::Hp <= WAVE && DM::nxh <= WAVE && DM::nu <= 16 && (DM::nY + WAVE - 1) / WAVE <= 4 &&
+               (DM::Hp * DM::ny * DM::nu + WAVE - 1) / WAVE <= 16 && DM::nw == 0 && !MPCQP_SPEC_DENSE;
+    } else {
+        return false;
+    }
+}
+
+template <class DM, bool ON = setup_prefetch<DM>()>
+struct SetupLoads {
+    static constexpr bool on = false;
+    template <class W>
+    MPCQP_HD void issue(const W&, const DM&, const Model&, const StepIO&, int) {}
+};
+
+template <class DM>
+struct SetupLoads<DM, true> {
+    static constexpr bool on = true;
+    static constexpr int NS = (DM::Hp * DM::ny * DM::nu + WAVE - 1) / WAVE;      // Σ entries per lane
+    static constexpr int QY = (DM::nY + WAVE - 1) / WAVE;                        // Ŷ rows per lane
+    static constexpr bool KREG = QY * DM::nxh <= 48;                             // the K rows of the lane's Ŷ rows as well
+    double S[NS];
+    int jl, blk;
+    double x0, lu[DM::nu], luc, zw;
+    double Bv[QY], K[KREG ? QY : 1][KREG ? DM::nxh : 1], Ry[QY], Md[QY];
+    double sc[SC_N];
+    double du[4];             // DUmin, DUmax, C_dumin, C_dumax of variable k = lane
+    double Y0[2][QY];         // Y0min, Y0max of row lane + 64 q
+    double Nd, Cw;
+
+    // a[k / 64] without a dynamic register index (k = lane + 64 q)
+    template <int Q>
+    MPCQP_HD static double pick(const double (&a)[Q], int k) {
+        double v = a[0];
+        MPCQP_UNROLL
+        for (int q_ = 1; q_ < Q; ++q_) v = (k >= WAVE * q_) ? a[q_] : v;
+        return v;
+    }
+
+    template <class W>
+    MPCQP_HD void issue(const W& w, const DM& d, const Model& m, const StepIO& io, int b) {
+        constexpr int ns = DM::Hp * DM::ny * DM::nu, nY = DM::nY, nDU = DM::nDU, nx = DM::nxh, nu = DM::nu, ny = DM::ny, n = DM::nZ;
+        const int lane = w.lane;
+        MPCQP_UNROLL
+        for (int q_ = 0; q_ < NS; ++q_) { const int i = lane + WAVE * q_; S[q_] = m.Stab[(size_t)b * ns + (i < ns ? i : 0)]; }
+        jl = 0; blk = 0;
+        if (!d.default_nb) { jl = m.jl[lane <= DM::Hc ? lane : 0]; blk = m.blk[lane < DM::Hp ? lane : 0]; }
+        x0 = io.xhat0[(size_t)b * nx + (lane < nx ? lane : 0)];
+        MPCQP_UNROLL
+        for (int cc = 0; cc < nu; ++cc) lu[cc] = io.lastu0[(size_t)b * nu + cc];
+        luc = io.lastu0[(size_t)b * nu + lane % nu];
+        const bool rconst = d.flags & 1u;
+        MPCQP_UNROLL
+        for (int q_ = 0; q_ < QY; ++q_) {
+            const int r = lane + WAVE * q_, rc = r < nY ? r : 0;
+            Bv[q_] = m.Bvec[(size_t)b * nY + rc];
+            if constexpr (KREG) {
+                MPCQP_UNROLL
+                for (int k = 0; k < nx; ++k) K[q_][k] = m.Ktab[(size_t)b * nx * nY + (size_t)k * nY + rc];
+            }
+        }
+        MPCQP_UNROLL
+        for (int q_ = 0; q_ < QY; ++q_) {
+            const int r = lane + WAVE * q_, rc = r < nY ? r : 0;
+            Ry[q_] = io.Ry[rconst ? (size_t)b * ny + (rc % ny) : (size_t)b * nY + rc];
+            Md[q_] = m.Mdiag[(size_t)b * nY + rc];
+        }
+        // (Optional arrays: the POINTER is selected -- an array that always exists stands in for an absent one and its value
+        //  is never used -- so the phase has no branch: inside a conditional block the compiler places the first use of a
+        //  loaded value next to the load, and with it a wait for everything requested so far.  For the same reason nothing
+        //  is computed from a loaded value in here.)
+        const int kc = lane < nDU ? lane : 0;
+        const double* anyk = m.Ndiag + (size_t)b * nDU + kc;
+        MPCQP_UNROLL
+        for (int a = 0; a < SC_N; ++a) sc[a] = *(m.stepc ? m.stepc + ((size_t)b * SC_N + a) * nDU + kc : anyk);
+        du[0] = *(m.DUmin ? m.DUmin + (size_t)b * nDU + kc : anyk);
+        du[1] = *(m.DUmax ? m.DUmax + (size_t)b * nDU + kc : anyk);
+        du[2] = *((d.neps && m.C_dumin) ? m.C_dumin + (size_t)b * nDU + kc : anyk);
+        du[3] = *((d.neps && m.C_dumax) ? m.C_dumax + (size_t)b * nDU + kc : anyk);
+        MPCQP_UNROLL
+        for (int q_ = 0; q_ < QY; ++q_) {
+            const int r = lane + WAVE * q_, rc = r < nY ? r : 0;
+            const double* anyr = m.Mdiag + (size_t)b * nY + rc;
+            Y0[0][q_] = *(m.Y0min ? m.Y0min + (size_t)b * nY + rc : anyr);
+            Y0[1][q_] = *(m.Y0max ? m.Y0max + (size_t)b * nY + rc : anyr);
+        }
+        Nd = *anyk;
+        Cw = d.neps ? m.Cwt[b] : 0.0;
+        // warm start: Z̃s = [Z̃prev[nu+1:nΔU]; 0; ϵprev]  (Step::run; the entry is read on a cold start too, and not used)
+        zw = io.Z[(size_t)b * n + (lane < nDU - nu ? lane + nu : (lane >= nDU && lane < n) ? lane : 0)];
+        MPCQP_SCHED_FENCE();      // (nothing of the phase sinks towards its use)
+    }
+};
+
+// ------------------------------------------------------------------------------------------
 // condensed problem resident in LDS + structured products with E, Pu, ex̂
 // ------------------------------------------------------------------------------------------
 template <class W, class DM>
@@ -408,16 +518,30 @@ struct Qp {
         }
     }
 
-    MPCQP_HD void load_tables() {
+    MPCQP_HD void load_tables() { load_tables(SetupLoads<DM, false>{}); }
+    // `pre`: the set-up's loads of a step are in flight / in registers already (SetupLoads)
+    template <class PRE>
+    MPCQP_HD void load_tables(const PRE& pre) {
         const int nb_ = d.ny * d.nu, ns = d.Hp * nb_;
-        stage(m.Stab + (size_t)b * ns, ns, [&](int i, double v) {
+        auto putS = [&](int i, double v) {
             const int blk_ = i / nb_, e = i - blk_ * nb_, a = e / d.nu;
             S[blk_ * sp + a * rs + (e - a * d.nu)] = v;
-        });
+        };
+        if constexpr (PRE::on) {
+            MPCQP_UNROLL
+            for (int q_ = 0; q_ < PRE::NS; ++q_) { const int i = w.lane + WAVE * q_; if (i < ns) putS(i, pre.S[q_]); }
+        } else {
+            stage(m.Stab + (size_t)b * ns, ns, putS);
+        }
         for (int i = w.lane; i < zpad_S(d) * sp; i += WAVE) sm[c.S + i] = 0.0;
         if (!d.default_nb) {
-            for (int i = w.lane; i <= d.Hc; i += WAVE) jlt[i] = m.jl[i];
-            for (int i = w.lane; i < d.Hp; i += WAVE) blkt[i] = m.blk[i];
+            if constexpr (PRE::on) {
+                if (w.lane <= d.Hc) jlt[w.lane] = pre.jl;
+                if (w.lane < d.Hp) blkt[w.lane] = pre.blk;
+            } else {
+                for (int i = w.lane; i <= d.Hc; i += WAVE) jlt[i] = m.jl[i];
+                for (int i = w.lane; i < d.Hp; i += WAVE) blkt[i] = m.blk[i];
+            }
         }
         if (pair_on(P_X) && m.exT) {      // (K2 of a specialisation with terminal rows runs before they are built)
             const int ne = d.Hc * d.nxh * d.nu;
@@ -1468,6 +1592,50 @@ MPCQP_HD void hessian_body(W& w, const DM& d, const Model& m, int b, double* sm)
 }
 
 // ------------------------------------------------------------------------------------------
+// Values of a move-blocking interval [t0, t1) of one input channel that only change with the handle's bounds / weights.
+// The step forms them with these functions when the handle carries no block of step constants (Model::stepc), and
+// k_step_consts forms the block with the very same functions: same operations in the same (step) order, same bits.
+// ------------------------------------------------------------------------------------------
+// tightest bound: bp[t nu], eight steps at a time, the index clamped to the interval's last step (min / max do not mind a repeat)
+MPCQP_HD inline double interval_tightest(const double* bp, int t0, int t1, int nu, bool upper) {
+    double v = upper ? INFINITY : -INFINITY;
+    for (int tb = t0; tb < t1; tb += 8) {
+        double xv[8];
+        MPCQP_UNROLL
+        for (int u = 0; u < 8; ++u) { const int t = tb + u < t1 ? tb + u : t1 - 1; xv[u] = bp[t * nu]; }
+        MPCQP_UNROLL
+        for (int u = 0; u < 8; ++u) v = upper ? fmin(v, xv[u]) : fmax(v, xv[u]);
+    }
+    return v;
+}
+// sum of Lp[t nu] in step order (eight loads in flight, Qp::stage)
+MPCQP_HD inline double interval_sum(const double* Lp, int t0, int t1, int nu) {
+    double acc = 0.0;
+    for (int tb = t0; tb < t1; tb += 8) {
+        double lv[8];
+        MPCQP_UNROLL
+        for (int u = 0; u < 8; ++u) { const int t = tb + u < t1 ? tb + u : t1 - 1; lv[u] = Lp[t * nu]; }
+        MPCQP_UNROLL
+        for (int u = 0; u < 8; ++u) acc += (tb + u < t1) ? lv[u] : 0.0;
+    }
+    return acc;
+}
+// entry k = (block j, channel c) of controller b of the block of step constants, out[b][SC_*][k]: lane k of a step reads its
+// four values with coalesced loads
+MPCQP_HD inline void step_consts_entry(const Dims& d, const Model& m, int b, int k, double* out) {
+    const int nu = d.nu, j = k / nu, cc = k - j * nu;
+    const int t0 = m.jl[j], t1 = m.jl[j + 1];           // (the table has Hc + 1 entries, the last one is Hp)
+    double* o = out + (size_t)b * SC_N * d.nDU + k;
+    o[SC_UMIN * d.nDU] = m.U0min ? interval_tightest(m.U0min + (size_t)b * d.nU + cc, t0, t1, nu, false) : -INFINITY;
+    o[SC_UMAX * d.nDU] = m.U0max ? interval_tightest(m.U0max + (size_t)b * d.nU + cc, t0, t1, nu, true) : INFINITY;
+    const double* Lp = m.Ldiag + (size_t)b * d.nU + cc;
+    o[SC_LSUM * d.nDU] = interval_sum(Lp, t0, t1, nu);
+    bool nz = false;                                     // (a NaN weight counts as non-zero: the step then runs its loop)
+    for (int t = t0; t < d.Hp; ++t) nz = nz || !(Lp[t * nu] == 0.0);
+    o[SC_LNZ * d.nDU] = nz ? 1.0 : 0.0;
+}
+
+// ------------------------------------------------------------------------------------------
 // Per-row interior-point state.  A row (group g, local index k) is owned by lane k % 64, and so
 // is primitive k of its pair: every access to row state is lane-local.  Runtime dims keep the
 // arrays in LDS; compile-time dims keep them in registers (slots resolved by full unrolling).
@@ -1571,6 +1739,9 @@ struct Step {
         Phi = qp.Phi;
         delta = d.dual_reg;
     }
+
+    // entry (block, channel) k of array `a` (SC_*) of this controller's step constants (Model::stepc non-null)
+    MPCQP_HD double stepc_at(int a, int k) const { return m.stepc[((size_t)b * SC_N + a) * d.nDU + k]; }
 
     // reference default softness: 0 for u and Δu, 1 for y and x̂end (construct.jl:909-913)
     MPCQP_HD double soft_init(int g, int k) const {
@@ -1713,30 +1884,37 @@ struct Step {
     }
 
     // ---- free response, gradient, right-hand sides (initpred!, linconstraint!) -------------
-    MPCQP_HD void build(const StepIO& io) {
+    // `pre`: the registers of the set-up's load phase (SetupLoads; PRE::on) -- every `if constexpr (PRE::on)` below takes a
+    // value from there that the other branch loads on the spot
+    template <class PRE>
+    MPCQP_HD void build(const StepIO& io, const PRE& pre) {
         const int nx = d.nxh, nu = d.nu, ny = d.ny, nd = d.nd, nY = d.nY;
         const double* x0 = sm + c.xh;                        // staged by step_body (after the optional correction)
         const double* lu = io.lastu0 + (size_t)b * nu;
         const double* K = m.Ktab + (size_t)b * nx * nY;
         const double* Bv = m.Bvec + (size_t)b * nY;
+        // lastu0 of channel cc (a constant after unrolling) / of the channel of variable k
+        auto lu_at = [&](int cc) { if constexpr (PRE::on) return pre.lu[cc]; else return lu[cc]; };
+        auto lu_of = [&](int cc) { if constexpr (PRE::on) return pre.luc; else return lu[cc]; };
+        if constexpr (PRE::on) fold_consts(pre);
         // F = B + K x̂0 + V lastu0 (+ G d0 + J D̂0)           execute.jl:249-255
-        for (int r = w.lane; r < nY; r += WAVE) {
-            const int t = r / ny, a = r - t * ny;
-            double acc = Bv[r];
-            {
-                // (the row's entries of K in batches of eight loads: see QP::stage)
-                int k = 0;
-                for (; k + 8 <= nx; k += 8) {
-                    double kv[8];
-                    MPCQP_UNROLL
-                    for (int u = 0; u < 8; ++u) kv[u] = K[(size_t)(k + u) * nY + r];
-                    MPCQP_UNROLL
-                    for (int u = 0; u < 8; ++u) acc += kv[u] * x0[k + u];
-                }
-                for (; k < nx; ++k) acc += K[(size_t)k * nY + r] * x0[k];
+        // (the row's entries of K in batches of eight loads: see QP::stage)
+        auto Kdot = [&](int r, double acc) {
+            int k = 0;
+            for (; k + 8 <= nx; k += 8) {
+                double kv[8];
+                MPCQP_UNROLL
+                for (int u = 0; u < 8; ++u) kv[u] = K[(size_t)(k + u) * nY + r];
+                MPCQP_UNROLL
+                for (int u = 0; u < 8; ++u) acc += kv[u] * x0[k + u];
             }
+            for (; k < nx; ++k) acc += K[(size_t)k * nY + r] * x0[k];
+            return acc;
+        };
+        auto Frest = [&](int r, double acc) {           // acc = B[r] + (K x̂0)[r]
+            const int t = r / ny, a = r - t * ny;
             const double* Sb = qp.S + t * qp.sp + a * qp.rs;    // V block t = Σ_t
-            for (int cc = 0; cc < nu; ++cc) acc += Sb[cc] * lu[cc];
+            for (int cc = 0; cc < nu; ++cc) acc += Sb[cc] * lu_at(cc);
             if (nd > 0) {
                 const double* Gd = m.Gdtab + (size_t)b * d.Hp * ny * nd;
                 const double* dd0 = io.d0 + (size_t)b * nd;
@@ -1750,6 +1928,24 @@ struct Step {
                 }
             }
             F[r] = acc;
+        };
+        if constexpr (PRE::on) {
+            MPCQP_UNROLL
+            for (int q_ = 0; q_ < PRE::QY; ++q_) {
+                const int r = w.lane + WAVE * q_;
+                if (r < nY) {
+                    double acc = pre.Bv[q_];
+                    if constexpr (PRE::KREG) {
+                        MPCQP_UNROLL
+                        for (int k = 0; k < nx; ++k) acc += pre.K[q_][k] * x0[k];
+                    } else {
+                        acc = Kdot(r, acc);
+                    }
+                    Frest(r, acc);
+                }
+            }
+        } else {
+            for (int r = w.lane; r < nY; r += WAVE) Frest(r, Kdot(r, Bv[r]));
         }
         w.sync();
         // q̃ = 2[(M Ẽ)'(F - R̂y) + (L P̃u)'(Tu lastu0 - R̂u)]   execute.jl:262-275 (deviation form)
@@ -1774,6 +1970,9 @@ struct Step {
                 for (int a2 = 0; a2 < ny; ++a2) acc += Mb[((size_t)t * ny + a2) * ny + a] * cy(t * ny + a2);
                 tY[r] = acc;
             }
+        } else if constexpr (PRE::on) {
+            MPCQP_UNROLL
+            for (int q_ = 0; q_ < PRE::QY; ++q_) { const int r = w.lane + WAVE * q_; if (r < nY) tY[r] = pre.Md[q_] * (F[r] - pre.Ry[q_]); }
         } else {
             for (int r = w.lane; r < nY; r += WAVE) tY[r] = Md[r] * cy(r);
         }
@@ -1781,10 +1980,23 @@ struct Step {
         w.sync();
         qp.Et_apply_add(tY, q, 2.0);
         const double* Ld = m.Ldiag + (size_t)b * d.nU;
+        // With the block of step constants and no per-step R̂u: weights that are zero from a block's first step on make every
+        // term of its sum a zero -- when that holds for every block of the controller (the usual Lwt = 0) the horizon of L is not
+        // read at all.  Otherwise the sum runs as ever (its terms L_t (lastu0 - R̂u_t) are not a product of a sum).
+        bool lterm = true;
+        if (m.stepc && !io.Ru) {
+            bool nz = false;
+            if constexpr (PRE::on) nz = w.lane < d.nDU && pre.sc[SC_LNZ] != 0.0;
+            else
+                for (int k = w.lane; k < d.nDU; k += WAVE) nz = nz || stepc_at(SC_LNZ, k) != 0.0;
+            lterm = w.any(nz);
+        }
         for (int k = w.lane; k < d.nDU; k += WAVE) {
             const int j = k / nu, cc = k - j * nu;
             double acc = 0.0;
-            if ((!DM::is_static || MPCQP_SPEC_DENSE) && m.Ldense) {    // dense L_Hp: (Pu' L (Tu lastu0 - R̂u))[k]
+            if (!lterm) {
+                // (every term is +-0 and the sum starts from +0: +0)
+            } else if ((!DM::is_static || MPCQP_SPEC_DENSE) && m.Ldense) {    // dense L_Hp: (Pu' L (Tu lastu0 - R̂u))[k]
                 const double* Lf = m.Ldense + (size_t)b * d.nU * d.nU;
                 for (int t = qp.jl(j); t < d.Hp; ++t)
                     for (int r2 = 0; r2 < d.nU; ++r2) {
@@ -1797,7 +2009,7 @@ struct Step {
                 const int t0 = qp.jl(j);
                 const double* Lp = Ld + cc;
                 const double* Rp = io.Ru ? io.Ru + (size_t)b * d.nU + cc : nullptr;
-                const double luc = lu[cc];
+                const double luc = lu_of(cc);
                 for (int tb = 0; tb < d.Hp; tb += 8) {
                     double lv[8], rv[8];
                     MPCQP_UNROLL
@@ -1819,10 +2031,15 @@ struct Step {
         for (int k = w.lane; k < d.nZ; k += WAVE) {
             double lo = -INFINITY, hi = INFINITY;
             if (k < d.nDU) {
-                if (m.DUmin && (!d.neps || !m.C_dumin || m.C_dumin[(size_t)b * d.nDU + k] == 0.0))
-                    lo = m.DUmin[(size_t)b * d.nDU + k];
-                if (m.DUmax && (!d.neps || !m.C_dumax || m.C_dumax[(size_t)b * d.nDU + k] == 0.0))
-                    hi = m.DUmax[(size_t)b * d.nDU + k];
+                if constexpr (PRE::on) {        // (one variable per lane: k = lane)
+                    if (m.DUmin && (!d.neps || !m.C_dumin || pre.du[2] == 0.0)) lo = pre.du[0];
+                    if (m.DUmax && (!d.neps || !m.C_dumax || pre.du[3] == 0.0)) hi = pre.du[1];
+                } else {
+                    if (m.DUmin && (!d.neps || !m.C_dumin || m.C_dumin[(size_t)b * d.nDU + k] == 0.0))
+                        lo = m.DUmin[(size_t)b * d.nDU + k];
+                    if (m.DUmax && (!d.neps || !m.C_dumax || m.C_dumax[(size_t)b * d.nDU + k] == 0.0))
+                        hi = m.DUmax[(size_t)b * d.nDU + k];
+                }
             } else {
                 lo = 0.0;            // ϵ >= 0
             }
@@ -1871,28 +2088,40 @@ struct Step {
                     if (bd) {
                         const int j = k / nu, cc = k - j * nu;
                         const int t0 = qp.jl(j), t1 = (j + 1 < d.Hc) ? qp.jl(j + 1) : d.Hp;
-                        const double* bp = bd + (size_t)b * d.nU + cc;
-                        double v = (g & 1) ? INFINITY : -INFINITY;
-                        // eight steps at a time, the index clamped to the interval's last step (min / max do not mind a repeat)
-                        for (int tb = t0; tb < t1; tb += 8) {
-                            double xv[8];
-                            MPCQP_UNROLL
-                            for (int u = 0; u < 8; ++u) { const int t = tb + u < t1 ? tb + u : t1 - 1; xv[u] = bp[t * nu]; }
-                            MPCQP_UNROLL
-                            for (int u = 0; u < 8; ++u) v = (g & 1) ? fmin(v, xv[u]) : fmax(v, xv[u]);
+                        // (the handle's block of step constants holds it; else: formed here)
+                        double v;
+                        if (m.stepc) {
+                            if constexpr (PRE::on) v = pre.sc[(g & 1) ? SC_UMAX : SC_UMIN];
+                            else v = stepc_at((g & 1) ? SC_UMAX : SC_UMIN, k);
+                        } else {
+                            v = interval_tightest(bd + (size_t)b * d.nU + cc, t0, t1, nu, g & 1);
                         }
-                        bound = (g & 1) ? v - lu[cc] : -v + lu[cc];
+                        bound = (g & 1) ? v - lu_of(cc) : -v + lu_of(cc);
                     }
                     break;
                 }
                 case 2 * P_DU:
-                    if (m.DUmin && m.C_dumin && m.C_dumin[o] != 0.0) bound = -m.DUmin[o];
+                    if constexpr (PRE::on) { if (m.DUmin && m.C_dumin && pre.du[2] != 0.0) bound = -pre.du[0]; }
+                    else { if (m.DUmin && m.C_dumin && m.C_dumin[o] != 0.0) bound = -m.DUmin[o]; }
                     break;
                 case 2 * P_DU + 1:
-                    if (m.DUmax && m.C_dumax && m.C_dumax[o] != 0.0) bound = m.DUmax[o];
+                    if constexpr (PRE::on) { if (m.DUmax && m.C_dumax && pre.du[3] != 0.0) bound = pre.du[1]; }
+                    else { if (m.DUmax && m.C_dumax && m.C_dumax[o] != 0.0) bound = m.DUmax[o]; }
                     break;
-                case 2 * P_Y: if (hosted) bound = (g == d.eps_host()) ? 0.0 : INFINITY; else if (m.Y0min) bound = -m.Y0min[o] + F[k]; break;
-                case 2 * P_Y + 1: if (hosted) bound = (g == d.eps_host()) ? 0.0 : INFINITY; else if (m.Y0max) bound = m.Y0max[o] - F[k]; break;
+                case 2 * P_Y:
+                    if (hosted) bound = (g == d.eps_host()) ? 0.0 : INFINITY;
+                    else if (m.Y0min) {
+                        if constexpr (PRE::on) bound = -PRE::pick(pre.Y0[0], k) + F[k];
+                        else bound = -m.Y0min[o] + F[k];
+                    }
+                    break;
+                case 2 * P_Y + 1:
+                    if (hosted) bound = (g == d.eps_host()) ? 0.0 : INFINITY;
+                    else if (m.Y0max) {
+                        if constexpr (PRE::on) bound = PRE::pick(pre.Y0[1], k) - F[k];
+                        else bound = m.Y0max[o] - F[k];
+                    }
+                    break;
                 case 2 * P_X: if (m.x0min) bound = -m.x0min[o] + fx[k]; break;
                 case 2 * P_X + 1: if (m.x0max) bound = m.x0max[o] - fx[k]; break;
                 case 2 * P_W: if (m.Wmin) bound = -m.Wmin[o] + Fw_at(k, io, x0, lu); break;
@@ -2073,22 +2302,28 @@ struct Step {
     MPCQP_HD double H2L_load(int k) const {
         if (k >= d.nDU) return 0.0;
         const int j = k / d.nu, cc = k - j * d.nu;
+        if (m.stepc) return 2.0 * stepc_at(SC_LSUM, k);
         const int t0 = qp.jl(j), t1 = (j + 1 < d.Hc) ? qp.jl(j + 1) : d.Hp;
-        const double* Lp = m.Ldiag + (size_t)b * d.nU + cc;
-        double acc = 0.0;
-        for (int tb = t0; tb < t1; tb += 8) {           // eight loads in flight (QP::stage)
-            double lv[8];
-            MPCQP_UNROLL
-            for (int u = 0; u < 8; ++u) { const int t = tb + u < t1 ? tb + u : t1 - 1; lv[u] = Lp[t * d.nu]; }
-            MPCQP_UNROLL
-            for (int u = 0; u < 8; ++u) acc += (tb + u < t1) ? lv[u] : 0.0;
-        }
-        return 2.0 * acc;
+        return 2.0 * interval_sum(m.Ldiag + (size_t)b * d.nU + cc, t0, t1, d.nu);
     }
     MPCQP_HD double H2L(int k) const { return one_row_per_lane<DM>() ? h2l_ : H2L_load(k); }
+    // this lane's 2 N_k / 2 C and 2 sum_{t in block(k)} L_t from the registers of the set-up's load phase (SetupLoads: one row
+    // per lane); init_fold_H<true> then loads the output weights only.  (Those stay a load of their own although the phase has
+    // M_r in a register for q~: with hwy_ formed from that register the C3 kernel spills two more loop invariants -- 12
+    // instead of 8 spilled VGPRs, measured in six variants of where and how hwy_ is formed, lib/isa_resources.txt.  The second
+    // read hits the cache and nothing waits for it before the first residual evaluation, a G z later.)
+    template <class PRE>
+    MPCQP_HD void fold_consts(const PRE& pre) {
+        const int k = w.lane;
+        h2n_ = k < d.nDU ? 2.0 * pre.Nd : ((d.neps && k == d.nZ - 1) ? 2.0 * pre.Cw : 0.0);
+        h2l_ = m.stepc ? (k < d.nDU ? 2.0 * pre.sc[SC_LSUM] : 0.0) : H2L_load(k);
+    }
+    template <bool LOADED = false>
     MPCQP_HD void init_fold_H() {
         double lmx = 0.0;
-        if (one_row_per_lane<DM>()) {
+        if (LOADED) {
+            lmx = fabs(h2l_);
+        } else if (one_row_per_lane<DM>()) {
             h2l_ = H2L_load(w.lane);
             h2n_ = H2N_load(w.lane);
             lmx = fabs(h2l_);
@@ -3290,15 +3525,19 @@ struct Step {
     }
 
     // ---- rp, mu ; then rd = H̃ z + q + G' lam with H̃ freshly staged in Phi ---------------------
-    MPCQP_HD void residuals(double& mu, double& rpn, double& rdn, double& nd_) {
+    // `gz_kept`: the rows hold (G z)[row] of this very z in gd and tA[P_Y] still holds E z (the starting point of run() has
+    // just formed them): the product is not formed a second time.
+    MPCQP_HD void residuals(double& mu, double& rpn, double& rdn, double& nd_, bool gz_kept = false) {
         const int n = d.nZ;
         double musum = 0.0, rpmax = 0.0;
-        apply_G(z, [&](Row& r, double gz) {
+        auto rowres = [&](Row& r, double gz) {
             const double v = gz + r.s - r.h;
             r.rp = v;
             rpmax = fmx_abs(rpmax, v);
             musum += r.s * r.lam;
-        });
+        };
+        if (gz_kept) for_rows([&](int, int, Row& r) { if (fin(r)) rowres(r, r.gd); });
+        else apply_G(z, rowres);
         mu = w.sum(musum) / wsum;
         rpn = w.maxv(rpmax);
         if (fold_H) {
@@ -3504,21 +3743,27 @@ struct Step {
         apply_G(dz, [&](Row& r, double g) { r.gd = g; rowfn(r); });
     }
 
-    MPCQP_HD int run(const StepIO& io, int& iters_out) {
+    template <class PRE>
+    MPCQP_HD int run(const StepIO& io, int& iters_out, const PRE& pre) {
         const int n = d.nZ;
         // warm start: Z̃s = [Z̃prev[nu+1:nΔU]; 0; ϵprev]       transcription.jl:1001-1004
         const double* Zg = io.Z + (size_t)b * n;
         const bool cold = d.flags & 2u;
-        for (int k = w.lane; k < n; k += WAVE) {
-            double v = 0.0;
-            if (!cold) {
-                if (k < d.nDU - d.nu) v = Zg[k + d.nu];
-                else if (k >= d.nDU) v = Zg[k];
+        if constexpr (PRE::on) {
+            const bool prev = !cold && (w.lane < d.nDU - d.nu || (w.lane >= d.nDU && w.lane < n));
+            if (w.lane < n) z[w.lane] = prev ? pre.zw : 0.0;
+        } else {
+            for (int k = w.lane; k < n; k += WAVE) {
+                double v = 0.0;
+                if (!cold) {
+                    if (k < d.nDU - d.nu) v = Zg[k + d.nu];
+                    else if (k >= d.nDU) v = Zg[k];
+                }
+                z[k] = v;
             }
-            z[k] = v;
         }
         w.sync();
-        if (mact != 0) init_fold_H();
+        if (mact != 0) init_fold_H<PRE::on>();
         if (mact == 0) {
             // no finite row at all: Z̃ = -H̃^{-1} q̃ (what ExplicitMPC computes, explicitmpc.jl:216)
             load_H();
@@ -3537,7 +3782,8 @@ struct Step {
         }
         // warm start kept in a register for the error path (nZ <= 64: one entry per lane; larger
         // problems read it again from the caller's Z̃, which is only overwritten after the solve)
-        const double zws = (w.lane < n) ? z[w.lane] : 0.0;
+        // (with the set-up's load phase the error path reads every entry again: no register is held across the solve for it)
+        const double zws = (!PRE::on && w.lane < n) ? z[w.lane] : 0.0;
         double mu, rpn, rdn, ndd;
         // ---- starting point (no factorisation): slacks of the warm start pushed to >= 1,
         //      multipliers on the central path of mu = 10:  s = max(h - G z, 1), lam = 10 / s.
@@ -3548,7 +3794,7 @@ struct Step {
         const double* lam_prev = ((d.flags & 8u) && !cold) ? io.lam_prev : nullptr;
         if (lam_prev) {
             const double* lp = lam_prev + (size_t)b * d.nrows();
-            apply_G(z, [&](Row& r, double gz) { r.s = r.h - gz; });
+            apply_G(z, [&](Row& r, double gz) { r.s = r.h - gz; r.gd = gz; });
             for_rows([&](int g, int k, Row& r) {
                 if (!fin(r)) return;
                 // s = max(h - G z, 1e-3), lam = max(lam_prev, mu0/s), s = max(s, mu0/lam), mu0 = 1e-3.
@@ -3565,8 +3811,12 @@ struct Step {
             apply_G(z, [&](Row& r, double gz) {
                 r.s = fmax(r.h - gz, 1.0);
                 r.lam = 10.0 * r.wt * rcp(r.s);
+                r.gd = gz;
             });
         }
+        // (G z)[row] of the starting point stays in the row's gd -- free until the first Newton solve writes it -- and E z in
+        // tA[P_Y]: the first exact residual evaluation takes both from there
+        bool gz_kept = true;
         int status = ST_ITERATION_LIMIT;
         int it = 0;
         // Residuals are evaluated exactly (G z, G'lam, H̃ z) at the first iterate and whenever the
@@ -3599,7 +3849,8 @@ struct Step {
             }
             MPCQP_MTIC();
             if (exact) {
-                residuals(mu, rpn, rdn, ndd);      // also stages H̃ in Phi
+                residuals(mu, rpn, rdn, ndd, gz_kept);      // also stages H̃ in Phi
+                gz_kept = false;
                 exact = false;
                 verified = true;
                 // The dual residual has hit the floor of the float64 normal equations when an exact
@@ -3746,8 +3997,8 @@ struct Step {
         // (MPCQP_FLAG_KEEP_ITERATE: diagnostics -- the iterate after exactly max_iter iterations is what the caller wants)
         if (status == ST_ITERATION_LIMIT && !(rpn <= 1e-6 * nh) && !(d.flags & 32u)) status = ST_ERROR;
         if (status == ST_ERROR) {
-            if (w.lane < n) z[w.lane] = zws;          // mpc.Z̃ .= Z̃s   execute.jl:499-500
-            for (int k = w.lane + WAVE; k < n; k += WAVE)
+            if (!PRE::on && w.lane < n) z[w.lane] = zws;          // mpc.Z̃ .= Z̃s   execute.jl:499-500
+            for (int k = w.lane + (PRE::on ? 0 : WAVE); k < n; k += WAVE)
                 z[k] = cold ? 0.0 : (k < d.nDU - d.nu) ? Zg[k + d.nu] : (k >= d.nDU) ? Zg[k] : 0.0;
             w.sync();
         }
@@ -3770,15 +4021,19 @@ struct Step {
 template <class W, class DM>
 MPCQP_HD void step_body(W& w, const DM& d, const Model& m, const StepIO& io, int b, double* sm) {
     const long long t_in_ = Step<W, DM>::clock64_();
+    SetupLoads<DM> pre;
+    pre.issue(w, d, m, io, b);
     Qp<W, DM> qp(w, d, m, b, sm);
-    qp.load_tables();
+    qp.load_tables(pre);
     const long long t_tab_ = Step<W, DM>::clock64_();
     // x̂0 of this period into LDS; with kf_y0m the SteadyKalmanFilter correction first
     // (correct_estimate_obsv!, src/estimator/kalman.jl:284-295; same arithmetic order as kf_correct_lane)
     {
         const int nx = d.nxh, ny = d.ny, nd = d.nd;
         double* xh = sm + qp.c.xh;
-        for (int i = w.lane; i < nx; i += WAVE) xh[i] = io.xhat0[(size_t)b * nx + i];
+        if constexpr (SetupLoads<DM>::on) { if (w.lane < nx) xh[w.lane] = pre.x0; }
+        else
+            for (int i = w.lane; i < nx; i += WAVE) xh[i] = io.xhat0[(size_t)b * nx + i];
         w.sync();
         if (io.kf_y0m) {
             const double* Cm = m.C + (size_t)b * ny * nx;
@@ -3807,7 +4062,7 @@ MPCQP_HD void step_body(W& w, const DM& d, const Model& m, const StepIO& io, int
     }
     Step<W, DM> st(qp);
     const long long t_b0_ = Step<W, DM>::clock64_();
-    st.build(io);
+    st.build(io, pre);
     const long long t_b1_ = Step<W, DM>::clock64_();
     if ((d.flags & 4u) && io.q_keep) {
         for (int k = w.lane; k < d.nZ; k += WAVE) io.q_keep[(size_t)b * d.nZ + k] = st.q[k];
@@ -3817,7 +4072,7 @@ MPCQP_HD void step_body(W& w, const DM& d, const Model& m, const StepIO& io, int
         for (int r = w.lane; r < d.nY; r += WAVE) io.Yhat0[(size_t)b * d.nY + r] = st.F[r];
     int iters = 0;
     const long long t_run0 = Step<W, DM>::clock64_();
-    const int status = st.run(io, iters);
+    const int status = st.run(io, iters, pre);
     if (io.prof) {
         st.prof_[15] = (double)(Step<W, DM>::clock64_() - t_run0);
 #ifdef MPCQP_PROFILE_SETUP      // (developer switch: the set-up of the step in the slots of the Newton sub-phases)

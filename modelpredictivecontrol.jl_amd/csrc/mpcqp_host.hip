@@ -37,6 +37,11 @@ struct mpcqp_handle_s {
     // launch is skipped (the problem did not fit the LDS at that moment: condensed_fits depends on the row groups, which
     // set_bounds / set_custom_bounds may shrink later); ensure_hessian() launches K2 lazily wherever H~ is about to be read.
     bool hessian_valid = false;
+    // Model::stepc holds the step constants of the CURRENT bounds and weights (k_step_consts).  Every setter that writes one of
+    // their inputs drops the block (invalidate_stepc); ensure_stepc() builds it lazily on the stream of the next step.
+    bool stepc_valid = false;
+    DBuf stepc;
+    int stepc_builds = 0;      // launches of k_step_consts so far (mpcqp_step_consts_builds)
     std::vector<int> nb, jl, blk;
     std::vector<void*> owned;
     // model / weights / bounds storage
@@ -287,6 +292,24 @@ static int refresh_hessian(mpcqp_handle h, hipStream_t st) {
 }
 static int ensure_hessian(mpcqp_handle h, hipStream_t st) { return h->hessian_valid ? MPCQP_OK : refresh_hessian(h, st); }
 
+// the step constants: dropped by the setters, built where a step is about to be launched.  Without the launcher (a library
+// linked without the kernel) or with a dense L_Hp the handle carries no block and the step forms the values itself.
+static void invalidate_stepc(mpcqp_handle h) { h->stepc_valid = false; h->m.stepc = nullptr; }
+static int ensure_stepc(mpcqp_handle h, hipStream_t st) {
+    if (h->stepc_valid) return MPCQP_OK;
+    h->m.stepc = nullptr;
+    if (!step_consts_available() || !h->have_weights || h->stage_only || h->m.Ldense) return MPCQP_OK;
+    const Dims& d = h->d;
+    int rc = dev_alloc(h, h->stepc, (size_t)d.B * SC_N * d.nDU * sizeof(double));
+    if (rc) return rc;
+    if (h->step_timed) HIPCHK(hipStreamWaitEvent(st, h->ev_s1, 0));     // (an earlier step, on whatever stream, may still read the block)
+    HIPCHK(launch_step_consts(d, h->m, (double*)h->stepc.p, st));
+    h->m.stepc = (const double*)h->stepc.p;
+    h->stepc_valid = true;
+    ++h->stepc_builds;
+    return MPCQP_OK;
+}
+
 static int condense(mpcqp_handle h, hipStream_t st, bool timed) {
     const Dims& d = h->d;
     if (!h->have_model || h->stage_only) return MPCQP_OK;
@@ -331,6 +354,7 @@ int mpcqp_set_model(mpcqp_handle h, const double* Ahat, const double* Bu, const 
     h->m.Dd = d.nd > 0 ? (const double*)h->Dd.p : nullptr;
     h->m.dop = dop ? (const double*)h->dop.p : nullptr;
     h->have_model = true;
+    invalidate_stepc(h);
     rc = condense(h, h->stream, true);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -353,6 +377,7 @@ int mpcqp_set_weights(mpcqp_handle h, const double* Mdiag, const double* Ndiag,
     h->m.Ldiag = (const double*)h->Ldiag.p;
     h->m.Cwt = d.neps ? (const double*)h->Cwt.p : nullptr;
     h->have_weights = true;
+    invalidate_stepc(h);
     { int rc = refresh_hessian(h, h->stream); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
@@ -370,6 +395,7 @@ int mpcqp_set_output_weight_blocks(mpcqp_handle h, const double* Mblk) {
     } else {
         h->m.Mblk = nullptr;
     }
+    invalidate_stepc(h);
     { int rc = refresh_hessian(h, h->stream); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
@@ -393,6 +419,7 @@ int mpcqp_set_dense_weights(mpcqp_handle h, const double* M_Hp, const double* N_
         }
     }
     d.dense_w = (h->m.Mfull || h->m.Ldense) ? 1 : 0;     // (a dense N_Hc only changes H̃: any step kernel serves it)
+    invalidate_stepc(h);
     { int rc = refresh_hessian(h, h->stream); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
@@ -503,6 +530,7 @@ int mpcqp_set_bounds(mpcqp_handle h, const mpcqp_bounds* bin) {
                         if (cu[b * d.nU + t * d.nu + c] != cu[b * d.nU + h->jl[j] * d.nu + c]) { varies = true; break; }
     }
     h->stage_rows = varies;
+    invalidate_stepc(h);
     ON_DEVICE(h);
     const double* src[16] = {bin->U0min, bin->U0max, bin->DUmin, bin->DUmax, bin->Y0min, bin->Y0max,
                              bin->x0min, bin->x0max, bin->C_umin, bin->C_umax, bin->C_dumin,
@@ -637,6 +665,8 @@ static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* l
 #endif
     // (refusals first: nothing is recorded on the stream for a step that does not run)
     if (uses_stage_kernel(h) && ms_unsupported(h)) return MPCQP_ERR_UNSUPPORTED;      // (the fused Kalman loop runs on the stage-structured kernel too since round 6)
+    // (the step constants are handle data like H~: built before the step's time starts)
+    if (!uses_stage_kernel(h)) { int rc = ensure_stepc(h, st); if (rc) return rc; }
     HIPCHK(hipEventRecord(h->ev_s0, st));
     if (uses_stage_kernel(h)) {
         // the stage-structured kernel: model as equality constraints, Riccati recursion, H~ and E never formed
@@ -1005,7 +1035,14 @@ int mpcqp_prepare(mpcqp_handle h) {
         // as its steps are (mpcqp_step*: MPCQP_ERR_UNSUPPORTED) -- the answer is what the steps WILL do
         return ms_unsupported(h) ? MPCQP_ERR_UNSUPPORTED : MPCQP_KERNEL_MS;
     }
-    { ON_DEVICE(h); int rc = ensure_hessian(h, h->stream); if (rc) return rc; }
+    {   // the steps that follow run on the caller's stream, which nothing orders after the handle's: like every setter,
+        // return with the handle's data complete
+        ON_DEVICE(h);
+        int rc = ensure_hessian(h, h->stream);
+        if (!rc) rc = ensure_stepc(h, h->stream);
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
     int kind = prepare_step(h->d, h->m, &g_build_err);
     // an on-demand kernel that has not been checked yet (fresh build, or a cache some other process filled): compare
     // it with the runtime-dimension kernel once; needs the model and weights (BatchLinMPC prepares before its first step)
@@ -1058,6 +1095,11 @@ int mpcqp_kernel_kind(mpcqp_handle h) {
     if (!h) return MPCQP_ERR_NULL;
     if (uses_stage_kernel(h)) return ms_unsupported(h) ? MPCQP_ERR_UNSUPPORTED : MPCQP_KERNEL_MS;
     return step_kernel_kind(h->d, h->m);
+}
+
+int mpcqp_step_consts_builds(mpcqp_handle h) {
+    if (!h) return MPCQP_ERR_NULL;
+    return h->stepc_builds;
 }
 
 int mpcqp_row_groups(mpcqp_handle h, uint32_t* row_groups) {

@@ -59,6 +59,13 @@ __global__ __launch_bounds__(64) void k_step(Dims d, Model m, StepIO io) {
     step_body(w, d, m, io, (int)blockIdx.x, mpcqp_smem);
 }
 
+// per-handle step constants (Model::stepc): one thread per (controller, block, channel); runs once per change of the
+// bounds / weights, so the strided reads along the horizon do not matter
+__global__ __launch_bounds__(256) void k_step_consts(Dims d, Model m, double* out) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < (long long)d.B * d.nDU) step_consts_entry(d, m, (int)(g / d.nDU), (int)(g % d.nDU), out);
+}
+
 // SteadyKalmanFilter steps: npad = next power of two >= nx̂ lanes per problem, 256-thread blocks
 __global__ __launch_bounds__(256) void k_kf_correct(Dims d, Model m, KfParams kf, double* xhat0,
                                                     const double* y0m, const double* d0, int npad) {
@@ -82,6 +89,12 @@ hipError_t launch_predmat(const Dims& d, const Model& m, bool terminal, hipStrea
     hipError_t e = ensure_lds((const void*)k_predmat, lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_predmat, dim3(d.B), dim3(WAVE), lds, st, d, m, terminal ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_step_consts(const Dims& d, const Model& m, double* out, hipStream_t st) {
+    const long long total = (long long)d.B * d.nDU;
+    hipLaunchKernelGGL(k_step_consts, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d, m, out);
     return hipGetLastError();
 }
 

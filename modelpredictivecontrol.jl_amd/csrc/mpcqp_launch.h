@@ -12,6 +12,11 @@ hipError_t launch_predmat(const Dims& d, const Model& m, bool terminal, hipStrea
 hipError_t launch_hessian(const Dims& d, const Model& m, hipStream_t st);
 hipError_t launch_step(const Dims& d, const Model& m, const StepIO& io, hipStream_t st);
 hipError_t launch_step_spec_or_aot(const Dims& d, const Model& m, const StepIO& io, hipStream_t st);   // never the small-problem kernel
+// Per-handle step constants (Model::stepc) into `out` ([B][SC_N][nDU]).  WEAK declaration: a library linked without the
+// kernel (the CPU emulator of tests/emu defines the entry points above only) still links, the handle then never carries
+// the block and the step keeps forming these values itself.
+__attribute__((weak)) hipError_t launch_step_consts(const Dims& d, const Model& m, double* out, hipStream_t st);
+inline bool step_consts_available() { return launch_step_consts != nullptr; }
 size_t step_lds_bytes(const Dims& d);
 // kernel a step runs on: 0 runtime-dimension kernel, 1 ahead-of-time specialisation, 2 on-demand specialisation
 int step_kernel_kind(const Dims& d, const Model& m);   // (m: the handle's arrays -- a block / dense M_Hp excludes the small-problem kernel)

@@ -42,7 +42,7 @@
 
 // Revision of the kernel sources / device structs: part of the name of cached on-demand
 // specialisations, so that objects built from older sources are never loaded.
-#define MPCQP_KERNEL_REV 12       // 12: matrix-core operands of E'DE in registers (EtDE_add_mfma, register-operand form); 11: on-demand objects compiled with the pragma-unroll threshold lifted (no scratch arrays / flat accesses from eight tile rows on); 10: the row eps >= 0 rides in a Ŷ group (eps_host_group); 9: a blocked step (alpha < 1/2) no longer passes the last-step test; 8: MPCQP_FLAG_KEEP_ITERATE
+#define MPCQP_KERNEL_REV 13       // 13: Model::stepc (per-handle step constants), one load phase for the set-up; 12: matrix-core operands of E'DE in registers (EtDE_add_mfma, register-operand form); 11: on-demand objects compiled with the pragma-unroll threshold lifted (no scratch arrays / flat accesses from eight tile rows on); 10: the row eps >= 0 rides in a Ŷ group (eps_host_group); 9: a blocked step (alpha < 1/2) no longer passes the last-step test; 8: MPCQP_FLAG_KEEP_ITERATE
 
 namespace mpcqp {
 
@@ -126,7 +126,12 @@ struct Model {
     // horizon tables
     const int* jl;   // [Hc+1] block starts j_l (move_blocking, construct.jl:597-660)
     const int* blk;  // [Hp]   index of the block that holds step t
+    // per-handle step constants (step_consts_entry, mpcqp_bodies.h), built once by k_step_consts and rebuilt after a setter
+    // changed one of their inputs; null: the step forms them itself (launcher absent, dense L_Hp)
+    const double* stepc;   // [B][SC_N][nDU]  per (block, channel): tightest U0min, tightest U0max, sum_t L[t, c] over the block's
+                           //                 steps, 1 if some L[t, c] from the block's first step on is non-zero
 };
+enum { SC_UMIN = 0, SC_UMAX = 1, SC_LSUM = 2, SC_LNZ = 3, SC_N = 4 };
 
 // steady-state Kalman filter of the batch (estimator/kalman.jl:284-309)
 struct KfParams {
