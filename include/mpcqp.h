@@ -135,8 +135,10 @@ int mpcqp_set_weights(mpcqp_handle h, const double* Mdiag, const double* Ndiag,
  *                            same optimal ΔU; mpcqp_step writes Z̃ = [ΔU; ϵ] as always and X̂0 is read with
  *                            mpcqp_get(MPCQP_GET_XHAT_MS).
  * Not every handle can run MultipleShooting: mpcqp_transcription_supported returns 0 when it can, else a bit mask
- * (1 block / dense weight matrices, 4 stage data beyond 160 KB of LDS, 8 KEEP_QP / WARM_DUAL flags; 2, custom linear
- * constraints, is kept as a value but no longer set: the stage-structured kernel takes them, every row in one stage); a step of an unsupported MultipleShooting handle returns MPCQP_ERR_UNSUPPORTED, and so do mpcqp_prepare and
+ * (1 a weight matrix of mpcqp_set_dense_weights that couples different stages -- such a cost is not block-tridiagonal and no
+ * Riccati recursion solves it -- or output-weight blocks beyond ny = 256; 4 stage data beyond 160 KB of LDS.  2, custom linear
+ * constraints, and 8, MPCQP_FLAG_KEEP_QP / _WARM_DUAL, are kept as values but no longer set: the stage-structured kernel takes
+ * them).  A step of an unsupported MultipleShooting handle returns MPCQP_ERR_UNSUPPORTED, and so do mpcqp_prepare and
  * mpcqp_kernel_kind for it (the Python mirror then keeps the SingleShooting kernels and says so).  The fused Kalman loop
  * (mpcqp_loop_device) runs on the stage-structured kernel too (round 6; MPCQP_ERR_UNSUPPORTED before).
  *
@@ -176,7 +178,15 @@ int mpcqp_set_output_weight_blocks(mpcqp_handle h, const double* Mblk);
  * mpcqp_set_weights.  H~ is rebuilt (K2, runtime-dimension kernel).  With a dense M_Hp or L_Hp the step
  * evaluates M (F - R^y) and L (Tu lastu0 - R^u) densely: on an on-demand specialisation that carries these products
  * (mpcqp_prepare AFTER this call; the kernels compiled into the library do not) or on the runtime-dimension kernel; a
- * dense N_Hc only changes H~ and keeps every specialised step kernel.                                           */
+ * dense N_Hc only changes H~ and keeps every specialised step kernel.
+ * The stage-structured kernel (MultipleShooting, and SingleShooting handles beyond the condensed kernels) takes a matrix
+ * that is STAGE-SEPARABLE: every entry outside its diagonal blocks -- ny x ny per prediction step for M_Hp, nu x nu per
+ * free move for N_Hc, nu x nu per step for L_Hp -- is exactly 0.0 in every member of the batch (an L_Hp entry that couples
+ * two steps of one move-blocking interval is not separable) and every diagonal block is symmetric, entry for entry.  The
+ * matrices are classified here, from the host pointers; one that couples stages, or has a block that is not symmetric,
+ * gives reason 1 of mpcqp_transcription_supported.  A stage-separable M_Hp given here takes precedence over the blocks of
+ * an earlier mpcqp_set_output_weight_blocks on that kernel (its blocks are copied out and uploaded here, once); M_Hp =
+ * NULL gives the earlier blocks back.                                                                                 */
 int mpcqp_set_dense_weights(mpcqp_handle h, const double* M_Hp, const double* N_Hc, const double* L_Hp);
 
 /* Custom linear inequality constraints over k .. k+Hp (keywords Wy, Wu, Wd, Wr of LinMPC,
@@ -255,7 +265,8 @@ int mpcqp_recondense_device(mpcqp_handle h, void* stream);
  *   STEPRESP Σ_m = Ĉ S(m) B̂u (ny,nu,Hp,B)       transcription.jl:134-139 (E is block-Toeplitz in it)
  *   KMAT     K (nY,nx̂,B)                        transcription.jl:143-147
  *   BVEC     B (nY,B)                           transcription.jl:184-192
- *   QTILDE   q̃ (nZ,B), FVEC F (nY,B) of the last step (needs MPCQP_FLAG_KEEP_QP)
+ *   QTILDE   q̃ (nZ,B), FVEC F (nY,B) of the last step (needs MPCQP_FLAG_KEEP_QP); the condensed definitions and layout
+ *            (Ŷ0 = E ΔU + F; q̃ over Z̃ = [ΔU; ϵ]) also when the step ran on the stage-structured kernel, which never forms E
  */
 #define MPCQP_GET_HESSIAN   1
 #define MPCQP_GET_STEPRESP  2

@@ -921,7 +921,7 @@ class BatchLinMPC:
                 if why:
                     self.hd.set_transcription(SINGLE_SHOOTING)
                     warnings.warn("mpcqp: MultipleShooting kernel not available for this controller (reason mask "
-                                  f"{why}: 1 block/dense weights, 4 LDS, 8 flags): the SingleShooting "
+                                  f"{why}: 1 weights that couple stages, 4 LDS): the SingleShooting "
                                   "kernels solve the same problem", RuntimeWarning)
                 else:
                     self._ms_kernel = True

@@ -52,6 +52,13 @@ struct mpcqp_handle_s {
     DBuf s_x, s_lu, s_ry, s_ru, s_d0, s_dh, s_Z, s_u0, s_st, s_it, s_yh;
     DBuf keep_q, keep_F, prof, lam, audit;
     bool lam_valid = false;     // lam holds the multipliers of the previous step (MPCQP_FLAG_WARM_DUAL)
+    bool lam_stage = false;     // ... in the row order of the stage-structured kernel (else of the condensed kernels)
+    int lam_rows = 0;           // ... that many per controller
+    // mpcqp_set_dense_weights: the matrix is stage-separable, every entry outside its diagonal blocks (M_Hp: ny x ny per
+    // step, N_Hc: nu x nu per free move, L_Hp: nu x nu per step) is exactly 0.0 in every member.  The stage-structured kernel
+    // takes such weights (ms_bodies.h); the condensed kernels go on reading Mfull / Ndense / Ldense.
+    bool sepM = false, sepN = false, sepL = false;
+    DBuf ms_Mblk;               // [B][Hp][ny][ny] the blocks of a stage-separable Mfull, for the stage kernel (Model::Mblk there)
     // SteadyKalmanFilter
     DBuf kf_K, kf_iym, kf_x, kf_y, kf_u, kf_d;
     KfParams kf{};
@@ -418,6 +425,35 @@ int mpcqp_set_dense_weights(mpcqp_handle h, const double* M_Hp, const double* N_
             *e.dst = nullptr;
         }
     }
+    // stage-separable?  (host pointers: looked at here, once.)  The blocks must be symmetric to the last bit: the stage kernel
+    // reads N_j / L_t as they are, one triangle here, the other there (ms_bodies.h), which is the same matrix only then.  A
+    // matrix with a block that is not keeps reason 1 and the condensed kernels, which take it as they always did.
+    auto separable = [&](const double* a, size_t n, int blk) {
+        if (!a) return false;
+        for (size_t b = 0; b < (size_t)d.B; ++b)
+            for (size_t j = 0; j < n; ++j)
+                for (size_t i = 0; i < n; ++i) {
+                    const double v = a[b * n * n + i + n * j];
+                    if (i / blk != j / blk ? v != 0.0 : v != a[b * n * n + j + n * i]) return false;
+                }
+        return true;
+    };
+    h->sepM = separable(M_Hp, (size_t)d.nY, d.ny);
+    h->sepN = separable(N_Hc, (size_t)d.nDU, d.nu);
+    h->sepL = separable(L_Hp, (size_t)d.nU, d.nu);
+    if (h->sepM) {      // the stage kernel's block path reads [Hp][ny][ny]
+        std::vector<double> blk((size_t)d.B * d.Hp * d.ny * d.ny);
+        const size_t n = (size_t)d.nY;
+        for (size_t b = 0; b < (size_t)d.B; ++b)
+            for (int t = 0; t < d.Hp; ++t)
+                for (int a2 = 0; a2 < d.ny; ++a2)
+                    for (int a = 0; a < d.ny; ++a)
+                        blk[((b * d.Hp + t) * d.ny + a2) * d.ny + a] = M_Hp[b * n * n + (size_t)(t * d.ny + a) + n * (size_t)(t * d.ny + a2)];
+        int rc = upload(h, h->ms_Mblk, blk.data(), blk.size() * sizeof(double));
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(h->stream));        // (blk leaves scope)
+    }
+    h->lam_valid = false;
     d.dense_w = (h->m.Mfull || h->m.Ldense) ? 1 : 0;     // (a dense N_Hc only changes H̃: any step kernel serves it)
     invalidate_stepc(h);
     { int rc = refresh_hessian(h, h->stream); if (rc) return rc; }
@@ -581,15 +617,15 @@ static bool uses_stage_kernel(mpcqp_handle h) {
     return h->transcription == MPCQP_MULTIPLE_SHOOTING || h->stage_only || h->stage_rows || !condensed_fits(h->d);
 }
 
-// 0 when the MultipleShooting kernel takes this handle; else the reason (bit mask): 1 dense weight matrices, 4 the stage
-// data does not fit the 160 KB of LDS, 8 flags of the condensed kernels only.  (2, custom linear constraints, is no longer
-// set: the stage kernel takes them, each row lives in one stage of its Riccati recursion -- ms_bodies.h.)
+// 0 when the MultipleShooting kernel takes this handle; else the reason (bit mask): 1 weight matrices that couple different
+// stages (a cost that is not block-tridiagonal: no Riccati recursion solves it) or output blocks beyond ny = 256, 4 the
+// stage data does not fit the 160 KB of LDS.  (2, custom linear constraints, and 8, MPCQP_FLAG_KEEP_QP / _WARM_DUAL, are no
+// longer set: the stage kernel takes them -- ms_bodies.h.  The values stay reserved.)
 static int ms_unsupported(mpcqp_handle h) {
     int why = 0;
-    if (h->m.Mfull || h->m.Ndense || h->m.Ldense) why |= 1;          // (a block-diagonal M_Hp, e.g. a terminal cost, is taken since round 5)
-    if (h->m.Mblk && h->d.ny > 4 * WAVE) why |= 1;                   // (the block-weight sweep of ms_bodies.h keeps a column in four registers per lane)
+    if ((h->m.Mfull && !h->sepM) || (h->m.Ndense && !h->sepN) || (h->m.Ldense && !h->sepL)) why |= 1;
+    if ((h->m.Mblk || h->m.Mfull) && h->d.ny > 4 * WAVE) why |= 1;   // (the block-weight sweep of ms_bodies.h keeps a column in four registers per lane)
     if (ms_lds_bytes(h->d, h->m) > 160 * 1024) why |= 4;
-    if (h->d.flags & (MPCQP_FLAG_KEEP_QP | MPCQP_FLAG_WARM_DUAL)) why |= 8;
     return why;
 }
 
@@ -597,6 +633,7 @@ int mpcqp_set_transcription(mpcqp_handle h, int32_t transcription) {
     if (!h) return MPCQP_ERR_NULL;
     if (transcription != MPCQP_SINGLE_SHOOTING && transcription != MPCQP_MULTIPLE_SHOOTING) return MPCQP_ERR_ARG;
     h->transcription = transcription;
+    h->lam_valid = false;       // (the handle may move between the condensed and the stage kernels: another row order)
     return MPCQP_OK;
 }
 
@@ -649,7 +686,14 @@ static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* l
         io.F_keep = (double*)h->keep_F.p;
     }
     if (d.flags & MPCQP_FLAG_WARM_DUAL) {
-        const size_t nl = (size_t)d.B * (size_t)(d.nrows() > 0 ? d.nrows() : 1) * sizeof(double);
+        // sized for the kernel that runs: the rows of the condensed kernels or of the stage carve; multipliers stored by the
+        // other kind, or for another number of rows, do not line up (a setter moved the handle between the kernels)
+        const bool stage = uses_stage_kernel(h);
+        const int rows = stage ? make_ms_carve(d, h->m).nrows : d.nrows();
+        if (stage != h->lam_stage || rows != h->lam_rows) h->lam_valid = false;
+        h->lam_stage = stage; h->lam_rows = rows;
+        const size_t nl = (size_t)d.B * (size_t)(rows > 0 ? rows : 1) * sizeof(double);
+        if (!h->lam.p || h->lam.bytes < nl) h->lam_valid = false;
         int rc = dev_alloc(h, h->lam, nl);
         if (rc) return rc;
         io.lam_out = (double*)h->lam.p;
@@ -691,8 +735,14 @@ static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* l
         //  against the condensed kernel once the gains of the Riccati recursion are refined (ms_bodies.h: factor):
         //  delta 1e-12 / 1e-10 / 1e-9: not OPTIMAL 0 / 3 / 5, worst dU difference 2.7e-6 / 1.4e-2 / 1 (error branch), 99.9 %
         //  quantile 2e-7 / 3e-8 / 2e-7; profiles/r4/ms_delta_sweep.txt)
+        // stage-separable weights of mpcqp_set_dense_weights: M_Hp on the block path (its blocks, extracted at the setter),
+        // N_Hc and L_Hp read block by block out of the dense matrices
+        Model mm = h->m;
+        if (mm.Mfull && h->sepM) mm.Mblk = (const double*)h->ms_Mblk.p;
+        if (mm.Ndense && h->sepN) ms.blocks |= MS_BLK_N;
+        if (mm.Ldense && h->sepL) ms.blocks |= MS_BLK_L;
         Dims dm = d;
-        HIPCHK(launch_ms_step(dm, h->m, io, ms, st));
+        HIPCHK(launch_ms_step(dm, mm, io, ms, st));
     } else {
         { int rc = ensure_hessian(h, st); if (rc) return rc; }      // (skipped while the problem did not fit the LDS: see hessian_valid)
         HIPCHK(launch_step(d, h->m, io, st));

@@ -41,6 +41,15 @@
 // G' (MsStep::Gt_apply), the slack border phi and the row loops (residuals, polish) through MsStep::wrow.  The custom-row
 // code is compiled only into the kernels of handles that have such rows (template flag HAS_W).
 //
+// Hermitian weight blocks.  A stage-separable N_Hc = blkdiag_j(N_j) or L_Hp = blkdiag_t(L_t) (mpcqp_set_dense_weights; nu x nu
+// blocks, MsIO::blocks) keeps the cost block-tridiagonal, like the ny x ny blocks of M_Hp (Mblk): with D~ the row weights,
+//     R_j = 2 N_j + diag(D~_dU)  (dense nu x nu)      enters  Lam = R_j + Bbar'P Bbar  and the Joseph term  K'(R_j K),
+//     the u part of Q_t = 2 L_t + diag(D~_U)          enters  P_t (add_Q) and the state rows of the adjoint pass,
+// and the cost gradient is 2 L_t (v_t - ru_t), 2 N_j du_j (Gt_apply).  The stage diagonals QV, RD then hold the row
+// weights alone (assemble()).  Lam was dense already, so the recursion keeps its form and its cost.  The blocks, the dual
+// warm start and the kept q~ / F are compiled only into the kernels of handles that use one of them (template flag
+// HAS_OPT, ms_has_options); inside those kernels each is a run-time branch, like Mblk.
+//
 // Written against the wave interface W of mpcqp_bodies.h (gfx950: DevWave; tests/emu: 64 host threads).
 #pragma once
 #include <math.h>
@@ -76,8 +85,12 @@ struct MsIO {
     double* defect;   // [B]           max |E_S Z + F_S| at the returned point, may be null
     double* scratch;  // [nslots][big] horizon-long data of the resident wavefronts (null: they live in LDS)
     int nslots;
+    uint32_t blocks;  // MS_BLK_N: Model::Ndense is blkdiag of Hc blocks nu x nu, the kernel reads them out of it (else Ndiag);
+                      // MS_BLK_L: Model::Ldense, Hp blocks nu x nu (else Ldiag).  (A stage-separable M_Hp arrives as Model::Mblk.)
+                      // (beside nslots: the struct, a kernel argument, keeps the size and the offsets it had without it)
     int* next;        // work counter of the persistent grid (HBM placement)
 };
+enum : uint32_t { MS_BLK_N = 1u, MS_BLK_L = 2u };
 
 // (the custom rows come after the slack row: a handle without them keeps the groups, and the code, it had before them)
 enum { MS_UMIN = 0, MS_UMAX, MS_DUMIN, MS_DUMAX, MS_YMIN, MS_YMAX, MS_XMIN, MS_XMAX, MS_EPS, MS_NGROUP,
@@ -198,8 +211,15 @@ MPCQP_HD inline MsCarve make_ms_carve(const Dims& d, const Model& m) {
 }
 
 // HAS_W: the handle has custom rows (d.nw > 0); false compiles the kernel of a handle without them, unchanged
-template <class W, bool HAS_W = false>
-struct MsStep {
+// HAS_OPT: the handle uses stage-separable N_Hc / L_Hp blocks, MPCQP_FLAG_KEEP_QP or MPCQP_FLAG_WARM_DUAL (ms_has_options);
+// false compiles the kernel of a handle without them
+// (MsIO::blocks reaches MsStep by value and only where HAS_OPT: an empty base otherwise, so that the object of a kernel
+//  without options keeps the layout it had.  A reference to the kernel argument MsIO kept as a member cost k_ms_step_g
+//  230 VGPR spills, with options or without.)
+template <bool HAS_OPT> struct MsBlockBits { MPCQP_HD explicit MsBlockBits(uint32_t) {} MPCQP_HD uint32_t bits() const { return 0u; } };
+template <> struct MsBlockBits<true> { const uint32_t blk; MPCQP_HD explicit MsBlockBits(uint32_t v) : blk(v) {} MPCQP_HD uint32_t bits() const { return blk; } };
+template <class W, bool HAS_W = false, bool HAS_OPT = false>
+struct MsStep : MsBlockBits<HAS_OPT> {
     W& w;
     double* bg;         // base of the horizon-long data: LDS behind the small block, or this wavefront's HBM scratch
     const Dims& d;
@@ -220,8 +240,21 @@ struct MsStep {
     // block-diagonal M_Hp (terminal costs, construct.jl:45-93; mpcqp_set_output_weight_blocks): [Hp][ny][ny] symmetric blocks
     // of this controller, or null (diagonal Mdiag)
     MPCQP_HD const double* Mblk_() const { return m.Mblk ? m.Mblk + (size_t)b * d.Hp * d.ny * d.ny : nullptr; }
-    MPCQP_HD MsStep(W& w_, const Dims& d_, const Model& m_, const StepIO& io_, int b_, double* sm_, double* big_)
-        : w(w_), bg(big_), d(d_), m(m_), io(io_), b(b_), sm(sm_), c(make_ms_carve<HAS_W>(d_, m_)), nx(d_.nxh), nu(d_.nu), ny(d_.ny), nd(d_.nd),
+    // stage-separable N_Hc / L_Hp (MsIO::blocks): this controller's dense column-major matrix, or null (diagonal Ndiag / Ldiag);
+    // entry (a, e) of block j of an n x n matrix with blocks of nu: nblk(n, j, a, e)
+    MPCQP_HD const double* Nblk_() const {
+        if constexpr (HAS_OPT) return (this->bits() & MS_BLK_N) ? m.Ndense + (size_t)b * d.nDU * d.nDU : nullptr;
+        else return nullptr;
+    }
+    MPCQP_HD const double* Lblk_() const {
+        if constexpr (HAS_OPT) return (this->bits() & MS_BLK_L) ? m.Ldense + (size_t)b * d.nU * d.nU : nullptr;
+        else return nullptr;
+    }
+    MPCQP_HD bool blkN() const { if constexpr (HAS_OPT) return this->bits() & MS_BLK_N; else return false; }
+    MPCQP_HD bool blkL() const { if constexpr (HAS_OPT) return this->bits() & MS_BLK_L; else return false; }
+    MPCQP_HD size_t nblk(int n, int j, int a, int e) const { return (size_t)(j * nu + a) + (size_t)n * (j * nu + e); }
+    MPCQP_HD MsStep(W& w_, const Dims& d_, const Model& m_, const StepIO& io_, uint32_t blk_, int b_, double* sm_, double* big_)
+        : MsBlockBits<HAS_OPT>(blk_), w(w_), bg(big_), d(d_), m(m_), io(io_), b(b_), sm(sm_), c(make_ms_carve<HAS_W>(d_, m_)), nx(d_.nxh), nu(d_.nu), ny(d_.ny), nd(d_.nd),
           ns(d_.nxh + d_.nu), Hp(d_.Hp), Hc(d_.Hc), nDU(d_.nDU), nY(d_.nY), nXt(d_.nxh * d_.Hp), nVt(d_.nu * d_.Hp),
           npk((d_.nxh + d_.nu) * (d_.nxh + d_.nu + 1) / 2) {
         jlt = reinterpret_cast<int*>(sm + c.jl);
@@ -539,7 +572,14 @@ struct MsStep {
         }
         for (int i = w.lane; i < nVt; i += WAVE) {
             double acc = rowv(MS_UMAX, i) - rowv(MS_UMIN, i);
-            if (with_cost) acc += 2.0 * m.Ldiag[(size_t)b * d.nU + i] * (bg[c.V + i] - bg[c.ru + i]);
+            if (with_cost) {
+                if (const double* Lb = Lblk_()) {            // 2 L_t (v_t - ru_t)
+                    const int t = i / nu, cc = i - t * nu;
+                    for (int e = 0; e < nu; ++e) acc += 2.0 * Lb[nblk(d.nU, t, cc, e)] * (bg[c.V + t * nu + e] - bg[c.ru + t * nu + e]);
+                } else {
+                    acc += 2.0 * m.Ldiag[(size_t)b * d.nU + i] * (bg[c.V + i] - bg[c.ru + i]);
+                }
+            }
             if constexpr (HAS_W) {
                 const int t = i / nu, cc = i - t * nu;
                 for (int ii = 0; ii < d.nw; ++ii) acc += sm[c.Wu + ii * nu + cc] * rww(t + 1, ii);
@@ -548,7 +588,14 @@ struct MsStep {
         }
         for (int i = w.lane; i < nDU; i += WAVE) {
             double acc = rowv(MS_DUMAX, i) - rowv(MS_DUMIN, i);
-            if (with_cost) acc += 2.0 * m.Ndiag[(size_t)b * nDU + i] * bg[c.DU + i];
+            if (with_cost) {
+                if (const double* Nb = Nblk_()) {            // 2 N_j du_j
+                    const int jj = i / nu, cc = i - jj * nu;
+                    for (int e = 0; e < nu; ++e) acc += 2.0 * Nb[nblk(nDU, jj, cc, e)] * bg[c.DU + jj * nu + e];
+                } else {
+                    acc += 2.0 * m.Ndiag[(size_t)b * nDU + i] * bg[c.DU + i];
+                }
+            }
             if constexpr (HAS_W) {
                 const int jj = i / nu, cc = i - jj * nu, ts = jlt[jj];
                 for (int ii = 0; ii < d.nw; ++ii) acc += sm[c.Wu + ii * nu + cc] * rww(ts, ii);
@@ -661,6 +708,9 @@ struct MsStep {
             } else if (i == j) {
                 acc = bg[c.QV + t * nu + (i - nx)];
             }
+            if constexpr (HAS_OPT)            // + 2 L_t (block weights) on the u part
+                if (const double* Lb = Lblk_())
+                    if (i >= nx && j >= nx) acc += 2.0 * Lb[nblk(d.nU, t, i - nx, j - nx)];
             if constexpr (HAS_W) {
                 // custom rows of step t + 1 without a free move (and of step Hp): g_xi' D~ g_xi.  (Those with a free move
                 // enter P through the Joseph form of factor(), with the gain.)
@@ -756,6 +806,7 @@ struct MsStep {
                     const int a = idx / nu, e = idx - a * nu;
                     // (symmetrised: the two triangles of Bbar'P Bbar differ by rounding)
                     double v = 0.5 * (S[a * ns + nx + e] + S[e * ns + nx + a]) + (a == e ? bg[c.RD + j * nu + a] : 0.0);
+                    if (const double* Nb = Nblk_()) v += Nb[nblk(nDU, j, a, e)] + Nb[nblk(nDU, j, e, a)];      // R_j = 2 N_j + diag(RD_j)
                     if constexpr (HAS_W)               // + Wu' D~ Wu of the custom rows of step t (dense nu x nu)
                         for (int ii = 0; ii < d.nw; ++ii) v += sm[c.Wu + ii * nu + a] * sD[ii] * sm[c.Wu + ii * nu + e];
                     Li[idx] = v;
@@ -839,22 +890,40 @@ struct MsStep {
                        [&](int i, int jj, double v) { T[i * ns + jj] = v; });
                     w.sync_lds();
                     // P_t = Acl' T + K' R K: the inner index runs over the ns rows of Acl / T, then over the nu rows of K
+                    // R_j = diag(RD_j) of the stage into LDS, read per k; with the options compiled in R_j K, R_j = diag(RD_j)
+                    // [+ 2 N_j, block weights], into the stage inputs c.stg (they belong to the sweeps: free here)
                     const double* Rd = bg + c.RD + j * nu;
-                    for (int e = w.lane; e < nu; e += WAVE) sm[c.wv + e] = Rd[e];         // (R of the stage into LDS: read per k)
+                    double* RK = sm + c.stg;
+                    if constexpr (HAS_OPT) {
+                        const double* Nb = Nblk_();
+                        for (int idx = w.lane; idx < nu * ns; idx += WAVE) {
+                            const int e = idx / ns, col = idx - e * ns;
+                            double acc = K[idx] * Rd[e];
+                            if (Nb)
+                                for (int e2 = 0; e2 < nu; ++e2) acc += (Nb[nblk(nDU, j, e, e2)] + Nb[nblk(nDU, j, e2, e)]) * K[e2 * ns + col];
+                            RK[idx] = acc;
+                        }
+                    } else {
+                        for (int e = w.lane; e < nu; e += WAVE) sm[c.wv + e] = Rd[e];
+                    }
                     w.sync_lds();
                     const double* Rl = sm + c.wv;
+                    auto rk = [&](int e, int i) {          // (R_j K)(e, i)
+                        if constexpr (HAS_OPT) return RK[e * ns + i];
+                        else return K[e * ns + i] * Rl[e];
+                    };
                     if constexpr (HAS_W) {
                         // ... + sum_i D~_i h_i' h_i: the custom rows of step t, one more term of the same sum (inner index
                         // ns + nu .. ns + nu + nw)
                         const double* Hw = sm + c.Hw;
                         const int n2 = ns + nu;
                         mm(ns, ns, n2 + d.nw, true,
-                           [&](int i, int k) { return k < ns ? S[k * ns + i] : k < n2 ? K[(k - ns) * ns + i] * Rl[k - ns] : Hw[(k - n2) * ns + i] * sD[k - n2]; },
+                           [&](int i, int k) { return k < ns ? S[k * ns + i] : k < n2 ? rk(k - ns, i) : Hw[(k - n2) * ns + i] * sD[k - n2]; },
                            [&](int k, int jj) { return k < ns ? T[k * ns + jj] : k < n2 ? K[(k - ns) * ns + jj] : Hw[(k - n2) * ns + jj]; },
                            [&](int i, int jj, double v) { Pn[i * ns + jj] = v; Pn[jj * ns + i] = v; });
                     } else {
                         mm(ns, ns, ns + nu, true,
-                           [&](int i, int k) { return k < ns ? S[k * ns + i] : K[(k - ns) * ns + i] * Rl[k - ns]; },
+                           [&](int i, int k) { return k < ns ? S[k * ns + i] : rk(k - ns, i); },
                            [&](int k, int jj) { return k < ns ? T[k * ns + jj] : K[(k - ns) * ns + jj]; },
                            [&](int i, int jj, double v) { Pn[i * ns + jj] = v; Pn[jj * ns + i] = v; });
                     }
@@ -1014,6 +1083,9 @@ struct MsStep {
             copy(sv0, oX + t * nx, nx); copy(sv0 + nx, oV + t * nu, nu);               // dxi_{t+1}
             copy(sv1, gX + t * nx, nx); copy(sv1 + nx, gV + t * nu, nu);               // g_{t+1}
             copy(sv2, bg + c.QV + t * nu, nu); copy(sv2 + nu, bg + c.QY + t * ny, ny);  // stage Hessian diagonals
+            const double* Lb = Lblk_();
+            if (Lb)                                                                    // L_t (block weights) where the gains were
+                for (int idx = w.lane; idx < nu * nu; idx += WAVE) sLi[idx] = Lb[nblk(d.nU, t, idx / nu, idx % nu)];
             w.sync_lds();
             if constexpr (HAS_W) {
                 // custom rows of step t + 1: g_xi' D~ (g_xi dxi_{t+1} + Wu du_{t+1}), the cross term of Phi included
@@ -1070,6 +1142,8 @@ struct MsStep {
                 } else {
                     const int cc = i - nx;
                     acc = sv1[i] + sv2[cc] * sv0[i];
+                    if (Lb)
+                        for (int e = 0; e < nu; ++e) acc += 2.0 * sLi[cc * nu + e] * sv0[nx + e];
                     if constexpr (HAS_W) acc += sm[c.wsc + d.nw + i];
                     for (int k = 0; k < nx; ++k) acc += Bu[k + nx * cc] * na[k];
                     acc += na[i];
@@ -1268,7 +1342,7 @@ struct MsStep {
             bg[c.CD + r] = cd;
         }
         for (int r = w.lane; r < nVt; r += WAVE) {
-            bg[c.QV + r] = 2.0 * m.Ldiag[(size_t)b * d.nU + r] + dt_(MS_UMIN, r) + dt_(MS_UMAX, r);
+            bg[c.QV + r] = (blkL() ? 0.0 : 2.0 * m.Ldiag[(size_t)b * d.nU + r]) + dt_(MS_UMIN, r) + dt_(MS_UMAX, r);   // (block weights: add_Q, sweep)
             double fv = cs_(MS_UMIN, r) * dt_(MS_UMIN, r) - cs_(MS_UMAX, r) * dt_(MS_UMAX, r);
             if constexpr (HAS_W) {
                 const int t = r / nu, cc = r - t * nu;
@@ -1277,7 +1351,7 @@ struct MsStep {
             bg[c.fV + r] = fv;
         }
         for (int r = w.lane; r < nDU; r += WAVE) {
-            bg[c.RD + r] = 2.0 * m.Ndiag[(size_t)b * nDU + r] + dt_(MS_DUMIN, r) + dt_(MS_DUMAX, r);
+            bg[c.RD + r] = (blkN() ? 0.0 : 2.0 * m.Ndiag[(size_t)b * nDU + r]) + dt_(MS_DUMIN, r) + dt_(MS_DUMAX, r);   // (block weights: factor)
             double fd = cs_(MS_DUMIN, r) * dt_(MS_DUMIN, r) - cs_(MS_DUMAX, r) * dt_(MS_DUMAX, r);
             if constexpr (HAS_W) {
                 const int jj = r / nu, cc = r - jj * nu, ts = jlt[jj];
@@ -1433,8 +1507,62 @@ struct MsStep {
 
     static constexpr int ST_OPTIMAL = 0, ST_ITERATION_LIMIT = 1, ST_ERROR = 2;
 
+    // MPCQP_FLAG_KEEP_QP: q~ and F of the CONDENSED problem (Y^0 = E dU + F, J = 1/2 Z~'H~ Z~ + q~'Z~; what the condensed
+    // kernels keep, whatever the handle's transcription) without forming E.  F is the free response: the model rolled out
+    // with dU = 0, C^ x^0(k+t+1) + D^d d^0(k+t+1).  q~ is the gradient of the objective with respect to dU at dU = 0,
+    //     q~ = 2 (M E)'(F - R^y) + 2 (L Pu)'(Tu u0(k-1) - R^u):
+    // the stage gradients of the cost at the free response (Gt_apply with zero row weights) swept once through the adjoint
+    // of the model, lam_t = g_t + Abar' lam_{t+1}, q~_j = Bbar' lam at the first step of block j.  Its slack entry is 0.
+    // Two O(Hp ns^2) sweeps; runs before the iterate is placed, on the iterate's arrays.
+    MPCQP_HD void keep_qp() {
+        double* X = bg + c.X; double* V = bg + c.V; double* DU = bg + c.DU;
+        for (int k = w.lane; k < nDU; k += WAVE) DU[k] = 0.0;
+        w.sync();
+        rollout(DU, X, V);
+        C_apply(X, bg + c.CX);
+        for (int r = w.lane; r < nY; r += WAVE) {
+            const int t = r / ny, a = r - t * ny;
+            double acc = bg[c.CX + r];
+            for (int e = 0; e < nd; ++e) acc += m.Dd[(size_t)b * ny * nd + a + ny * e] * io.Dhat0[(size_t)b * d.nD + t * nd + e];
+            io.F_keep[(size_t)b * nY + r] = acc;
+        }
+        Gt_apply([&](int) { return 0.0; }, bg + c.gX, bg + c.gV, bg + c.gDU, true);
+        double* na = sm + c.pl;        // lam_{t+1} (zero beyond the horizon)
+        double* nb = na + ns;
+        double* q = io.q_keep + (size_t)b * d.nZ;
+        for (int i = w.lane; i < ns; i += WAVE) na[i] = 0.0;
+        w.sync_lds();
+        for (int t = Hp - 1; t >= 0; --t) {
+            for (int i = w.lane; i < ns; i += WAVE) {
+                double acc;
+                if (i < nx) {
+                    acc = bg[c.gX + t * nx + i];
+                    for (int k = 0; k < nx; ++k) acc += A[k + nx * i] * na[k];
+                } else {
+                    const int cc = i - nx;
+                    acc = bg[c.gV + t * nu + cc] + na[i];
+                    for (int k = 0; k < nx; ++k) acc += Bu[k + nx * cc] * na[k];
+                }
+                nb[i] = acc;
+            }
+            w.sync_lds();
+            { double* t_ = na; na = nb; nb = t_; }
+            const int j = ctrl[t];
+            if (j >= 0)                // q~_j = Bbar' lam_t
+                for (int cc = w.lane; cc < nu; cc += WAVE) {
+                    double acc = na[nx + cc];
+                    for (int k = 0; k < nx; ++k) acc += Bu[k + nx * cc] * na[k];
+                    q[j * nu + cc] = acc;
+                }
+        }
+        if (d.neps && w.lane == 0) q[d.nZ - 1] = 0.0;
+        w.sync();
+    }
+
     MPCQP_HD int run(int& iters_out, double& defect_out) {
         double* X = bg + c.X; double* V = bg + c.V; double* DU = bg + c.DU;
+        if constexpr (HAS_OPT)
+            if ((d.flags & 4u) && io.q_keep) keep_qp();
         // warm start: dU shifted (transcription.jl:1001-1004), X^0 rolled out from it, multipliers of the model 0
         const double* Zg = io.Z + (size_t)b * d.nZ;
         const bool cold = d.flags & 2u;
@@ -1447,17 +1575,32 @@ struct MsStep {
         const double eps_ws = eps;
         double mu = 0.0, rpn = 0.0, rdn = 0.0, ndd = 1.0, cn = 0.0, xs = 1.0;
         int status = ST_ITERATION_LIMIT, it = 0;
-        // starting point of the rows: s = max(h - G z, 1), lam = 10 / s   (Step::run)
+        // starting point of the rows: s = max(h - G z, 1), lam = 10 / s   (Step::run); with MPCQP_FLAG_WARM_DUAL and the row
+        // multipliers of the previous period at hand, on the central path of mu0 = 1e-3 around them (Step::run's rule:
+        // s = max(h - G z, 1e-3), lam = max(lam_prev, mu0 / s), s = max(s, mu0 / lam)).  The multipliers nu of the model
+        // start at 0 either way: the first Newton system returns them in full.
+        const double* lam_prev = nullptr;
+        if constexpr (HAS_OPT)
+            if ((d.flags & 8u) && !cold && io.lam_prev) lam_prev = io.lam_prev + (size_t)b * c.nrows;
         C_apply(X, bg + c.CX);
         for_rows([&](int g, int k, int r) {
             if (!fin(r)) return;
             const double gz = prim(g, k, X, V, DU, bg + c.CX, eps) - (g == MS_EPS ? 0.0 : rcs[r] * eps);
-            rs[r] = fmax(rh[r] - gz, 1.0);
-            rl[r] = 10.0 / rs[r];
+            if (lam_prev) {
+                const double mu0 = 1e-3;
+                double si = fmax(rh[r] - gz, 1e-3);
+                const double li = fmax(lam_prev[r], mu0 / si);
+                rs[r] = fmax(si, mu0 / li);
+                rl[r] = li;
+            } else {
+                rs[r] = fmax(rh[r] - gz, 1.0);
+                rl[r] = 10.0 / rs[r];
+            }
         });
         w.sync();
         double step_c = 1e300, zabs_c = 0.0, rd_prev = 1e300, alpha_prev = 0.0, rd_best = 1e300;
         int rd_flat = 0, npolish = 0;
+        bool polished = false;          // the returned point is an accepted polish: its multipliers are in rpp
         double polmu_next = 1e-6;
         const int max_iter = mact ? d.max_iter : 1;
         while (true) {
@@ -1490,7 +1633,7 @@ struct MsStep {
                 const long long t6_ = clk();
                 const bool pok_ = polish(xs, npolish);
                 prof_[6] += (double)(clk() - t6_);
-                if (pok_) { status = ST_OPTIMAL; break; }
+                if (pok_) { status = ST_OPTIMAL; polished = true; break; }
                 residuals(mu, rpn, rdn, ndd, cn, xs);        // (the row arrays served the polish)
             }
             // D~ of the rows -> stage diagonals, border column phi, Phi_ee
@@ -1590,6 +1733,11 @@ struct MsStep {
             w.sync();
             rollout(DU, X, V);
         }
+        if (HAS_OPT && (d.flags & 8u) && io.lam_out) {           // row multipliers for the next period's start: this kernel's row order (MsCarve::rowoff), c.nrows per controller
+            double* lo = io.lam_out + (size_t)b * c.nrows;
+            const bool good = status != ST_ERROR;
+            for_rows([&](int, int, int r) { lo[r] = (good && fin(r)) ? (polished ? fmax(rpp[r], 0.0) : rl[r]) : 0.0; });
+        }
         iters_out = it + npolish;      // factorisations: interior-point iterations + polish attempts
         defect_out = cn;
         if (io.audit && w.lane == 0) {
@@ -1604,14 +1752,17 @@ struct MsStep {
 // in LDS behind the small block.  (A template parameter, not a run-time choice: a pointer that may be LDS or HBM is a
 // generic pointer, every access a flat_load / flat_store -- which count on BOTH memory counters, so that not even the
 // LDS-only fences of the stage loops could run ahead of the stores.)
-// HAS_W: instantiated for handles with custom rows (d.nw > 0); the kernels choose at launch.
-template <bool IN_HBM, bool HAS_W, class W>
+// HAS_W: instantiated for handles with custom rows (d.nw > 0), HAS_OPT: for handles with ms_has_options(); the kernels
+// choose at launch.
+// (a dense N_Hc / L_Hp on a handle that reaches this kernel is stage-separable: the host refuses the others)
+MPCQP_HD inline bool ms_has_options(const Dims& d, const Model& m) { return m.Ndense || m.Ldense || (d.flags & (4u | 8u)) != 0; }
+template <bool IN_HBM, bool HAS_W, bool HAS_OPT, class W>
 MPCQP_HD void ms_step_body_t(W& w, const Dims& d, const Model& m, const StepIO& io, const MsIO& ms, int b, double* sm, double* scratch) {
     double* big;
     if constexpr (IN_HBM) big = scratch;
     else big = sm + make_ms_carve<HAS_W>(d, m).small;
-    MsStep<W, HAS_W> st(w, d, m, io, b, sm, big);
-    const long long tp0_ = MsStep<W, HAS_W>::clk();
+    MsStep<W, HAS_W, HAS_OPT> st(w, d, m, io, HAS_OPT ? ms.blocks : 0u, b, sm, big);
+    const long long tp0_ = MsStep<W, HAS_W, HAS_OPT>::clk();
     (void)tp0_;
     st.load();
     st.build_rows();
@@ -1648,7 +1799,7 @@ MPCQP_HD void ms_step_body_t(W& w, const Dims& d, const Model& m, const StepIO& 
     if (ms.Xhat)
         for (int i = w.lane; i < d.nxh * d.Hp; i += WAVE) ms.Xhat[(size_t)b * d.nxh * d.Hp + i] = st.bg[st.c.X + i];
 #if defined(MPCQP_MS_PROFILE)
-    if (ms.Xhat && w.lane == 0) { st.prof_[7] = (double)(MsStep<W, HAS_W>::clk() - tp0_); for (int i = 0; i < 8; ++i) ms.Xhat[(size_t)b * d.nxh * d.Hp + i] = st.prof_[i]; }
+    if (ms.Xhat && w.lane == 0) { st.prof_[7] = (double)(MsStep<W, HAS_W, HAS_OPT>::clk() - tp0_); for (int i = 0; i < 8; ++i) ms.Xhat[(size_t)b * d.nxh * d.Hp + i] = st.prof_[i]; }
 #endif
     if (w.lane == 0) {
         io.status[b] = status;
@@ -1660,8 +1811,14 @@ MPCQP_HD void ms_step_body_t(W& w, const Dims& d, const Model& m, const StepIO& 
 // run-time choice between the two instantiations (the CPU emulator; the gfx950 kernels instantiate one each)
 template <bool IN_HBM, class W>
 MPCQP_HD void ms_step_body(W& w, const Dims& d, const Model& m, const StepIO& io, const MsIO& ms, int b, double* sm, double* scratch) {
-    if (d.nw > 0) ms_step_body_t<IN_HBM, true>(w, d, m, io, ms, b, sm, scratch);
-    else ms_step_body_t<IN_HBM, false>(w, d, m, io, ms, b, sm, scratch);
+    const bool opt = ms_has_options(d, m);
+    if (d.nw > 0) {
+        if (opt) ms_step_body_t<IN_HBM, true, true>(w, d, m, io, ms, b, sm, scratch);
+        else ms_step_body_t<IN_HBM, true, false>(w, d, m, io, ms, b, sm, scratch);
+    } else {
+        if (opt) ms_step_body_t<IN_HBM, false, true>(w, d, m, io, ms, b, sm, scratch);
+        else ms_step_body_t<IN_HBM, false, false>(w, d, m, io, ms, b, sm, scratch);
+    }
 }
 
 }  // namespace mpcqp

@@ -16,15 +16,17 @@
 
 namespace mpcqp {
 
-// (custom linear constraints: the _w kernels, instantiated with the rows; a handle without them runs the kernels it ran before)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void k_ms_step(Dims d, Model m, StepIO io, MsIO ms) {
-    DevWave w{(int)threadIdx.x};
-    ms_step_body_t<false, false>(w, d, m, io, ms, (int)blockIdx.x, mpcqp_smem, (double*)nullptr);
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void k_ms_step_w(Dims d, Model m, StepIO io, MsIO ms) {
-    DevWave w{(int)threadIdx.x};
-    ms_step_body_t<false, true>(w, d, m, io, ms, (int)blockIdx.x, mpcqp_smem, (double*)nullptr);
-}
+// (custom linear constraints: the _w kernels, instantiated with the rows; stage-separable N_Hc / L_Hp blocks, MPCQP_FLAG_KEEP_QP
+//  and MPCQP_FLAG_WARM_DUAL: the _o kernels (ms_has_options).  A handle without them runs the kernels it ran before.)
+#define MPCQP_MS_KERNEL_LDS(name, HAS_W, HAS_OPT)                                                                              \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void name(Dims d, Model m, StepIO io, MsIO ms) { \
+        DevWave w{(int)threadIdx.x};                                                                                           \
+        ms_step_body_t<false, HAS_W, HAS_OPT>(w, d, m, io, ms, (int)blockIdx.x, mpcqp_smem, (double*)nullptr);                \
+    }
+MPCQP_MS_KERNEL_LDS(k_ms_step, false, false)
+MPCQP_MS_KERNEL_LDS(k_ms_step_w, true, false)
+MPCQP_MS_KERNEL_LDS(k_ms_step_o, false, true)
+MPCQP_MS_KERNEL_LDS(k_ms_step_wo, true, true)
 
 #ifndef MPCQP_MS_WAVES
 #define MPCQP_MS_WAVES 2
@@ -34,29 +36,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8))) void
 // batch -- with the static assignment b = blockIdx + k gridDim one such controller set the time of the whole launch
 // (measured: 131 ms for 2048 C3 controllers of which one is at the limit, 25 ms of work per wavefront otherwise)
 // (two wavefronts per SIMD: without the attribute the compiler takes 372 registers and leaves one)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MPCQP_MS_WAVES, 8))) void k_ms_step_g(Dims d, Model m, StepIO io, MsIO ms, size_t big) {
-    DevWave w{(int)threadIdx.x};
-    double* scratch = ms.scratch + (size_t)blockIdx.x * big;
-    for (;;) {
-        int b = 0;
-        if (threadIdx.x == 0) b = atomicAdd(ms.next, 1);
-        b = __builtin_amdgcn_readfirstlane(b);
-        if (b >= d.B) break;
-        ms_step_body_t<true, false>(w, d, m, io, ms, b, mpcqp_smem, scratch);
-        w.sync();
+#define MPCQP_MS_KERNEL_HBM(name, HAS_W, HAS_OPT)                                                                                \
+    __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MPCQP_MS_WAVES, 8))) void name(Dims d, Model m, StepIO io, \
+                                                                                                   MsIO ms, size_t big) {        \
+        DevWave w{(int)threadIdx.x};                                                                                             \
+        double* scratch = ms.scratch + (size_t)blockIdx.x * big;                                                                 \
+        for (;;) {                                                                                                               \
+            int b = 0;                                                                                                           \
+            if (threadIdx.x == 0) b = atomicAdd(ms.next, 1);                                                                     \
+            b = __builtin_amdgcn_readfirstlane(b);                                                                               \
+            if (b >= d.B) break;                                                                                                 \
+            ms_step_body_t<true, HAS_W, HAS_OPT>(w, d, m, io, ms, b, mpcqp_smem, scratch);                                      \
+            w.sync();                                                                                                            \
+        }                                                                                                                        \
     }
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MPCQP_MS_WAVES, 8))) void k_ms_step_gw(Dims d, Model m, StepIO io, MsIO ms, size_t big) {
-    DevWave w{(int)threadIdx.x};
-    double* scratch = ms.scratch + (size_t)blockIdx.x * big;
-    for (;;) {
-        int b = 0;
-        if (threadIdx.x == 0) b = atomicAdd(ms.next, 1);
-        b = __builtin_amdgcn_readfirstlane(b);
-        if (b >= d.B) break;
-        ms_step_body_t<true, true>(w, d, m, io, ms, b, mpcqp_smem, scratch);
-        w.sync();
-    }
+MPCQP_MS_KERNEL_HBM(k_ms_step_g, false, false)
+MPCQP_MS_KERNEL_HBM(k_ms_step_gw, true, false)
+MPCQP_MS_KERNEL_HBM(k_ms_step_go, false, true)
+MPCQP_MS_KERNEL_HBM(k_ms_step_gwo, true, true)
+
+// the kernel of a handle: [HBM placement][custom rows][options]
+static const void* ms_kernel(bool hbm, bool hw, bool opt) {
+    static const void* const k[2][2][2] = {{{(const void*)k_ms_step, (const void*)k_ms_step_o}, {(const void*)k_ms_step_w, (const void*)k_ms_step_wo}},
+                                           {{(const void*)k_ms_step_g, (const void*)k_ms_step_go}, {(const void*)k_ms_step_gw, (const void*)k_ms_step_gwo}}};
+    return k[hbm][hw][opt];
 }
 
 size_t ms_lds_bytes(const Dims& d, const Model& m) { return (size_t)make_ms_carve(d, m).total * sizeof(double); }
@@ -72,7 +75,7 @@ size_t ms_scratch_bytes(const Dims& d, const Model& m, int* nslots) {
     // so that a step does no runtime queries.
     int dev = 0, cus = 256, per_cu = 0;
     (void)hipGetDevice(&dev);
-    const void* kern = d.nw > 0 ? (const void*)k_ms_step_gw : (const void*)k_ms_step_g;
+    const void* kern = ms_kernel(true, d.nw > 0, ms_has_options(d, m));
     {
         static std::mutex mu;
         static std::map<std::pair<std::pair<int, size_t>, const void*>, std::pair<int, int>> seen;
@@ -99,22 +102,21 @@ size_t ms_scratch_bytes(const Dims& d, const Model& m, int* nslots) {
 hipError_t launch_ms_step(const Dims& d, const Model& m, const StepIO& io, const MsIO& ms, hipStream_t st) {
     const MsCarve c = make_ms_carve(d, m);
     const size_t lds = (size_t)c.total * sizeof(double);
-    const bool hw = d.nw > 0;
+    const void* kern = ms_kernel(!c.big_in_lds, d.nw > 0, ms_has_options(d, m));
+    hipError_t e = ensure_lds(kern, lds);
+    if (e != hipSuccess) return e;
     if (c.big_in_lds) {
-        hipError_t e = ensure_lds(hw ? (const void*)k_ms_step_w : (const void*)k_ms_step, lds);
-        if (e != hipSuccess) return e;
-        if (hw) hipLaunchKernelGGL(k_ms_step_w, dim3(d.B), dim3(WAVE), lds, st, d, m, io, ms);
-        else hipLaunchKernelGGL(k_ms_step, dim3(d.B), dim3(WAVE), lds, st, d, m, io, ms);
+        void* args[] = {(void*)&d, (void*)&m, (void*)&io, (void*)&ms};
+        e = hipLaunchKernel(kern, dim3(d.B), dim3(WAVE), args, lds, st);
     } else {
-        if (!ms.scratch || ms.nslots < 1) return hipErrorInvalidValue;
-        hipError_t e = ensure_lds(hw ? (const void*)k_ms_step_gw : (const void*)k_ms_step_g, lds);
-        if (e != hipSuccess) return e;
-        if (!ms.next) return hipErrorInvalidValue;
+        if (!ms.scratch || ms.nslots < 1 || !ms.next) return hipErrorInvalidValue;
         e = hipMemsetAsync(ms.next, 0, sizeof(int), st);
         if (e != hipSuccess) return e;
-        if (hw) hipLaunchKernelGGL(k_ms_step_gw, dim3(ms.nslots), dim3(WAVE), lds, st, d, m, io, ms, (size_t)c.big);
-        else hipLaunchKernelGGL(k_ms_step_g, dim3(ms.nslots), dim3(WAVE), lds, st, d, m, io, ms, (size_t)c.big);
+        size_t big = (size_t)c.big;
+        void* args[] = {(void*)&d, (void*)&m, (void*)&io, (void*)&ms, (void*)&big};
+        e = hipLaunchKernel(kern, dim3(ms.nslots), dim3(WAVE), args, lds, st);
     }
+    if (e != hipSuccess) return e;
     return hipGetLastError();
 }
 
