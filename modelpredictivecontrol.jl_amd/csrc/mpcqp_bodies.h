@@ -658,7 +658,21 @@ struct Qp {
         E_apply_share(v, out);
         if constexpr (W::NTEAM > 1) w.join();
     }
-    MPCQP_HD void E_apply_share(const double* v, double* out) {
+    MPCQP_HD void E_apply_share(const double* v, double* out) { E_apply_share_<false>(v, out, nullptr); }
+    // the two forms below that give lane l the rows r = l + 64 q are the ones a one-wavefront kernel of default move blocking
+    // takes (a compile-time choice); EVQ: row slots per lane, 0 where another form runs
+    MPCQP_HD static constexpr int ev_slots() {
+        if constexpr (DM::is_static) {
+            constexpr bool c3 = DM::nu == 4 && DM::nY <= 2 * WAVE && DM::Hc <= MPCQP_EAPPLY44_HCMAX;
+            constexpr int nr = (DM::nY + WAVE - 1) / WAVE;
+            return (W::NTEAM == 1 && DM::default_nb && (c3 || DM::zpad > 0) && nr <= 4) ? nr : 0;
+        } else {
+            return 0;
+        }
+    }
+    // REG (ev_slots() > 0): the lane's results also go to mine_q[q] (row r = lane + 64 q; rows >= nY: unspecified)
+    template <bool REG>
+    MPCQP_HD void E_apply_share_(const double* v, double* out, double* mine_q) {
         const int ny = d.ny, nu = d.nu;
         if constexpr (DM::is_static) {
             if (W::NTEAM == 1 && DM::nu == 4 && DM::nY <= 2 * WAVE && DM::Hc <= MPCQP_EAPPLY44_HCMAX && d.default_nb) {
@@ -685,6 +699,10 @@ struct Qp {
                 }
                 if (ok0) out[r0] = x0 + x1;
                 if (ok1) out[r1] = y0 + y1;
+                if constexpr (REG) {
+                    mine_q[0] = x0 + x1;
+                    if constexpr (DM::nY > WAVE) mine_q[1] = y0 + y1;
+                }
                 return;
             }
         }
@@ -721,6 +739,7 @@ struct Qp {
                 for (int q_ = 0; q_ < NR; ++q_) {
                     const int r = w.lane + WAVE * q_;
                     if (mine(q_) && r < DM::nY) out[r] = acc[q_][0] + acc[q_][1];
+                    if constexpr (REG) mine_q[q_] = acc[q_][0] + acc[q_][1];
                 }
                 return;
             }
@@ -748,6 +767,13 @@ struct Qp {
         if constexpr (W::NTEAM > 1) w.join();
     }
     MPCQP_HD void Et_apply_share(const double* wv, double* out, double scale, int t_hi) {
+        double none = 0.0;
+        Et_apply_share_<false>(wv, out, scale, t_hi, none);
+    }
+    // REG (one variable per lane, one wavefront per problem): the lane's entry k = lane is the register `mine_k` instead of
+    // out[k] (`out` is not touched) -- the same `+= scale * sum`, without the store and the load of a value the lane holds
+    template <bool REG>
+    MPCQP_HD void Et_apply_share_(const double* wv, double* out, double scale, int t_hi, double& mine_k) {
         const int ny = d.ny, nu = d.nu;
         if (t_hi < 0) t_hi = d.Hp;          // only the steps t < t_hi contribute
         if constexpr (DM::is_static) {
@@ -791,7 +817,8 @@ struct Qp {
                 }
                 p0 = w.quad_sum(p0); p1 = w.quad_sum(p1); p2 = w.quad_sum(p2); p3 = w.quad_sum(p3);
                 const double mine = a == 0 ? p0 : a == 1 ? p1 : a == 2 ? p2 : p3;
-                if (w.lane < DM::nDU) out[k] += scale * mine;
+                if constexpr (REG) { if (w.lane < DM::nDU) mine_k += scale * mine; }
+                else { if (w.lane < DM::nDU) out[k] += scale * mine; }
                 return;
             }
         }
@@ -828,7 +855,8 @@ struct Qp {
                 MPCQP_UNROLL
                 for (int q_ = 0; q_ < NQ; ++q_) {
                     const int k = w.lane + WAVE * q_;
-                    if (mine(q_) && k < DM::nDU) out[k] += scale * (acc[q_][0] + acc[q_][1]);
+                    if constexpr (REG) { if (k < DM::nDU) mine_k += scale * (acc[q_][0] + acc[q_][1]); }
+                    else { if (mine(q_) && k < DM::nDU) out[k] += scale * (acc[q_][0] + acc[q_][1]); }
                 }
                 return;
             }
@@ -851,7 +879,8 @@ struct Qp {
                 acc0 += ok ? p0 : 0.0;
                 acc1 += ok ? p1 : 0.0;
             }
-            out[k] += scale * (acc0 + acc1);
+            if constexpr (REG) mine_k += scale * (acc0 + acc1);
+            else out[k] += scale * (acc0 + acc1);
         }
     }
 
@@ -2175,21 +2204,45 @@ struct Step {
     }
 
     // ---- primitives of G v: ucum (held cumulative sum), tY = E v, tX = ex̂ v ------------------
-    MPCQP_HD void primitives(const double* v) {
+    // what a lane computes in primitives() for the rows it owns itself (lane_regs(): row k of a group is on lane k mod 64)
+    static constexpr int EVQ = Qp<W, DM>::ev_slots();
+    struct Prims {
+        double ucum = 0.0;                      // (Pu v)[lane]
+        double ey[EVQ > 0 ? EVQ : 1] = {0.0};   // (E v)[lane + 64 q]
+        MPCQP_HD double ey_at(int k) const {
+            double x = ey[0];
+            MPCQP_UNROLL
+            for (int q_ = 1; q_ < EVQ; ++q_) x = (k >= WAVE * q_) ? ey[q_] : x;
+            return x;
+        }
+    };
+    // REG (lane_regs() only): vk is v[lane], which this lane has just computed (any value on the lanes >= nZ); the lane's own
+    // results go to `pr` -- ucum[] is stored only for the custom rows, which read it across lanes; tA[P_Y] always (H̃ z and
+    // the kept E z of the starting point read it later)
+    template <bool REG>
+    MPCQP_HD void primitives(const double* v, double vk, Prims& pr) {
         const int nu = d.nu;
         MPCQP_TICK(tic11_);
         if (qp.pair_on(P_U) || qp.pair_on(P_W)) {
             double* ucum = sm + c.ucum;
             if (d.nDU <= WAVE) {
-                const double acc = qp.block_prefix(w.lane < d.nDU ? v[w.lane] : 0.0);
-                if (w.lane < d.nDU) ucum[w.lane] = acc;
+                const double acc = qp.block_prefix(w.lane < d.nDU ? (REG ? vk : v[w.lane]) : 0.0);
+                if constexpr (REG) {
+                    pr.ucum = acc;
+                    if (qp.pair_on(P_W) && w.lane < d.nDU) ucum[w.lane] = acc;
+                } else {
+                    if (w.lane < d.nDU) ucum[w.lane] = acc;
+                }
             } else {
                 block_scan(v, ucum, false);
             }
         }
         MPCQP_TOCK(11, tic11_);
         MPCQP_TICK(tic12_);
-        if (qp.pair_on(P_Y) || qp.pair_on(P_W)) qp.E_apply(v, sm + c.tA[P_Y]);
+        if (qp.pair_on(P_Y) || qp.pair_on(P_W)) {
+            if constexpr (REG && EVQ > 0) qp.template E_apply_share_<true>(v, sm + c.tA[P_Y], pr.ey);
+            else qp.E_apply(v, sm + c.tA[P_Y]);
+        }
         MPCQP_TOCK(12, tic12_);
         if (qp.pair_on(P_X)) {
             double* tX = sm + c.tA[P_X];
@@ -2202,12 +2255,13 @@ struct Step {
         w.sync();
     }
 
-    MPCQP_HD double prim(int p, int k, const double* v) const {
+    template <bool REG>
+    MPCQP_HD double prim(int p, int k, const double* v, double vk, const Prims& pr) const {
         switch (p) {
-            case P_BOX: return v[k];
-            case P_U: return sm[c.ucum + k];
-            case P_DU: return v[k];
-            case P_Y: return (d.eps_host() >= 0 && k >= d.nY) ? 0.0 : sm[c.tA[P_Y] + k];      // (hosted row -eps <= 0: its row of E is zero)
+            case P_BOX: return REG ? vk : v[k];          // (REG: k = lane)
+            case P_U: return REG ? pr.ucum : sm[c.ucum + k];
+            case P_DU: return REG ? vk : v[k];
+            case P_Y: return (d.eps_host() >= 0 && k >= d.nY) ? 0.0 : (REG && EVQ > 0) ? pr.ey_at(k) : sm[c.tA[P_Y] + k];      // (hosted row -eps <= 0: its row of E is zero)
             case P_W: {
                 if constexpr (!has_w<DM>()) return 0.0;
                 else {
@@ -2226,13 +2280,18 @@ struct Step {
 
     // ---- fn(Row&, (G v)[row]) for every finite row -------------------------------------------
     template <class Fn>
-    MPCQP_HD void apply_G(const double* v, Fn fn) {
+    MPCQP_HD void apply_G(const double* v, Fn fn) { apply_G_<false>(v, fn, 0.0); }
+    // REG (lane_regs() only): vk is v[lane], as the lane that has just stored it holds it (v[] itself is complete and fenced:
+    // the products read it across lanes)
+    template <bool REG, class Fn>
+    MPCQP_HD void apply_G_(const double* v, Fn fn, double vk) {
         MPCQP_TIC();
-        primitives(v);
+        Prims pr;
+        primitives<REG>(v, vk, pr);
         const double e = d.neps ? v[d.nZ - 1] : 0.0;
         for_rows([&](int g, int k, Row& r) {
             if (!fin(r)) return;
-            const double pv = prim(g >> 1, k, v);
+            const double pv = prim<REG>(g >> 1, k, v, vk, pr);
             fn(r, ((g & 1) ? pv : -pv) - r.cs * e);
         });
         w.sync();    // tA[P_Y]/ucum are reused by the next product
@@ -2241,17 +2300,37 @@ struct Step {
 
     // ---- gt = G' wv, wv(Row&) evaluated on finite rows ---------------------------------------
     template <class Fn>
-    MPCQP_HD void apply_Gt(Fn wv) {
+    MPCQP_HD void apply_Gt(Fn wv) { apply_Gt_<false>(wv, nullptr); }
+    // One variable per lane on one wavefront (lane_regs()): what a lane computes for its own entry of a vector and reads
+    // back after the next fence is handed over in a register instead -- a store and a dependent LDS read less per hand-off.
+    MPCQP_HD static constexpr bool lane_regs() {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return one_row_per_lane<DM>() && W::NTEAM == 1;
+#else
+        return false;
+#endif
+    }
+    // REG (lane_regs() only): returns this lane's entry of G'w - sub (sub: a vector whose entry k lane k owns, or null; 0 on
+    // the lanes >= nZ) and leaves gt[] alone
+    template <bool REG, class Fn>
+    MPCQP_HD double apply_Gt_(Fn wv, const double* sub) {
         MPCQP_TIC();
         MPCQP_TICK(tic_gt_);
         const int nu = d.nu;
         // per pair: tA[k] = w_max - w_min ; eps accumulates -(c_min w_min + c_max w_max)
         double eacc = 0.0;
+        // REG: the differences of the groups whose entry k only lane k reads below (variable bounds, ΔU rows, U rows unless
+        // custom rows fold into them) stay in registers
+        const bool regU = REG && !(has_w<DM>() && qp.pair_on(P_W));
+        double tbox = 0.0, tdu = 0.0, tu = 0.0;
         for_pairs([&](int p, int k, Row* r0, Row* r1) {
             double wmin = 0.0, wmax = 0.0;
             if (r0 && fin(*r0)) { wmin = wv(*r0); eacc -= r0->cs * wmin; }
             if (r1 && fin(*r1)) { wmax = wv(*r1); eacc -= r1->cs * wmax; }
-            sm[c.tA[p] + k] = wmax - wmin;
+            if (REG && p == P_BOX) tbox = wmax - wmin;
+            else if (REG && p == P_DU) tdu = wmax - wmin;
+            else if (regU && p == P_U) tu = wmax - wmin;
+            else sm[c.tA[p] + k] = wmax - wmin;
         });
         eacc = w.sum(eacc);
         w.sync();
@@ -2265,13 +2344,14 @@ struct Step {
         MPCQP_TOCK(8, tic_gt_);
         MPCQP_TICK(tic9_);
         double sufU = 0.0;
-        if (useU && d.nDU <= WAVE) sufU = qp.block_suffix(w.lane < d.nDU ? sm[c.tA[P_U] + w.lane] : 0.0);
+        if (useU && d.nDU <= WAVE) sufU = qp.block_suffix(w.lane < d.nDU ? (regU ? tu : sm[c.tA[P_U] + w.lane]) : 0.0);
         else if (useU) block_scan(sm + c.tA[P_U], sm + c.tA[P_U], true);       // (tA[P_U] is consumed here: in place)
+        double mine = 0.0;
         for (int k = w.lane; k < d.nZ; k += WAVE) {
             double acc = 0.0;
-            if (qp.pair_on(P_BOX)) acc += sm[c.tA[P_BOX] + k];
+            if (qp.pair_on(P_BOX)) acc += REG ? tbox : sm[c.tA[P_BOX] + k];
             if (k < d.nDU) {
-                if (qp.pair_on(P_DU)) acc += sm[c.tA[P_DU] + k];
+                if (qp.pair_on(P_DU)) acc += REG ? tdu : sm[c.tA[P_DU] + k];
                 if (useU && d.nDU <= WAVE) acc += sufU;
                 else if (useU) acc += sm[c.tA[P_U] + k];
                 if (qp.pair_on(P_X)) {
@@ -2281,14 +2361,22 @@ struct Step {
             } else {
                 acc += eacc;
             }
-            gt[k] = acc;
+            if constexpr (REG) mine = acc;
+            else gt[k] = acc;
         }
         MPCQP_TOCK(9, tic9_);
         MPCQP_TICK(tic10_);
-        if (useY) qp.Et_apply_add(sm + c.tA[P_Y], gt);   // same lane owns gt[k]
+        if constexpr (REG) {
+            const double sk = (sub && w.lane < d.nZ) ? sub[w.lane] : 0.0;       // (in flight during E'w)
+            if (useY) qp.template Et_apply_share_<true>(sm + c.tA[P_Y], gt, 1.0, -1, mine);
+            if (sub) mine -= sk;
+        } else {
+            if (useY) qp.Et_apply_add(sm + c.tA[P_Y], gt);   // same lane owns gt[k]
+        }
         w.sync();
         MPCQP_TOCK(10, tic10_);
         MPCQP_TOC(1);
+        return mine;
     }
 
     // 2 N_k (k < nDU), 2 C (slack); 2 sum over the steps of block(k) of L[t, c(k)]
@@ -2987,16 +3075,21 @@ struct Step {
     // (enough of them for the strided offsets e (k0 + 4)); otherwise their entries are multiplied by zero
     static constexpr bool solve_zero_region() { return DM::zpad * DM::sp >= 3 * (DM::nZ + 3) + 4; }
     __device__ __forceinline__ void solve_static() {
+        const int i = w.lane;
+        solve_static_reg(i < DM::nZ ? gt[i] : 0.0);
+    }
+    // the right-hand side's entry of this lane in a register (0 on the lanes >= nZ); returns the lane's entry of the solution
+    __device__ __forceinline__ double solve_static_reg(double r) {
         constexpr int n = DM::nZ;
         const int i = w.lane;
         const bool act = i < n;
         const int rowi = pk(act ? i : 0, 0);
-        double r = act ? gt[i] : 0.0;
         double cf[4][4];
         solve_fwd_load<0>(cf, rowi, act);
         solve_fwd_tile<0>(r, cf, rowi, act);                // (runs on into the backward sweep)
         if (act) dz[i] = r;
         w.sync();
+        return act ? r : 0.0;
     }
 #endif
 
@@ -3598,12 +3691,14 @@ struct Step {
             cholesky();
             if (chol_broke) break;
             double rpa = 0.0;
+            bool Ez_kept = false;             // tA[P_Y] holds E z of this very z: the first round's H̃ z starts from it
             if (fresh) {                      // r evaluated exactly once, then carried as r += G dz
                 apply_G(z, [&](Row& r, double gz) {
                     r.gd = gz - r.h;
                     rpa = fmax(rpa, r.rp * fabs(r.gd));
                 });
                 fresh = false;
+                Ez_kept = true;
             } else {
                 for_rows([&](int, int, Row& r) { if (fin(r)) rpa = fmax(rpa, r.rp * fabs(r.gd)); });
             }
@@ -3618,7 +3713,8 @@ struct Step {
                 rpa_prev = rpa;
                 // r_A above the floor: the step needs G_A'l^; at the floor: the test needs G_A'l
                 const bool last = rpa <= 1e-13 * nh && !retry;
-                if (fold_H) Hz_structured(false);
+                if (fold_H) Hz_structured(Ez_kept);       // (later rounds: G dz has left E dz there)
+                Ez_kept = false;
                 apply_Gt([&](Row& r) { return last ? r.pp : r.rp * fma(rho, r.gd, r.pp); });
                 double rdn2, ndd2;
                 if (fold_H) {
@@ -3734,9 +3830,21 @@ struct Step {
     // same pass over the rows as G dz (one traversal of the row slots less per Newton solve).
     template <class Fn, class RowFn>
     MPCQP_HD void newton(Fn rc, RowFn rowfn) {
-        apply_Gt([&](Row& r) {
-            return row_wi_cached(r) * (rc(r) - r.lam * r.rp);
-        });
+        auto rhs = [&](Row& r) { return row_wi_cached(r) * (rc(r) - r.lam * r.rp); };
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (lane_regs()) {
+            // the lane's entry of the right-hand side goes from G'w to the solve in a register (gt[] is not written: nobody
+            // else reads it here)
+            const double g = apply_Gt_<true>(rhs, rd);
+            w.relane();
+            MPCQP_TIC();
+            const double dzk = solve_static_reg(g);
+            MPCQP_TOC(7);
+            apply_G_<true>(dz, [&](Row& r, double g_) { r.gd = g_; rowfn(r); }, dzk);
+            return;
+        }
+#endif
+        apply_Gt(rhs);
         for (int k = w.lane; k < d.nZ; k += WAVE) gt[k] -= rd[k];
         w.sync();
         solve_into_dz();
