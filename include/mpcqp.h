@@ -279,6 +279,8 @@ int mpcqp_recondense_device(mpcqp_handle h, void* stream);
 #define MPCQP_GET_XHAT_MS   8   /* (nx̂,Hp,B): X̂0(k+1..k+Hp) of the last MultipleShooting step -- the second block of the
                                  * reference's decision vector Z = [ΔU; X̂0] (src/controller/transcription.jl:5-7) */
 #define MPCQP_GET_MS_DEFECT 9   /* (B): max |E_S Z + F_S| (defect of the model equations, transcription.jl:303-327) of it */
+#define MPCQP_GET_KF_COV    10  /* (nx̂,nx̂,B): P̂ of the time-varying KalmanFilter (MPCQP_ERR_ORDER on a steady gain) */
+#define MPCQP_GET_KF_GAIN   11  /* (nx̂,nym,B): K̂ the estimator steps use -- the steady gain or K̂(k) of the last correction */
 int mpcqp_get(mpcqp_handle h, int which, double* out);
 
 /* ---- next row: the SteadyKalmanFilter steps on both sides of moveinput! --------
@@ -297,6 +299,37 @@ int mpcqp_kf_predict(mpcqp_handle h, double* xhat0, const double* u0, const doub
 /* device pointers, asynchronous on `stream` */
 int mpcqp_kf_correct_device(mpcqp_handle h, double* xhat0, const double* y0m, const double* d0, void* stream);
 int mpcqp_kf_predict_device(mpcqp_handle h, double* xhat0, const double* u0, const double* d0, void* stream);
+
+/* ---- the time-varying KalmanFilter (src/estimator/kalman.jl:1235-1290), direct = true -------------
+ * The estimator the reference asks for when the model changes during the run ("SteadyKalmanFilter does not support
+ * setmodel! (use KalmanFilter instead)", kalman.jl:229-232).  The covariance recursion
+ *       correction   M̂ = Ĉm P̂ Ĉm' + R̂,  K̂ = P̂ Ĉm' M̂⁻¹,  P̂ <- (I - K̂ Ĉm) P̂      (stored as ½ (P̂ + P̂'))
+ *       prediction   P̂ <- Â P̂ Â' + Q̂
+ * does not depend on the data: a kernel of its own advances P̂ and writes K̂(k) into the gain buffer of the handle, on the
+ * stream and ahead of the estimator step that reads it.  There are NO new per-period calls -- on a handle in
+ * time-varying mode
+ *       mpcqp_kf_correct / _correct_device   run the covariance correction, then the state correction with K̂(k);
+ *       mpcqp_kf_predict / _predict_device   run the state prediction, then the covariance prediction;
+ *       mpcqp_loop_device                    runs both halves of the covariance period, then the fused step.
+ * Every launch reads the model that is resident at that moment: a mpcqp_set_model between two periods is picked up
+ * with nothing else to call.
+ *
+ * mpcqp_kf_set_covariances: Qhat (nx̂,nx̂,B), Rhat (nym,nym,B), P0 (nx̂,nx̂,B), i_ym [nym] as in mpcqp_kf_set.  Puts the
+ * handle in time-varying mode with K̂ = 0, P̂ = P0 and every status 0.  Matrices that are not symmetric (beyond 1e-12 of
+ * their largest entry): MPCQP_ERR_ARG.  max(nx̂, nym) > 32, or a build without the kernel: MPCQP_ERR_UNSUPPORTED (the
+ * handle keeps what it had).  Called again with P0 == NULL (same nym) it replaces Q̂ and R̂ and keeps P̂ and K̂ -- the Q̂, R̂
+ * keywords of setmodel!.  A later mpcqp_kf_set returns the handle to the steady gain.
+ * mpcqp_kf_set_state_covariance: P (nx̂,nx̂,B) replaces P̂ -- setstate!(estim, x̂, P̂).
+ * mpcqp_kf_status: out [B], 0 or 2.  2: the last correction of that estimator was dropped because M̂ was not positive
+ * definite or not finite, or the new P̂ / K̂ was not finite (where the reference's cholesky! throws): P̂ and K̂ keep their
+ * values, and so does P̂ in the prediction of that period; the next correction that succeeds puts 0 back.  The other
+ * estimators of the batch and the LinMPC step statuses are unaffected.
+ * mpcqp_kf_lanes_per_estimator: 0 on a steady gain, else 16 (max(nx̂, nym) <= 16: four estimators per wavefront) or 64. */
+int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* Rhat, const double* P0,
+                             const int32_t* i_ym, int32_t nym);
+int mpcqp_kf_set_state_covariance(mpcqp_handle h, const double* P);
+int mpcqp_kf_status(mpcqp_handle h, int32_t* out);
+int mpcqp_kf_lanes_per_estimator(mpcqp_handle h);
 
 
 /* ---- which kernel runs a step; building specialised kernels ahead of the control loop -----------

@@ -184,6 +184,43 @@ function moveinput!(b::BatchLinMPC, ry::AbstractMatrix, d::AbstractMatrix=zeros(
 end
 
 # ------------------------------------------------------------------------------------------------
+# Time-varying KalmanFilter behind the batch (include/mpcqp.h, "the time-varying KalmanFilter"): P̂ and K̂(k) live on the
+# device and follow mpcqp_kf_correct / mpcqp_kf_predict / mpcqp_loop_device, on the model that is resident at that moment
+# (a setmodel! -> mpcqp_set_model between two periods needs nothing else).  direct = true only.  Call sequence = the one of
+# modelpredictivecontrol.jl_amd/api.py (BatchLinMPC.setestimator(covariances=...)), which the GPU tests drive; these ccalls
+# have not been run (no Julia on the build machines).
+import ModelPredictiveControl: KalmanFilter
+
+"Q̂, R̂, P̂ of the batch's KalmanFilters to the device; `keepP = true` replaces Q̂ and R̂ only (the keywords of setmodel!)."
+function push_kalmanfilter!(b::BatchLinMPC; keepP::Bool=false)
+    es = [c.estim for c in b.mpcs]
+    all(e -> e isa KalmanFilter && e.direct, es) || throw(ArgumentError("time-varying filter: KalmanFilter with direct=true"))
+    stack3(f) = cat((Matrix{Float64}(f(e)) for e in es)...; dims=3)          # (n, n, B)
+    Q̂, R̂, P̂ = stack3(e -> e.cov.Q̂), stack3(e -> e.cov.R̂), stack3(e -> e.cov.P̂)
+    i_ym = Cint.(es[1].i_ym .- 1)                                            # 0-based
+    GC.@preserve Q̂ R̂ P̂ i_ym check(ccall((:mpcqp_kf_set_covariances, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Cint),
+        b.h, Q̂, R̂, keepP ? C_NULL : pointer(P̂), i_ym, length(i_ym)))
+    return b
+end
+
+"setstate!(estim, x̂, P̂) for the batch: P (nx̂, nx̂, B)."
+set_state_covariance!(b::BatchLinMPC, P::Array{Float64,3}) =
+    check(ccall((:mpcqp_kf_set_state_covariance, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.h, P))
+
+"P̂ (nx̂, nx̂, B), K̂ (nx̂, nym, B) and the per-estimator status (0, or 2: the last correction was dropped) back into Julia."
+function pull_kalmanfilter(b::BatchLinMPC)
+    e = b.mpcs[1].estim
+    nx̂, nym, B = e.nx̂, e.nym, length(b.mpcs)
+    P̂, K̂, st = Array{Float64}(undef, nx̂, nx̂, B), Array{Float64}(undef, nx̂, nym, B), Vector{Cint}(undef, B)
+    check(ccall((:mpcqp_get, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), b.h, 10 #= MPCQP_GET_KF_COV =#, P̂))
+    check(ccall((:mpcqp_get, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), b.h, 11 #= MPCQP_GET_KF_GAIN =#, K̂))
+    check(ccall((:mpcqp_kf_status, lib), Cint, (Ptr{Cvoid}, Ptr{Cint}), b.h, st))
+    lanes = ccall((:mpcqp_kf_lanes_per_estimator, lib), Cint, (Ptr{Cvoid},), b.h)      # 0 steady gain, 16 or 64
+    return (; P̂, K̂, status=st, lanes)
+end
+
+# ------------------------------------------------------------------------------------------------
 # Batch of linear MovingHorizonEstimator objects (include/mpcqp_mhe.h; SURVEY 8 row f2).  The estimators keep
 # their Julia fields; preparestate! / updatestate! of the BATCH run on the device.  Call sequence = the one of
 # modelpredictivecontrol.jl_amd/mhe.py (BatchMHE), which the GPU tests drive.

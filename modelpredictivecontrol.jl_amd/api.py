@@ -31,11 +31,14 @@ KERNEL_GENERIC, KERNEL_AOT, KERNEL_ONDEMAND, KERNEL_SMALL, KERNEL_MS = 0, 1, 2, 
 SINGLE_SHOOTING, MULTIPLE_SHOOTING = 0, 1
 STATUS_OPTIMAL, STATUS_ITERATION_LIMIT, STATUS_ERROR = 0, 1, 2
 GET_HESSIAN, GET_STEPRESP, GET_KMAT, GET_BVEC, GET_QTILDE, GET_FVEC, GET_AUDIT, GET_XHAT_MS, GET_MS_DEFECT = 1, 2, 3, 4, 5, 6, 7, 8, 9
+GET_KF_COV, GET_KF_GAIN = 10, 11
+KF_STATUS_OK, KF_STATUS_DROPPED = 0, 2
 EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_create",
            "mpcqp_destroy", "mpcqp_get_sizes", "mpcqp_set_model", "mpcqp_set_weights",
            "mpcqp_set_bounds", "mpcqp_step", "mpcqp_step_device", "mpcqp_loop_device", "mpcqp_recondense_device",
            "mpcqp_get", "mpcqp_last_step_ms", "mpcqp_last_condense_ms", "mpcqp_last_predmat_ms", "mpcqp_kf_set",
            "mpcqp_kf_correct", "mpcqp_kf_predict", "mpcqp_kf_correct_device", "mpcqp_kf_predict_device",
+           "mpcqp_kf_set_covariances", "mpcqp_kf_set_state_covariance", "mpcqp_kf_status", "mpcqp_kf_lanes_per_estimator",
            "mpcqp_set_output_weight_blocks", "mpcqp_set_dense_weights", "mpcqp_set_custom_constraints", "mpcqp_set_custom_bounds",
            "mpcqp_set_flags", "mpcqp_set_iteration_limit", "mpcqp_set_transcription", "mpcqp_transcription_supported", "mpcqp_set_current_setpoint", "mpcqp_prepare", "mpcqp_kernel_kind", "mpcqp_lds_bytes", "mpcqp_row_groups", "mpcqp_step_consts_builds", "mpcqp_prebuild",
            "mpcqp_last_build_error", "mpcqp_multi_create", "mpcqp_multi_destroy", "mpcqp_multi_ndev",
@@ -165,6 +168,10 @@ def load_library(path: str | None = None):
     lib.mpcqp_kf_predict.argtypes = [C.c_void_p] * 4
     lib.mpcqp_kf_correct_device.argtypes = [C.c_void_p] * 5
     lib.mpcqp_kf_predict_device.argtypes = [C.c_void_p] * 5
+    lib.mpcqp_kf_set_covariances.argtypes = [C.c_void_p] * 5 + [C.c_int32]
+    lib.mpcqp_kf_set_state_covariance.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mpcqp_kf_status.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mpcqp_kf_lanes_per_estimator.argtypes = [C.c_void_p]
     lib.mpcqp_set_current_setpoint.argtypes = [C.c_void_p, C.c_void_p]
     lib.mpcqp_prepare.argtypes = [C.c_void_p]
     lib.mpcqp_kernel_kind.argtypes = [C.c_void_p]
@@ -369,7 +376,8 @@ class Handle:
         shape = {GET_HESSIAN: (self.B, self.nZ, self.nZ), GET_STEPRESP: (self.B, self.Hp, self.nu, self.ny),
                  GET_KMAT: (self.B, self.nxhat, self.nY), GET_BVEC: (self.B, self.nY),
                  GET_QTILDE: (self.B, self.nZ), GET_FVEC: (self.B, self.nY), GET_AUDIT: (self.B, 4),
-                 GET_XHAT_MS: (self.B, self.Hp, self.nxhat), GET_MS_DEFECT: (self.B,)}[which]
+                 GET_XHAT_MS: (self.B, self.Hp, self.nxhat), GET_MS_DEFECT: (self.B,),
+                 GET_KF_COV: (self.B, self.nxhat, self.nxhat), GET_KF_GAIN: (self.B, getattr(self, "nym", 0), self.nxhat)}[which]
         out = np.empty(shape)
         _chk(self.lib, self.lib.mpcqp_get(self.h, which, _ptr(out)))
         return out
@@ -389,6 +397,39 @@ class Handle:
         iy = np.ascontiguousarray(i_ym, dtype=np.int32)
         self.nym = int(iy.size)
         _chk(self.lib, self.lib.mpcqp_kf_set(self.h, _ptr(K), _ptr(iy), self.nym))
+
+    # -- time-varying KalmanFilter: covariance / gain recursion on the device (csrc/kf_kernels.hip) --------
+    def kf_set_covariances(self, Qhat, Rhat, P0, i_ym):
+        """Qhat (B,nx̂,nx̂), Rhat (B,nym,nym), P0 (B,nx̂,nx̂) or None (keep P̂: the Q̂, R̂ keywords of setmodel!), symmetric.
+        The handle then runs the covariance recursion ahead of kf_correct / kf_predict / loop_device."""
+        iy = np.ascontiguousarray(i_ym, dtype=np.int32)
+        arrs = [None if a is None else colmajor(a) for a in (Qhat, Rhat, P0)]
+        _chk(self.lib, self.lib.mpcqp_kf_set_covariances(self.h, *[_ptr(a) for a in arrs], _ptr(iy), int(iy.size)))
+        self.nym = int(iy.size)
+
+    def kf_set_state_covariance(self, P):
+        _chk(self.lib, self.lib.mpcqp_kf_set_state_covariance(self.h, _ptr(colmajor(P))))
+
+    def kf_covariance(self):
+        """P̂ (B,nx̂,nx̂)."""
+        return self.get(GET_KF_COV).transpose(0, 2, 1).copy()
+
+    def kf_gain(self):
+        """K̂ (B,nx̂,nym): the steady gain, or K̂(k) of the last correction."""
+        return self.get(GET_KF_GAIN).transpose(0, 2, 1).copy()
+
+    def kf_status(self):
+        """(B,) int32: 0, or 2 where the last covariance correction was dropped (include/mpcqp.h)."""
+        out = np.empty(self.B, np.int32)
+        _chk(self.lib, self.lib.mpcqp_kf_status(self.h, _ptr(out)))
+        return out
+
+    def kf_lanes_per_estimator(self):
+        """0 on a steady gain; 16 / 64 lanes per estimator of the covariance kernel otherwise."""
+        n = self.lib.mpcqp_kf_lanes_per_estimator(self.h)
+        if n < 0:
+            _chk(self.lib, n)
+        return n
 
     def kf_correct(self, xhat0, y0m, d0=None):
         """x̂0 += K̂ (y0m - Ĉm x̂0 - D̂dm d0), in place on the (B,nx̂) host array."""
@@ -848,16 +889,68 @@ class BatchLinMPC:
         return self
 
     # -- estimator steps on both sides of moveinput! (SteadyKalmanFilter) ---------------------
-    def setestimator(self, Khat, i_ym=None, xhat0=None):
+    def setestimator(self, Khat=None, i_ym=None, xhat0=None, *, covariances=None, direct=True):
         """Attach a SteadyKalmanFilter: Khat (B,nx̂,nym) steady-state gain (see
         `steady_kalman_gain`), i_ym measured-output indices (default all).  The estimate x̂0
-        (deviation, (B,nx̂)) is then carried by this object like `mpc.estim.x̂0`."""
+        (deviation, (B,nx̂)) is then carried by this object like `mpc.estim.x̂0`.
+
+        `covariances=dict(Qhat=…, Rhat=…, P0=…)` attaches the time-varying `KalmanFilter` instead (kalman.jl:1235-1290):
+        Q̂ (nx̂,nx̂), R̂ (nym,nym), P̂_0 (nx̂,nx̂), each shared or with a leading batch axis.  P̂ and K̂(k) then live on the
+        device and follow `preparestate` / `updatestate` (and `setmodel`: the recursion reads the current model)."""
+        if not direct:
+            raise NotImplementedError("direct=False (predictor form) is not built: the estimator steps assume direct=True")
+        if covariances is not None:
+            if Khat is not None:
+                raise ValueError("give either Khat (SteadyKalmanFilter) or covariances (KalmanFilter)")
+            return self.setkalmanfilter(**covariances, i_ym=i_ym, xhat0=xhat0)
+        if Khat is None:
+            raise ValueError("setestimator needs Khat or covariances")
+        self.kf_timevarying = False
         self.i_ym = np.arange(self.ny) if i_ym is None else np.asarray(i_ym, int)
         Khat = np.asarray(Khat, float)
         if Khat.shape != (self.B, self.nxh, len(self.i_ym)):
             raise ValueError("Khat size must be (B, nx̂, nym)")
         self.hd.kf_set(colmajor(Khat), self.i_ym)
         self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
+        return self
+
+    def _cov(self, M, n, name):
+        a = np.asarray(M, float)
+        if a.shape == (n, n):
+            a = np.broadcast_to(a, (self.B, n, n))
+        if a.shape != (self.B, n, n):
+            raise ValueError(f"{name} size must be ({n}, {n})")
+        if not np.allclose(a, a.transpose(0, 2, 1), rtol=0.0, atol=1e-12 * max(float(np.abs(a).max()), 0.0)):
+            raise ValueError(f"{name} must be Hermitian")                # (the reference's Hermitian{NT} fields)
+        return a
+
+    def setkalmanfilter(self, Qhat, Rhat, P0, i_ym=None, xhat0=None, direct=True):
+        """The time-varying `KalmanFilter` (see `setestimator(covariances=…)`); keyword names are the reference's Q̂, R̂, P̂_0."""
+        if not direct:
+            raise NotImplementedError("direct=False (predictor form) is not built: the estimator steps assume direct=True")
+        self.i_ym = np.arange(self.ny) if i_ym is None else np.asarray(i_ym, int)
+        nym = len(self.i_ym)
+        self.hd.kf_set_covariances(self._cov(Qhat, self.nxh, "Q̂"), self._cov(Rhat, nym, "R̂"), self._cov(P0, self.nxh, "P̂_0"), self.i_ym)
+        self.kf_timevarying = True
+        self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
+        return self
+
+    def setcovariances(self, Qhat, Rhat):
+        """The Q̂, R̂ keywords of `setmodel!` (KalmanFilter only): new noise covariances, P̂ and x̂0 stay."""
+        if not getattr(self, "kf_timevarying", False):
+            raise ValueError("Q̂ and R̂ can only be replaced on a time-varying KalmanFilter (setestimator(covariances=…))")
+        self.hd.kf_set_covariances(self._cov(Qhat, self.nxh, "Q̂"), self._cov(Rhat, len(self.i_ym), "R̂"), None, self.i_ym)
+
+    def setstate(self, xhat, Phat=None):
+        """`setstate!(estim, x̂, P̂)` (src/estimator/execute.jl): x̂ (nx̂,) or (B,nx̂) in engineering units; P̂ only on a
+        time-varying KalmanFilter."""
+        if not hasattr(self, "i_ym"):
+            raise ValueError("no estimator attached (setestimator)")
+        if Phat is not None:
+            if not getattr(self, "kf_timevarying", False):
+                raise ValueError("the SteadyKalmanFilter has no covariance estimate P̂ to set")
+            self.hd.kf_set_state_covariance(self._cov(Phat, self.nxh, "P̂"))
+        self.xhat0 = _f64(self._bc(xhat, self.nxh, "x̂") - self.xhop).copy()
         return self
 
     def preparestate(self, ym, d=None):
@@ -1003,6 +1096,8 @@ class BatchLinMPC:
             X0 = self.hd.get(GET_XHAT_MS)
             x = X0[:, -1]
         info["x̂end"] = x + self.xhop
+        if getattr(self, "kf_timevarying", False):     # the estimator's covariance, gain and per-estimator status
+            info["P̂"], info["K̂"], info["kf_status"] = self.hd.kf_covariance(), self.hd.kf_gain(), self.hd.kf_status()
         # decision vector in the transcription's layout: [ΔU; ϵ] or [ΔU; X̂0(k+1..k+Hp); ϵ] (get_nZ_mpc, transcription.jl:2-7)
         parts = [DU] + ([X0.reshape(self.B, -1)] if self.transcription == "MultipleShooting" else []) + ([eps[:, None]] if self.neps else [])
         info["Z̃"] = np.concatenate(parts, axis=1)
@@ -1040,7 +1135,7 @@ class BatchLinMPC:
                     Wv = Wv + np.einsum("bij,btj->bti", self.Wd, de)
                 info["W"] = Wv.reshape(self.B, -1)
         for a, k in (("DeltaU", "ΔU"), ("epsilon", "ϵ"), ("Dhat", "D̂"), ("xhat", "x̂"), ("yhat", "ŷ"), ("Yhat", "Ŷ"),
-                     ("xhatend", "x̂end"), ("Yhats", "Ŷs"), ("Rhaty", "R̂y"), ("Rhatu", "R̂u"), ("Ztilde", "Z̃"), ("Xhat0", "X̂0")):
+                     ("xhatend", "x̂end"), ("Yhats", "Ŷs"), ("Rhaty", "R̂y"), ("Rhatu", "R̂u"), ("Ztilde", "Z̃"), ("Xhat0", "X̂0"), ("Phat", "P̂"), ("Khat", "K̂")):
             if k in info:
                 info[a] = info[k]
         return info

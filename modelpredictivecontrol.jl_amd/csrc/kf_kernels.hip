@@ -1,0 +1,62 @@
+// kf_kernels.hip -- gfx950 kernels of the covariance / gain recursion of the time-varying KalmanFilter (bodies:
+// kf_cov_bodies.h).  One wavefront per workgroup, persistent grid, the same split as the MovingHorizonEstimator:
+//   k_kf_cov<NX>,      NX = 4, 8, 12, 16: max(nx̂, nym) <= 16, four estimators per wavefront (one per DPP row, MheDevWave);
+//   k_kf_cov_wide<NX>, NX = 24, 32: 16 < max(nx̂, nym) <= 32, one estimator per wavefront, the NX^3 products on the
+//                      matrix cores through the LDS staging buffer of Ops::mm_staged.
+#include <hip/hip_runtime.h>
+
+#include "kf_cov_bodies.h"
+#include "kf_cov_launch.h"
+#include "mhe_devwave.h"
+#include "mhe_wide_devwave.h"
+#include "mpcqp_launch.h"
+
+namespace mpcqp {
+namespace kf {
+
+using mhe::MheDevWave;
+using WideWave = mhe::MheWideMfmaWave;
+static constexpr size_t kStageBytes = mhe::stage_doubles() * sizeof(double);
+
+template <int NX>
+__global__ __launch_bounds__(64) void k_kf_cov(CovArgs a, int mode) {
+    MheDevWave w{(int)threadIdx.x};
+    kf_cov_body<MheDevWave, NX>(w, a, mode, (int)blockIdx.x);
+}
+// (registers: five rows of NX doubles, 320 at NX = 32 -- one wavefront per SIMD)
+template <int NX>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_kf_cov_wide(CovArgs a, int mode) {
+    WideWave w;
+    w.lane = (int)threadIdx.x;
+    w.stage = mpcqp_smem;
+    kf_cov_body<WideWave, NX>(w, a, mode, (int)blockIdx.x);
+}
+
+hipError_t launch_kf_cov(const CovArgs& a, int mode, hipStream_t st) {
+    if (a.B < 1 || a.nwaves < 1 || a.nx < 1 || a.nym < 1 || a.nx > a.NX || a.nym > a.NX) return hipErrorInvalidValue;
+    switch (a.NX) {
+        case 4: hipLaunchKernelGGL(k_kf_cov<4>, dim3(a.nwaves), dim3(WAVE), 0, st, a, mode); break;
+        case 8: hipLaunchKernelGGL(k_kf_cov<8>, dim3(a.nwaves), dim3(WAVE), 0, st, a, mode); break;
+        case 12: hipLaunchKernelGGL(k_kf_cov<12>, dim3(a.nwaves), dim3(WAVE), 0, st, a, mode); break;
+        case 16: hipLaunchKernelGGL(k_kf_cov<16>, dim3(a.nwaves), dim3(WAVE), 0, st, a, mode); break;
+        case 24: hipLaunchKernelGGL(k_kf_cov_wide<24>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a, mode); break;
+        case 32: hipLaunchKernelGGL(k_kf_cov_wide<32>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a, mode); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// The grid: registers allow two wavefronts per SIMD for the 16-lane kernels (eight per CU), one for the wide ones (four per
+// CU; their 16.5 KB of staging would allow nine).
+int kf_cov_waves_for(int device, int B, int NX) {
+    int cus = 256;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    const bool wide = NX > mhe::RL;
+    const int groups = wide ? B : (B + mhe::GPW - 1) / mhe::GPW;
+    const int cap = cus * (wide ? 4 : 8);
+    return groups < cap ? groups : cap;
+}
+
+}  // namespace kf
+}  // namespace mpcqp

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mpcqp.h"
+#include "kf_cov_launch.h"
 #include "mpcqp_hostutil.h"
 #include "mpcqp_launch.h"
 #include "ms_bodies.h"
@@ -63,6 +64,11 @@ struct mpcqp_handle_s {
     DBuf kf_K, kf_iym, kf_x, kf_y, kf_u, kf_d;
     KfParams kf{};
     bool have_kf = false;
+    // time-varying KalmanFilter (mpcqp_kf_set_covariances): kf_K then holds K̂(k), written by the covariance kernel
+    // (kf_kernels.hip) ahead of every estimator step that reads it
+    bool kf_tv = false;
+    DBuf kf_Q, kf_R, kf_P, kf_st;
+    int kf_NX = 0, kf_waves = 0;   // register columns and persistent grid of the covariance kernel
     // MultipleShooting transcription (mpcqp_set_transcription): the stage-structured kernel of ms_bodies.h
     int transcription = MPCQP_SINGLE_SHOOTING;
     bool stage_only = false;         // nZ~ > 256: only the stage-structured kernel can take this handle (nothing is condensed)
@@ -642,6 +648,22 @@ int mpcqp_transcription_supported(mpcqp_handle h) {
     return uses_stage_kernel(h) ? ms_unsupported(h) : 0;
 }
 
+// One launch of the covariance / gain recursion of a time-varying handle (kf_kernels.hip) on the model that is resident
+// now: mode bit 0 the correction (K̂(k), P̂(k|k)), bit 1 the prediction (P̂(k+1|k)).
+static int kf_cov_launch(mpcqp_handle h, int mode, hipStream_t st) {
+    if (!kf::kf_cov_available()) return MPCQP_ERR_UNSUPPORTED;
+    ON_DEVICE(h);
+    const Dims& d = h->d;
+    kf::CovArgs a{};
+    a.Ahat = h->m.Ahat; a.C = h->m.C; a.i_ym = h->kf.i_ym;
+    a.Q = (const double*)h->kf_Q.p; a.R = (const double*)h->kf_R.p;
+    a.P = (double*)h->kf_P.p; a.K = (double*)h->kf_K.p; a.status = (int32_t*)h->kf_st.p;
+    a.B = d.B; a.nx = d.nxh; a.ny = d.ny; a.nym = h->kf.nym;
+    a.NX = h->kf_NX; a.nwaves = h->kf_waves;
+    HIPCHK(kf::launch_kf_cov(a, mode, st));
+    return MPCQP_OK;
+}
+
 // shared by mpcqp_step_device (kf = false) and mpcqp_loop_device
 static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* Ry,
                             const double* Ru, const double* d0, const double* Dhat0, double* Ztilde, double* u0,
@@ -759,6 +781,13 @@ int mpcqp_loop_device(mpcqp_handle h, double* xhat0, const double* y0m, const do
     if (!h || !y0m || !xhat0) return MPCQP_ERR_NULL;
     if (!h->have_kf) return MPCQP_ERR_ORDER;
     if (h->d.nxh > 4 * WAVE) return MPCQP_ERR_UNSUPPORTED;
+    if (h->kf_tv) {     // K̂(k) and P̂(k+1|k) first: the recursion is data independent (a refused step leaves P̂ one period ahead)
+        if (!lastu0 || !Ry || !Ztilde || !u0 || !status || (h->d.nd > 0 && (!d0 || !Dhat0))) return MPCQP_ERR_NULL;
+        if (!h->have_model || !h->have_weights) return MPCQP_ERR_ORDER;
+        if (uses_stage_kernel(h) && ms_unsupported(h)) return MPCQP_ERR_UNSUPPORTED;
+        int rc = kf_cov_launch(h, kf::COV_CORRECT | kf::COV_PREDICT, (hipStream_t)stream);
+        if (rc) return rc;
+    }
     return step_device_impl(h, xhat0, lastu0, Ry, Ru, d0, Dhat0, Ztilde, u0, status, iters, Yhat0, stream,
                             y0m, xhat0, 1);
 }
@@ -881,6 +910,14 @@ int mpcqp_get(mpcqp_handle h, int which, double* out) {
             if (!h->audit.p) return MPCQP_ERR_ORDER;
             HIPCHK(hipMemcpy(out, h->audit.p, B * 4 * sizeof(double), hipMemcpyDeviceToHost));
             return MPCQP_OK;
+        case MPCQP_GET_KF_COV:
+            if (!h->have_kf || !h->kf_tv) return MPCQP_ERR_ORDER;
+            HIPCHK(hipMemcpy(out, h->kf_P.p, B * d.nxh * d.nxh * sizeof(double), hipMemcpyDeviceToHost));
+            return MPCQP_OK;
+        case MPCQP_GET_KF_GAIN:
+            if (!h->have_kf) return MPCQP_ERR_ORDER;
+            HIPCHK(hipMemcpy(out, h->kf_K.p, B * d.nxh * h->kf.nym * sizeof(double), hipMemcpyDeviceToHost));
+            return MPCQP_OK;
 #ifdef MPCQP_PROFILE
         case 99:     /* per-phase cycle counters of profiling builds (-DMPCQP_PROFILE): (16,B) */
             if (!h->prof.p) return MPCQP_ERR_ORDER;
@@ -911,7 +948,88 @@ int mpcqp_kf_set(mpcqp_handle h, const double* Khat, const int32_t* i_ym, int32_
     h->kf.i_ym = (const int*)h->kf_iym.p;
     h->kf.nym = nym;
     h->have_kf = true;
+    h->kf_tv = false;           // (back to the steady gain: the covariance kernel no longer runs)
     return MPCQP_OK;
+}
+
+// every member of a (n,n,B) array symmetric up to 1e-12 of its largest entry (a NaN fails)
+static bool kf_symmetric(const double* M, size_t B, int n) {
+    for (size_t b = 0; b < B; ++b) {
+        const double* A = M + b * (size_t)n * n;
+        double big = 0.0;
+        for (int i = 0; i < n * n; ++i) big = std::fmax(big, std::fabs(A[i]));
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < i; ++j)
+                if (!(std::fabs(A[i + (size_t)n * j] - A[j + (size_t)n * i]) <= 1e-12 * big)) return false;
+        if (!(big == big)) return false;
+    }
+    return true;
+}
+
+int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* Rhat, const double* P0,
+                             const int32_t* i_ym, int32_t nym) {
+    if (!h || !Qhat || !Rhat || !i_ym) return MPCQP_ERR_NULL;
+    if (!P0 && !h->kf_tv) return MPCQP_ERR_NULL;        // (Q̂ / R̂ alone: only on a handle that carries a P̂)
+    const Dims& d = h->d;
+    if (nym < 1 || nym > d.ny) return MPCQP_ERR_DIMS;
+    if (!P0 && nym != h->kf.nym) return MPCQP_ERR_DIMS;
+    for (int i = 0; i < nym; ++i) {
+        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;     // validate_ym, construct.jl:190-196
+        for (int j = 0; j < i; ++j)
+            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
+    }
+    if (std::max(d.nxh, (int)nym) > mhe::NX_MAX || !kf::kf_cov_available()) return MPCQP_ERR_UNSUPPORTED;
+    const size_t B = d.B, nn = (size_t)d.nxh * d.nxh, sz = sizeof(double);
+    if (!kf_symmetric(Qhat, B, d.nxh) || !kf_symmetric(Rhat, B, nym) || (P0 && !kf_symmetric(P0, B, d.nxh))) return MPCQP_ERR_ARG;
+    ON_DEVICE(h);
+    int rc = upload(h, h->kf_Q, Qhat, B * nn * sz);
+    if (!rc) rc = upload(h, h->kf_R, Rhat, B * (size_t)nym * nym * sz);
+    if (!rc) rc = upload(h, h->kf_iym, i_ym, (size_t)nym * sizeof(int32_t));
+    if (!rc && P0) rc = upload(h, h->kf_P, P0, B * nn * sz);
+    if (!rc && P0) rc = dev_alloc(h, h->kf_K, B * (size_t)d.nxh * nym * sz);
+    if (!rc && P0) rc = dev_alloc(h, h->kf_st, B * sizeof(int32_t));
+    if (rc) return rc;
+    if (P0) {
+        HIPCHK(hipMemsetAsync(h->kf_K.p, 0, B * (size_t)d.nxh * nym * sz, h->stream));
+        HIPCHK(hipMemsetAsync(h->kf_st.p, 0, B * sizeof(int32_t), h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->kf.Khat = (const double*)h->kf_K.p;
+    h->kf.i_ym = (const int*)h->kf_iym.p;
+    h->kf.nym = nym;
+    h->kf_NX = kf::kf_cov_columns_for(std::max(d.nxh, (int)nym));
+    h->kf_waves = kf::kf_cov_waves_for(h->device, d.B, h->kf_NX);
+    h->have_kf = true;
+    h->kf_tv = true;
+    return MPCQP_OK;
+}
+
+int mpcqp_kf_set_state_covariance(mpcqp_handle h, const double* P) {
+    if (!h || !P) return MPCQP_ERR_NULL;
+    if (!h->kf_tv) return MPCQP_ERR_ORDER;
+    const Dims& d = h->d;
+    if (!kf_symmetric(P, d.B, d.nxh)) return MPCQP_ERR_ARG;
+    ON_DEVICE(h);
+    int rc = upload(h, h->kf_P, P, (size_t)d.B * d.nxh * d.nxh * sizeof(double));
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(h->kf_st.p, 0, (size_t)d.B * sizeof(int32_t), h->stream));     // (a P̂ the caller vouches for)
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
+int mpcqp_kf_status(mpcqp_handle h, int32_t* out) {
+    if (!h || !out) return MPCQP_ERR_NULL;
+    if (!h->kf_tv) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, h->kf_st.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MPCQP_OK;
+}
+
+int mpcqp_kf_lanes_per_estimator(mpcqp_handle h) {
+    if (!h) return MPCQP_ERR_NULL;
+    return h->kf_tv ? kf::kf_cov_lanes_for(h->kf_NX) : 0;
 }
 
 int mpcqp_kf_correct_device(mpcqp_handle h, double* xhat0, const double* y0m, const double* d0, void* stream) {
@@ -919,6 +1037,7 @@ int mpcqp_kf_correct_device(mpcqp_handle h, double* xhat0, const double* y0m, co
     if (h->d.nd > 0 && !d0) return MPCQP_ERR_NULL;
     if (!h->have_model || !h->have_kf) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
+    if (h->kf_tv) { int rc = kf_cov_launch(h, kf::COV_CORRECT, (hipStream_t)stream); if (rc) return rc; }
     HIPCHK(launch_kf_correct(h->d, h->m, h->kf, xhat0, y0m, d0, (hipStream_t)stream));
     return MPCQP_OK;
 }
@@ -930,6 +1049,7 @@ int mpcqp_kf_predict_device(mpcqp_handle h, double* xhat0, const double* u0, con
     if (h->d.nxh > 64) return MPCQP_ERR_UNSUPPORTED;
     ON_DEVICE(h);
     HIPCHK(launch_kf_predict(h->d, h->m, xhat0, u0, d0, (hipStream_t)stream));
+    if (h->kf_tv) { int rc = kf_cov_launch(h, kf::COV_PREDICT, (hipStream_t)stream); if (rc) return rc; }
     return MPCQP_OK;
 }
 
