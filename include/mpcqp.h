@@ -283,34 +283,64 @@ int mpcqp_recondense_device(mpcqp_handle h, void* stream);
 #define MPCQP_GET_KF_GAIN   11  /* (nx̂,nym,B): K̂ the estimator steps use -- the steady gain or K̂(k) of the last correction */
 int mpcqp_get(mpcqp_handle h, int which, double* out);
 
-/* ---- next row: the SteadyKalmanFilter steps on both sides of moveinput! --------
- * `preparestate!` -> correct_estimate_obsv! (src/estimator/kalman.jl:284-295):
+/* ---- next row: the Kalman filter steps on both sides of moveinput! ----------------
+ * correction, correct_estimate_obsv! (src/estimator/kalman.jl:284-295):
  *       x̂0 += K̂ (y0m - Ĉm x̂0 - D̂dm d0)
- * `updatestate!`  -> predict_estimate_obsv! (src/estimator/kalman.jl:298-309):
+ * prediction, predict_estimate_obsv! (src/estimator/kalman.jl:298-309):
  *       x̂0 <- Â x̂0 + B̂u u0 + B̂d d0 + (f̂op - x̂op)
  * on the model given to mpcqp_set_model, so that a closed loop keeps x̂0 resident on the GPU.
  * Khat (nx̂,nym,B) is the steady-state gain (the reference gets it from
  * ControlSystemsBase.kalman at construction, kalman.jl:204-236: host-side, once);
- * i_ym [nym] are the 0-based indices of the measured outputs.  nx̂ <= 64.                     */
+ * i_ym [nym] are the 0-based indices of the measured outputs.  nx̂ <= 64.
+ *
+ * Missing measurements (kalman.jl:245-251, 478-484; execute.jl:335,375).  Estimator b MISSES the correction of a period
+ * when any of the nym entries of its y0m row is NaN -- the reference's any(isnan, y0m); Inf is a measurement -- or when
+ * the period has no y0m at all (mpcqp_kf_correct[_device] or mpcqp_kf_update[_device] with y0m == NULL, `ym = nothing`).  On a missed correction x̂0 keeps its
+ * bits (and so do P̂ and K̂ of a time-varying handle); the prediction of that period DOES run.  The decision is per
+ * estimator: the rest of the batch is untouched.  mpcqp_kf_correct[_device], mpcqp_kf_update[_device] and
+ * mpcqp_loop_device all follow the rule.
+ *
+ * The two forms of the estimator (`direct`, kalman.jl:112).  Filter form, direct = true (the default): a period is
+ * correction with y0m(k) [preparestate!], step, prediction with u0(k) [updatestate!].  Predictor form, direct = false:
+ * preparestate! does nothing, the step works on x̂ as it stands, x̂_{k-1}(k), and updatestate! runs the correction and then
+ * the prediction (kalman.jl:276-281, 520-525) -- the input of period k does not wait for y(k).  The arithmetic of each
+ * half is that of the filter form.  The gain stays the caller's and stays the FILTER-form gain: the library applies
+ * x̂ <- Â (x̂ + K̂ v) + ... like update_estimate!, so the Khat to hand over is the same in both forms (the reference's own
+ * direct = false gain, Â K̂, is not what is expected here).
+ * mpcqp_kf_set_direct: 1 (default) or 0; anything else MPCQP_ERR_ARG.  A property of the handle that mpcqp_kf_set and
+ * mpcqp_kf_set_covariances leave alone.  It changes the one entry point whose order is fixed inside a launch:
+ * mpcqp_loop_device runs correction -> step -> prediction with 1 and step -> correction -> prediction with 0.
+ * mpcqp_kf_update[_device]: correction, then prediction -- updatestate! of a direct = false estimator; legal whatever the
+ * flag.  The result equals mpcqp_kf_correct followed by mpcqp_kf_predict bit for bit.  y0m == NULL: no correction for
+ * any estimator.  MPCQP_ERR_ORDER before a model and an estimator are attached.                                   */
 int mpcqp_kf_set(mpcqp_handle h, const double* Khat, const int32_t* i_ym, int32_t nym);
-/* xhat0 (nx̂,B) in/out, y0m (nym,B), d0 (nd,B) or NULL, u0 (nu,B): host pointers, synchronous */
+int mpcqp_kf_set_direct(mpcqp_handle h, int32_t direct);
+/* xhat0 (nx̂,B) in/out, y0m (nym,B) -- or NULL in mpcqp_kf_correct / mpcqp_kf_update: no measurement this period --,
+ * d0 (nd,B) or NULL, u0 (nu,B): host pointers, synchronous */
 int mpcqp_kf_correct(mpcqp_handle h, double* xhat0, const double* y0m, const double* d0);
 int mpcqp_kf_predict(mpcqp_handle h, double* xhat0, const double* u0, const double* d0);
+int mpcqp_kf_update(mpcqp_handle h, double* xhat0, const double* u0, const double* y0m, const double* d0);
 /* device pointers, asynchronous on `stream` */
 int mpcqp_kf_correct_device(mpcqp_handle h, double* xhat0, const double* y0m, const double* d0, void* stream);
 int mpcqp_kf_predict_device(mpcqp_handle h, double* xhat0, const double* u0, const double* d0, void* stream);
+int mpcqp_kf_update_device(mpcqp_handle h, double* xhat0, const double* u0, const double* y0m, const double* d0,
+                           void* stream);
 
-/* ---- the time-varying KalmanFilter (src/estimator/kalman.jl:1235-1290), direct = true -------------
+/* ---- the time-varying KalmanFilter (src/estimator/kalman.jl:1235-1290) ----------------------------
  * The estimator the reference asks for when the model changes during the run ("SteadyKalmanFilter does not support
  * setmodel! (use KalmanFilter instead)", kalman.jl:229-232).  The covariance recursion
  *       correction   M̂ = Ĉm P̂ Ĉm' + R̂,  K̂ = P̂ Ĉm' M̂⁻¹,  P̂ <- (I - K̂ Ĉm) P̂      (stored as ½ (P̂ + P̂'))
  *       prediction   P̂ <- Â P̂ Â' + Q̂
- * does not depend on the data: a kernel of its own advances P̂ and writes K̂(k) into the gain buffer of the handle, on the
- * stream and ahead of the estimator step that reads it.  There are NO new per-period calls -- on a handle in
- * time-varying mode
+ * depends on WHICH measurements are missing and on nothing else in the data: a kernel of its own advances P̂ and writes
+ * K̂(k) into the gain buffer of the handle, on the stream and ahead of the estimator step that reads it.  There are NO
+ * new per-period calls -- on a handle in time-varying mode
  *       mpcqp_kf_correct / _correct_device   run the covariance correction, then the state correction with K̂(k);
  *       mpcqp_kf_predict / _predict_device   run the state prediction, then the covariance prediction;
- *       mpcqp_loop_device                    runs both halves of the covariance period, then the fused step.
+ *       mpcqp_kf_update / _update_device     run both halves of the covariance period in ONE launch (P̂ moves once), then
+ *                                            the state correction and the state prediction; with y0m == NULL the
+ *                                            covariance prediction alone, and every status becomes 1;
+ *       mpcqp_loop_device                    runs both halves of the covariance period (given y0m), then the fused step,
+ *                                            in either form.
  * Every launch reads the model that is resident at that moment: a mpcqp_set_model between two periods is picked up
  * with nothing else to call.
  *
@@ -320,10 +350,15 @@ int mpcqp_kf_predict_device(mpcqp_handle h, double* xhat0, const double* u0, con
  * handle keeps what it had).  Called again with P0 == NULL (same nym) it replaces Q̂ and R̂ and keeps P̂ and K̂ -- the Q̂, R̂
  * keywords of setmodel!.  A later mpcqp_kf_set returns the handle to the steady gain.
  * mpcqp_kf_set_state_covariance: P (nx̂,nx̂,B) replaces P̂ -- setstate!(estim, x̂, P̂).
- * mpcqp_kf_status: out [B], 0 or 2.  2: the last correction of that estimator was dropped because M̂ was not positive
- * definite or not finite, or the new P̂ / K̂ was not finite (where the reference's cholesky! throws): P̂ and K̂ keep their
- * values, and so does P̂ in the prediction of that period; the next correction that succeeds puts 0 back.  The other
- * estimators of the batch and the LinMPC step statuses are unaffected.
+ * mpcqp_kf_status: out [B], what became of the last correction attempt of each estimator (MPCQP_ERR_ORDER on a steady
+ * gain, which keeps no status):
+ *       0  done.
+ *       1  skipped for a missing measurement (see above): P̂ and K̂ keep their bits -- MPCQP_GET_KF_GAIN goes on showing
+ *          the K̂ of the last correction that ran -- and the prediction of that period runs, P̂ <- Â P̂ Â' + Q̂.
+ *       2  dropped because M̂ was not positive definite or not finite, or the new P̂ / K̂ was not finite (where the
+ *          reference's cholesky! throws): P̂ and K̂ keep their values, and so does P̂ in the prediction of that period --
+ *          only status 2 holds the covariance prediction back; the next correction that succeeds puts 0 back.
+ * The other estimators of the batch and the LinMPC step statuses are unaffected.
  * mpcqp_kf_lanes_per_estimator: 0 on a steady gain, else 16 (max(nx̂, nym) <= 16: four estimators per wavefront) or 64. */
 int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* Rhat, const double* P0,
                              const int32_t* i_ym, int32_t nym);

@@ -186,7 +186,8 @@ end
 # ------------------------------------------------------------------------------------------------
 # Time-varying KalmanFilter behind the batch (include/mpcqp.h, "the time-varying KalmanFilter"): P̂ and K̂(k) live on the
 # device and follow mpcqp_kf_correct / mpcqp_kf_predict / mpcqp_loop_device, on the model that is resident at that moment
-# (a setmodel! -> mpcqp_set_model between two periods needs nothing else).  direct = true only.  Call sequence = the one of
+# (a setmodel! -> mpcqp_set_model between two periods needs nothing else).  Both forms: `direct` of the estimators goes to
+# mpcqp_kf_set_direct, and update_kalmanfilter! is updatestate! of the predictor form.  Call sequence = the one of
 # modelpredictivecontrol.jl_amd/api.py (BatchLinMPC.setestimator(covariances=...)), which the GPU tests drive; these ccalls
 # have not been run (no Julia on the build machines).
 import ModelPredictiveControl: KalmanFilter
@@ -194,21 +195,45 @@ import ModelPredictiveControl: KalmanFilter
 "Q̂, R̂, P̂ of the batch's KalmanFilters to the device; `keepP = true` replaces Q̂ and R̂ only (the keywords of setmodel!)."
 function push_kalmanfilter!(b::BatchLinMPC; keepP::Bool=false)
     es = [c.estim for c in b.mpcs]
-    all(e -> e isa KalmanFilter && e.direct, es) || throw(ArgumentError("time-varying filter: KalmanFilter with direct=true"))
+    all(e -> e isa KalmanFilter && e.direct == es[1].direct, es) || throw(ArgumentError("time-varying filter: KalmanFilters of one form (direct)"))
     stack3(f) = cat((Matrix{Float64}(f(e)) for e in es)...; dims=3)          # (n, n, B)
     Q̂, R̂, P̂ = stack3(e -> e.cov.Q̂), stack3(e -> e.cov.R̂), stack3(e -> e.cov.P̂)
     i_ym = Cint.(es[1].i_ym .- 1)                                            # 0-based
     GC.@preserve Q̂ R̂ P̂ i_ym check(ccall((:mpcqp_kf_set_covariances, lib), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Cint),
         b.h, Q̂, R̂, keepP ? C_NULL : pointer(P̂), i_ym, length(i_ym)))
+    set_direct!(b, es[1].direct)
     return b
 end
+
+"`direct` of the batch's estimators: true filter form, false predictor form (mpcqp_loop_device: step, correction, prediction)."
+set_direct!(b::BatchLinMPC, direct::Bool) =
+    check(ccall((:mpcqp_kf_set_direct, lib), Cint, (Ptr{Cvoid}, Int32), b.h, direct ? 1 : 0))
+
+"""
+updatestate! of a direct=false batch: correction with y0m (nym, B), then prediction with u0 (nu, B), in place on x̂0 (nx̂, B).
+`y0m = nothing` skips every correction; a NaN in a column of y0m skips that estimator's (status 1 in pull_kalmanfilter).
+The K̂ behind a steady gain is the FILTER-form gain in both forms (include/mpcqp.h).
+"""
+function update_kalmanfilter!(b::BatchLinMPC, x̂0::Matrix{Float64}, u0::Matrix{Float64}, y0m::Union{Nothing,Matrix{Float64}},
+                              d0::Union{Nothing,Matrix{Float64}}=nothing)
+    GC.@preserve x̂0 u0 y0m d0 check(ccall((:mpcqp_kf_update, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        b.h, x̂0, u0, y0m === nothing ? C_NULL : pointer(y0m), d0 === nothing ? C_NULL : pointer(d0)))
+    return x̂0
+end
+
+"The same with device pointers, asynchronous on `stream` (y0m, d0: C_NULL allowed as above)."
+update_kalmanfilter_device!(b::BatchLinMPC, x̂0::Ptr{Float64}, u0::Ptr{Float64}, y0m::Ptr{Float64}, d0::Ptr{Float64},
+                            stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:mpcqp_kf_update_device, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}), b.h, x̂0, u0, y0m, d0, stream))
 
 "setstate!(estim, x̂, P̂) for the batch: P (nx̂, nx̂, B)."
 set_state_covariance!(b::BatchLinMPC, P::Array{Float64,3}) =
     check(ccall((:mpcqp_kf_set_state_covariance, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), b.h, P))
 
-"P̂ (nx̂, nx̂, B), K̂ (nx̂, nym, B) and the per-estimator status (0, or 2: the last correction was dropped) back into Julia."
+"P̂ (nx̂, nx̂, B), K̂ (nx̂, nym, B) and the per-estimator status (0 done, 1 skipped for a missing measurement, 2 dropped) back into Julia."
 function pull_kalmanfilter(b::BatchLinMPC)
     e = b.mpcs[1].estim
     nx̂, nym, B = e.nx̂, e.nym, length(b.mpcs)

@@ -39,6 +39,7 @@ EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_cre
            "mpcqp_get", "mpcqp_last_step_ms", "mpcqp_last_condense_ms", "mpcqp_last_predmat_ms", "mpcqp_kf_set",
            "mpcqp_kf_correct", "mpcqp_kf_predict", "mpcqp_kf_correct_device", "mpcqp_kf_predict_device",
            "mpcqp_kf_set_covariances", "mpcqp_kf_set_state_covariance", "mpcqp_kf_status", "mpcqp_kf_lanes_per_estimator",
+           "mpcqp_kf_set_direct", "mpcqp_kf_update", "mpcqp_kf_update_device",
            "mpcqp_set_output_weight_blocks", "mpcqp_set_dense_weights", "mpcqp_set_custom_constraints", "mpcqp_set_custom_bounds",
            "mpcqp_set_flags", "mpcqp_set_iteration_limit", "mpcqp_set_transcription", "mpcqp_transcription_supported", "mpcqp_set_current_setpoint", "mpcqp_prepare", "mpcqp_kernel_kind", "mpcqp_lds_bytes", "mpcqp_row_groups", "mpcqp_step_consts_builds", "mpcqp_prebuild",
            "mpcqp_last_build_error", "mpcqp_multi_create", "mpcqp_multi_destroy", "mpcqp_multi_ndev",
@@ -172,6 +173,9 @@ def load_library(path: str | None = None):
     lib.mpcqp_kf_set_state_covariance.argtypes = [C.c_void_p, C.c_void_p]
     lib.mpcqp_kf_status.argtypes = [C.c_void_p, C.c_void_p]
     lib.mpcqp_kf_lanes_per_estimator.argtypes = [C.c_void_p]
+    lib.mpcqp_kf_set_direct.argtypes = [C.c_void_p, C.c_int32]
+    lib.mpcqp_kf_update.argtypes = [C.c_void_p] * 5
+    lib.mpcqp_kf_update_device.argtypes = [C.c_void_p] * 6
     lib.mpcqp_set_current_setpoint.argtypes = [C.c_void_p, C.c_void_p]
     lib.mpcqp_prepare.argtypes = [C.c_void_p]
     lib.mpcqp_kernel_kind.argtypes = [C.c_void_p]
@@ -419,7 +423,8 @@ class Handle:
         return self.get(GET_KF_GAIN).transpose(0, 2, 1).copy()
 
     def kf_status(self):
-        """(B,) int32: 0, or 2 where the last covariance correction was dropped (include/mpcqp.h)."""
+        """(B,) int32, what became of the last correction attempt: 0 done, 1 skipped for a missing measurement (P̂ and K̂ keep
+        their bits, the prediction runs), 2 dropped (include/mpcqp.h)."""
         out = np.empty(self.B, np.int32)
         _chk(self.lib, self.lib.mpcqp_kf_status(self.h, _ptr(out)))
         return out
@@ -431,10 +436,16 @@ class Handle:
             _chk(self.lib, n)
         return n
 
+    def kf_set_direct(self, direct):
+        """True (default): filter form; False: predictor form -- loop_device then runs step, correction, prediction.  The
+        gain stays the filter-form gain in both forms (include/mpcqp.h)."""
+        _chk(self.lib, self.lib.mpcqp_kf_set_direct(self.h, 1 if direct else 0))
+
     def kf_correct(self, xhat0, y0m, d0=None):
-        """x̂0 += K̂ (y0m - Ĉm x̂0 - D̂dm d0), in place on the (B,nx̂) host array."""
+        """x̂0 += K̂ (y0m - Ĉm x̂0 - D̂dm d0), in place on the (B,nx̂) host array.  A member whose y0m row holds a NaN keeps
+        its x̂0 (missed correction); y0m=None: every member misses."""
         assert xhat0.dtype == np.float64 and xhat0.flags.c_contiguous
-        y, dd = _f64(y0m), (None if d0 is None else _f64(d0))
+        y, dd = (None if y0m is None else _f64(y0m)), (None if d0 is None else _f64(d0))
         _chk(self.lib, self.lib.mpcqp_kf_correct(self.h, _ptr(xhat0), _ptr(y), _ptr(dd)))
 
     def kf_predict(self, xhat0, u0, d0=None):
@@ -442,6 +453,17 @@ class Handle:
         assert xhat0.dtype == np.float64 and xhat0.flags.c_contiguous
         u, dd = _f64(u0), (None if d0 is None else _f64(d0))
         _chk(self.lib, self.lib.mpcqp_kf_predict(self.h, _ptr(xhat0), _ptr(u), _ptr(dd)))
+
+    def kf_update(self, xhat0, u0, y0m=None, d0=None):
+        """Correction, then prediction (`updatestate!` of a direct=false estimator), in place on the (B,nx̂) host array;
+        bit-equal to kf_correct followed by kf_predict.  y0m=None is the reference's `ym = nothing`: prediction only."""
+        assert xhat0.dtype == np.float64 and xhat0.flags.c_contiguous
+        u, y, dd = _f64(u0), (None if y0m is None else _f64(y0m)), (None if d0 is None else _f64(d0))
+        _chk(self.lib, self.lib.mpcqp_kf_update(self.h, _ptr(xhat0), _ptr(u), _ptr(y), _ptr(dd)))
+
+    def kf_update_device(self, xhat0, u0, y0m=0, d0=0, stream=0):
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _chk(self.lib, self.lib.mpcqp_kf_update_device(self.h, v(xhat0), v(u0), v(y0m), v(d0), v(stream)))
 
     def kf_correct_device(self, xhat0, y0m, d0=0, stream=0):
         v = lambda p: C.c_void_p(int(p)) if p else None
@@ -896,13 +918,18 @@ class BatchLinMPC:
 
         `covariances=dict(Qhat=…, Rhat=…, P0=…)` attaches the time-varying `KalmanFilter` instead (kalman.jl:1235-1290):
         Q̂ (nx̂,nx̂), R̂ (nym,nym), P̂_0 (nx̂,nx̂), each shared or with a leading batch axis.  P̂ and K̂(k) then live on the
-        device and follow `preparestate` / `updatestate` (and `setmodel`: the recursion reads the current model)."""
-        if not direct:
-            raise NotImplementedError("direct=False (predictor form) is not built: the estimator steps assume direct=True")
+        device and follow `preparestate` / `updatestate` (and `setmodel`: the recursion reads the current model).
+
+        `direct=False` is the predictor form (kalman.jl:112): `preparestate` does nothing, `moveinput` works on x̂ₖ₋₁(k) and
+        `updatestate(u, ym, d)` corrects and then predicts.  Khat is the FILTER-form gain in both forms (what
+        `steady_kalman_gain` returns): the library applies x̂ <- Â (x̂ + K̂ v) + ... like `update_estimate!`.
+
+        In both forms a member whose `ym` row holds a NaN, or every member when `ym` is None, skips the correction of that
+        period (RuntimeWarning with the count); its prediction runs."""
         if covariances is not None:
             if Khat is not None:
                 raise ValueError("give either Khat (SteadyKalmanFilter) or covariances (KalmanFilter)")
-            return self.setkalmanfilter(**covariances, i_ym=i_ym, xhat0=xhat0)
+            return self.setkalmanfilter(**covariances, i_ym=i_ym, xhat0=xhat0, direct=direct)
         if Khat is None:
             raise ValueError("setestimator needs Khat or covariances")
         self.kf_timevarying = False
@@ -910,9 +937,22 @@ class BatchLinMPC:
         Khat = np.asarray(Khat, float)
         if Khat.shape != (self.B, self.nxh, len(self.i_ym)):
             raise ValueError("Khat size must be (B, nx̂, nym)")
+        self._set_direct(direct)
         self.hd.kf_set(colmajor(Khat), self.i_ym)
         self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
         return self
+
+    def _set_direct(self, direct):
+        """The form of the estimator about to be attached, settled before the estimator itself goes to the device.  The
+        handle's flag (default: filter form) survives its setters, so it is told about a change only.  A handle without
+        mpcqp_kf_set_direct cannot run the predictor form: NotImplementedError, and nothing has been sent to it."""
+        direct = bool(direct)
+        if direct != getattr(self, "_hd_direct", True):
+            if not hasattr(self.hd, "kf_set_direct"):
+                raise NotImplementedError("direct=False (predictor form): this handle has no mpcqp_kf_set_direct")
+            self.hd.kf_set_direct(direct)
+            self._hd_direct = direct
+        self.direct = direct
 
     def _cov(self, M, n, name):
         a = np.asarray(M, float)
@@ -926,11 +966,11 @@ class BatchLinMPC:
 
     def setkalmanfilter(self, Qhat, Rhat, P0, i_ym=None, xhat0=None, direct=True):
         """The time-varying `KalmanFilter` (see `setestimator(covariances=…)`); keyword names are the reference's Q̂, R̂, P̂_0."""
-        if not direct:
-            raise NotImplementedError("direct=False (predictor form) is not built: the estimator steps assume direct=True")
         self.i_ym = np.arange(self.ny) if i_ym is None else np.asarray(i_ym, int)
         nym = len(self.i_ym)
-        self.hd.kf_set_covariances(self._cov(Qhat, self.nxh, "Q̂"), self._cov(Rhat, nym, "R̂"), self._cov(P0, self.nxh, "P̂_0"), self.i_ym)
+        Qhat, Rhat, P0 = self._cov(Qhat, self.nxh, "Q̂"), self._cov(Rhat, nym, "R̂"), self._cov(P0, self.nxh, "P̂_0")
+        self._set_direct(direct)
+        self.hd.kf_set_covariances(Qhat, Rhat, P0, self.i_ym)
         self.kf_timevarying = True
         self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
         return self
@@ -953,20 +993,36 @@ class BatchLinMPC:
         self.xhat0 = _f64(self._bc(xhat, self.nxh, "x̂") - self.xhop).copy()
         return self
 
+    def _y0m(self, ym):
+        """y0m of a period, or None for `ym = nothing`; warns once when members miss the correction (kalman.jl:245-251)."""
+        y0m = None if ym is None else self._bc(ym, len(self.i_ym), "ym") - self.yop[:, self.i_ym]
+        n = self.B if y0m is None else int(np.isnan(y0m).any(axis=1).sum())
+        if n:
+            warnings.warn("NaN values in the Kalman filter measurements ym: skipping correction step "
+                          f"({n} of {self.B} estimators)", RuntimeWarning)
+        return y0m
+
     def preparestate(self, ym, d=None):
         """`preparestate!` (src/estimator/execute.jl:334-345 -> correct_estimate_obsv!,
-        kalman.jl:284-295): x̂0 += K̂ (y0m - Ĉm x̂0 - D̂dm d0).  Returns x̂ = x̂0 + x̂op."""
-        y0m = self._bc(ym, len(self.i_ym), "ym") - self.yop[:, self.i_ym]
+        kalman.jl:284-295): x̂0 += K̂ (y0m - Ĉm x̂0 - D̂dm d0).  Returns x̂ = x̂0 + x̂op.  Members with a NaN in `ym` (all of
+        them with ym=None) keep their x̂0.  Predictor form (direct=False): nothing to do, no device call."""
+        if not getattr(self, "direct", True):
+            return self.xhat0 + self.xhop
+        y0m = self._y0m(ym)
         d0 = None if self.nd == 0 else self._bc(d, self.nd, "d") - self.dop
-        self.hd.kf_correct(self.xhat0, y0m, d0)
+        self.hd.kf_correct(self.xhat0, y0m, d0)       # (y0m None: a time-varying filter records the miss, status 1)
         return self.xhat0 + self.xhop
 
     def updatestate(self, u, ym=None, d=None):
         """`updatestate!` (src/estimator/execute.jl:374-386 -> predict_estimate_obsv!,
-        kalman.jl:298-309): x̂0 <- Â x̂0 + B̂u u0 + B̂d d0 + f̂op - x̂op."""
+        kalman.jl:298-309): x̂0 <- Â x̂0 + B̂u u0 + B̂d d0 + f̂op - x̂op.  Predictor form (direct=False): the correction with
+        `ym` first (kalman.jl:276-281, 520-525; ym=None or NaN rows: skipped), then the prediction."""
         u0 = self._bc(u, self.nu, "u") - self.uop
         d0 = None if self.nd == 0 else self._bc(d, self.nd, "d") - self.dop
-        self.hd.kf_predict(self.xhat0, u0, d0)
+        if getattr(self, "direct", True):
+            self.hd.kf_predict(self.xhat0, u0, d0)
+        else:
+            self.hd.kf_update(self.xhat0, u0, self._y0m(ym), d0)
         return self.xhat0 + self.xhop
 
     # -- per-step ---------------------------------------------------------------------------

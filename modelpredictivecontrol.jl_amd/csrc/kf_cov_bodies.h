@@ -7,8 +7,17 @@
 //       P̂Ĉm' = P̂ Ĉm';  M̂ = Ĉm (P̂Ĉm') + R̂;  K̂ = (P̂Ĉm') M̂⁻¹;  P̂ <- (I - K̂ Ĉm) P̂
 //   predict_estimate_kf!  src/estimator/kalman.jl:1275-1290  -> mode bit 1 (COV_PREDICT)
 //       P̂ <- Â (P̂ Â') + Q̂
-// in that order of operations.  The recursion does not depend on the data, so it runs as a kernel of its own ahead of
-// the step on the same stream and hands K̂(k) to every step kernel through the gain buffer they already read.
+// in that order of operations.  The recursion depends on WHICH measurements are missing and on nothing else in the data,
+// so it runs as a kernel of its own ahead of the step on the same stream and hands K̂(k) to every step kernel through the
+// gain buffer they already read.
+//
+// Missed corrections (kalman.jl:478-484, "NaN values in the Kalman filter measurements ym: skipping correction step"): an
+// estimator whose row of CovArgs::y0m holds a NaN -- or every estimator of a COV_NO_YM launch -- keeps P̂ and K̂ bit for bit
+// and gets COV_MISSED.  The prediction of that period runs, from P̂(k|k-1).  Every lane reads the nym entries of its own
+// estimator's row (the same addresses within a DPP row here, within the wavefront in the wide family: no cross-lane
+// operation, no register held beyond the flag); the products of the correction are computed all
+// the same and discarded by the selects that already serve the drop policy, so the other estimators of the wavefront see
+// the same instruction stream whoever misses.
 //
 // Symmetry: the corrected covariance is stored as ½ (P̂ + P̂') (what oracle/mhe.py keeps; the reference takes
 // Hermitian(P̂, :L)), the predicted one as computed -- Â P̂ Â' + Q̂ of a symmetric P̂ is symmetric up to rounding, and the
@@ -54,6 +63,12 @@ MPCQP_HD void kf_cov_body(W& w, const CovArgs& a, int mode, int wave_id) {
         sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; P[c] = (r < nx && c < nx) ? Pb[c * nx + r] : 0.0; });
         bool dropped = false, changed = false;
         if (mode & COV_CORRECT) {
+            // any(isnan, y0m) of this estimator (Inf is a measurement)
+            bool missed = false;
+            if (a.y0m) {
+                const double* yb = a.y0m + (size_t)b * nym;
+                for (int i = 0; i < nym; ++i) missed = missed || yb[i] != yb[i];
+            }
             sfor<NX>([&](auto ic) {
                 constexpr int c = decltype(ic)::v;
                 S[c] = (r < nym && c < nx) ? Cb[my + ny * c] : 0.0;                           // Ĉm (row = measured output)
@@ -77,12 +92,15 @@ MPCQP_HD void kf_cov_body(W& w, const CovArgs& a, int mode, int wave_id) {
             });
             const bool fin_all = w.rmin(fin) > 0.5;          // (every lane takes part: not behind `good &&`)
             good = good && fin_all;
-            sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; P[c] = good ? M[c] : P[c]; });
-            if (live && good && r < nx)
+            const bool apply = good && !missed;
+            sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; P[c] = apply ? M[c] : P[c]; });
+            if (live && apply && r < nx)
                 sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; if (c < nym) Kb[c * nx + r] = X[c]; });
-            if (live && r == 0) a.status[b] = good ? COV_OK : COV_DROPPED;
-            dropped = !good;
-            changed = good;
+            if (live && r == 0) a.status[b] = missed ? COV_MISSED : good ? COV_OK : COV_DROPPED;
+            dropped = !good && !missed;
+            changed = apply;
+        } else if (mode & COV_NO_YM) {
+            if (live && r == 0) a.status[b] = COV_MISSED;
         } else if (mode & COV_PREDICT) {
             dropped = a.status[b] == COV_DROPPED;
         }

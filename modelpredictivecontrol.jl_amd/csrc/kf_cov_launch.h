@@ -11,8 +11,12 @@
 namespace mpcqp {
 namespace kf {
 
-enum { COV_CORRECT = 1, COV_PREDICT = 2 };      // mode bits of one launch (3: both, P̂(k|k) stays in registers)
-enum { COV_OK = 0, COV_DROPPED = 2 };           // per-estimator status
+// mode bits of one launch (3: both, P̂(k|k) stays in registers).  COV_NO_YM (without COV_CORRECT): the period has no
+// measurement at all (ym = nothing) -- every estimator's correction is missed, its status becomes COV_MISSED
+enum { COV_CORRECT = 1, COV_PREDICT = 2, COV_NO_YM = 4 };
+// per-estimator status: what became of the last correction attempt.  COV_MISSED: skipped for a missing measurement (a NaN
+// in the estimator's y0m row); P̂ and K̂ keep their bits and, unlike COV_DROPPED, the prediction of that period runs
+enum { COV_OK = 0, COV_MISSED = 1, COV_DROPPED = 2 };
 
 // Everything in ABI layout (column-major inside an estimator), read where mpcqp_set_model / mpcqp_kf_set_covariances
 // left it: the launch sees the model that is resident at that moment.
@@ -22,10 +26,12 @@ struct CovArgs {
     const double *Q, *R;         // [B][nx*nx], [B][nym*nym]
     double* P;                   // [B][nx*nx]  P̂, in and out
     double* K;                   // [B][nym][nx] K̂ (KfParams::Khat / StepIO::kf_K), out of a correction
-    int32_t* status;             // [B] COV_OK / COV_DROPPED
+    int32_t* status;             // [B] COV_OK / COV_MISSED / COV_DROPPED
     int B, nx, ny, nym;
     int NX;                      // register columns: mhe::register_columns_for(max(nx, nym))
     int nwaves;                  // wavefronts launched (each loops over groups of GPW estimators)
+    const double* y0m;           // [B][nym] measurements of a COV_CORRECT launch (any(isnan) of a row: that estimator's
+                                 // correction is missed), or null: every correction runs
 };
 
 __attribute__((weak)) hipError_t launch_kf_cov(const CovArgs& a, int mode, hipStream_t st);

@@ -4126,6 +4126,61 @@ struct Step {
     static constexpr int ST_OPTIMAL = 0, ST_ITERATION_LIMIT = 1, ST_ERROR = 2;
 };
 
+// The estimator correction of a fused control period (mpcqp_loop_device) on x̂0 in LDS, shared by step_body and the stage
+// kernel (ms_bodies.h): x̂0 += K̂ (y0m - Ĉm x̂0 - D̂dm d0)  (correct_estimate_obsv!, src/estimator/kalman.jl:284-295; same
+// arithmetic order as kf_correct_lane).  Filter form (direct = true): x̂0 in LDS is corrected in place and the step works
+// on it.  Predictor form (StepIO::kf_late, kalman.jl:276-281: step, correction, prediction): the step must see x̂0 as it
+// stands, and neither x̂0 nor y0m(k) changes while it runs, so the correction is still COMPUTED here, once, but parked in
+// xhat0_out instead of LDS; kf_restage_late brings it back behind the step, directly in front of the prediction.  Nothing
+// of the estimator stays live across the Newton iteration that way, and the kernel holds one copy of this code (a second
+// call in the epilogue cost the step kernels 5 % more instructions and scalar spills in the iteration).
+// A NaN in the controller's y0m row is a missed measurement (kalman.jl:245-251): x̂0 keeps its bits.  Every lane that holds
+// a row of x̂0 reads the whole y0m row, so the test costs no load and needs no reduction.
+template <class W, class DM>
+MPCQP_HD void kf_correct_lds(W& w, const DM& d, const Model& m, const StepIO& io, int b, double* xh) {
+    const int nx = d.nxh, ny = d.ny, nd = d.nd;
+    const double* Cm = m.C + (size_t)b * ny * nx;
+    const double* K = io.kf_K + (size_t)b * io.kf_nym * nx;
+    double acc[4];                                     // rows i = lane + 64 q (nx̂ <= 256); unrolled: acc stays in registers
+    bool missed = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = w.lane + WAVE * q;
+        if (i < nx) {
+            double a_ = xh[i];
+            for (int mm = 0; mm < io.kf_nym; ++mm) {
+                const int a = io.kf_iym[mm];
+                double v = io.kf_y0m[(size_t)b * io.kf_nym + mm];
+                missed = missed || v != v;
+                for (int k = 0; k < nx; ++k) v -= Cm[a + ny * k] * xh[k];
+                for (int e = 0; e < nd; ++e) v -= m.Dd[(size_t)b * ny * nd + a + ny * e] * io.d0[(size_t)b * nd + e];
+                a_ += K[i + nx * mm] * v;
+            }
+            acc[q] = a_;
+        }
+    }
+    w.sync();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = w.lane + WAVE * q;
+        if (i < nx) {
+            const double xc = missed ? xh[i] : acc[q];
+            if (!io.kf_late) xh[i] = xc;
+            if (io.kf_late || !io.kf_predict) io.xhat0_out[(size_t)b * nx + i] = xc;
+        }
+    }
+    w.sync();
+}
+
+// Predictor form, behind the step: the corrected x̂0 that kf_correct_lds parked in xhat0_out goes into LDS, where the
+// prediction reads it (every lane reads back what it wrote itself: same rows i = lane + 64 q).
+template <class W, class DM>
+MPCQP_HD void kf_restage_late(W& w, const DM& d, const StepIO& io, int b, double* xh) {
+    const int nx = d.nxh;
+    for (int i = w.lane; i < nx; i += WAVE) xh[i] = io.xhat0_out[(size_t)b * nx + i];
+    w.sync();
+}
+
 template <class W, class DM>
 MPCQP_HD void step_body(W& w, const DM& d, const Model& m, const StepIO& io, int b, double* sm) {
     const long long t_in_ = Step<W, DM>::clock64_();
@@ -4137,36 +4192,13 @@ MPCQP_HD void step_body(W& w, const DM& d, const Model& m, const StepIO& io, int
     // x̂0 of this period into LDS; with kf_y0m the SteadyKalmanFilter correction first
     // (correct_estimate_obsv!, src/estimator/kalman.jl:284-295; same arithmetic order as kf_correct_lane)
     {
-        const int nx = d.nxh, ny = d.ny, nd = d.nd;
+        const int nx = d.nxh;
         double* xh = sm + qp.c.xh;
         if constexpr (SetupLoads<DM>::on) { if (w.lane < nx) xh[w.lane] = pre.x0; }
         else
             for (int i = w.lane; i < nx; i += WAVE) xh[i] = io.xhat0[(size_t)b * nx + i];
         w.sync();
-        if (io.kf_y0m) {
-            const double* Cm = m.C + (size_t)b * ny * nx;
-            const double* K = io.kf_K + (size_t)b * io.kf_nym * nx;
-            double acc[4];                                     // rows i = lane + 64 q (nx̂ <= 256)
-            int nq = 0;
-            for (int i = w.lane; i < nx; i += WAVE, ++nq) {
-                double a_ = xh[i];
-                for (int mm = 0; mm < io.kf_nym; ++mm) {
-                    const int a = io.kf_iym[mm];
-                    double v = io.kf_y0m[(size_t)b * io.kf_nym + mm];
-                    for (int k = 0; k < nx; ++k) v -= Cm[a + ny * k] * xh[k];
-                    for (int e = 0; e < nd; ++e) v -= m.Dd[(size_t)b * ny * nd + a + ny * e] * io.d0[(size_t)b * nd + e];
-                    a_ += K[i + nx * mm] * v;
-                }
-                acc[nq] = a_;
-            }
-            w.sync();
-            nq = 0;
-            for (int i = w.lane; i < nx; i += WAVE, ++nq) {
-                xh[i] = acc[nq];
-                if (!io.kf_predict) io.xhat0_out[(size_t)b * nx + i] = acc[nq];
-            }
-            w.sync();
-        }
+        if (io.kf_y0m) kf_correct_lds(w, d, m, io, b, xh);
     }
     Step<W, DM> st(qp);
     const long long t_b0_ = Step<W, DM>::clock64_();
@@ -4201,6 +4233,8 @@ MPCQP_HD void step_body(W& w, const DM& d, const Model& m, const StepIO& io, int
         qp.E_apply(st.z, tY);
         for (int r = w.lane; r < d.nY; r += WAVE) io.Yhat0[(size_t)b * d.nY + r] += tY[r];      // same lane parked F[r]
     }
+    // predictor form: the correction with y0m(k) takes effect now, in front of the prediction
+    if (io.kf_late) kf_restage_late(w, d, io, b, sm + st.c.xh);
     if (io.kf_predict) {
         // updatestate! (predict_estimate_obsv!, kalman.jl:298-309) with the input just computed:
         // x̂0 <- Â x̂0 + B̂u u0 + B̂d d0 + (f̂op - x̂op)
@@ -4291,15 +4325,17 @@ MPCQP_HD inline void kf_correct_lane(const Dims& d, const Model& m, const KfPara
     const double* Cm = m.C + (size_t)slot * ny * nx;            // (ny,nx̂) col-major
     const double* K = kf.Khat + (size_t)slot * kf.nym * nx;     // (nx̂,nym) col-major
     double acc = x[i];
+    bool missed = false;                                        // any(isnan, y0m): the lane stores nothing (kalman.jl:245-251)
     for (int mm = 0; mm < kf.nym; ++mm) {
         const int a = kf.i_ym[mm];
         double v = y0m[(size_t)slot * kf.nym + mm];             // innovation y0m - Ĉm x̂0 - D̂dm d0
+        missed = missed || v != v;
         for (int k = 0; k < nx; ++k) v -= Cm[a + ny * k] * x[k];
         for (int e = 0; e < nd; ++e) v -= m.Dd[(size_t)slot * ny * nd + a + ny * e] * d0[(size_t)slot * nd + e];
         acc += K[i + nx * mm] * v;
     }
     // (all loads of the wave above precede this store in program order)
-    xhat0[(size_t)slot * nx + i] = acc;
+    if (!missed) xhat0[(size_t)slot * nx + i] = acc;
 }
 
 MPCQP_HD inline void kf_predict_lane(const Dims& d, const Model& m, int slot, int i, const double* xin,

@@ -69,6 +69,9 @@ struct mpcqp_handle_s {
     bool kf_tv = false;
     DBuf kf_Q, kf_R, kf_P, kf_st;
     int kf_NX = 0, kf_waves = 0;   // register columns and persistent grid of the covariance kernel
+    // mpcqp_kf_set_direct: 1 filter form (mpcqp_loop_device: correction, step, prediction), 0 predictor form (step, correction,
+    // prediction).  A property of the handle: the setters of the gain and of the covariances leave it alone
+    int kf_direct = 1;
     // MultipleShooting transcription (mpcqp_set_transcription): the stage-structured kernel of ms_bodies.h
     int transcription = MPCQP_SINGLE_SHOOTING;
     bool stage_only = false;         // nZ~ > 256: only the stage-structured kernel can take this handle (nothing is condensed)
@@ -649,8 +652,9 @@ int mpcqp_transcription_supported(mpcqp_handle h) {
 }
 
 // One launch of the covariance / gain recursion of a time-varying handle (kf_kernels.hip) on the model that is resident
-// now: mode bit 0 the correction (K̂(k), P̂(k|k)), bit 1 the prediction (P̂(k+1|k)).
-static int kf_cov_launch(mpcqp_handle h, int mode, hipStream_t st) {
+// now: mode bit 0 the correction (K̂(k), P̂(k|k)), bit 1 the prediction (P̂(k+1|k)), bit 2 a period without measurements.
+// y0m (device, [B][nym]) of a correction: the estimators whose row holds a NaN miss it.
+static int kf_cov_launch(mpcqp_handle h, int mode, const double* y0m, hipStream_t st) {
     if (!kf::kf_cov_available()) return MPCQP_ERR_UNSUPPORTED;
     ON_DEVICE(h);
     const Dims& d = h->d;
@@ -660,6 +664,7 @@ static int kf_cov_launch(mpcqp_handle h, int mode, hipStream_t st) {
     a.P = (double*)h->kf_P.p; a.K = (double*)h->kf_K.p; a.status = (int32_t*)h->kf_st.p;
     a.B = d.B; a.nx = d.nxh; a.ny = d.ny; a.nym = h->kf.nym;
     a.NX = h->kf_NX; a.nwaves = h->kf_waves;
+    a.y0m = y0m;
     HIPCHK(kf::launch_kf_cov(a, mode, st));
     return MPCQP_OK;
 }
@@ -694,6 +699,7 @@ static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* l
     if (y0m) {
         io.kf_K = h->kf.Khat; io.kf_iym = h->kf.i_ym; io.kf_nym = h->kf.nym;
         io.kf_y0m = y0m; io.xhat0_out = xhat0_out; io.kf_predict = predict;
+        io.kf_late = h->kf_direct ? 0 : 1;
     }
     {       // what the convergence test of every solve saw last (mpcqp_get MPCQP_GET_AUDIT)
         int rc = dev_alloc(h, h->audit, (size_t)d.B * 4 * sizeof(double));
@@ -781,11 +787,13 @@ int mpcqp_loop_device(mpcqp_handle h, double* xhat0, const double* y0m, const do
     if (!h || !y0m || !xhat0) return MPCQP_ERR_NULL;
     if (!h->have_kf) return MPCQP_ERR_ORDER;
     if (h->d.nxh > 4 * WAVE) return MPCQP_ERR_UNSUPPORTED;
-    if (h->kf_tv) {     // K̂(k) and P̂(k+1|k) first: the recursion is data independent (a refused step leaves P̂ one period ahead)
+    // K̂(k) and P̂(k+1|k) first, in either form: the recursion depends on which measurements are missing and on nothing else
+    // (a refused step leaves P̂ one period ahead)
+    if (h->kf_tv) {
         if (!lastu0 || !Ry || !Ztilde || !u0 || !status || (h->d.nd > 0 && (!d0 || !Dhat0))) return MPCQP_ERR_NULL;
         if (!h->have_model || !h->have_weights) return MPCQP_ERR_ORDER;
         if (uses_stage_kernel(h) && ms_unsupported(h)) return MPCQP_ERR_UNSUPPORTED;
-        int rc = kf_cov_launch(h, kf::COV_CORRECT | kf::COV_PREDICT, (hipStream_t)stream);
+        int rc = kf_cov_launch(h, kf::COV_CORRECT | kf::COV_PREDICT, y0m, (hipStream_t)stream);
         if (rc) return rc;
     }
     return step_device_impl(h, xhat0, lastu0, Ry, Ru, d0, Dhat0, Ztilde, u0, status, iters, Yhat0, stream,
@@ -1033,11 +1041,13 @@ int mpcqp_kf_lanes_per_estimator(mpcqp_handle h) {
 }
 
 int mpcqp_kf_correct_device(mpcqp_handle h, double* xhat0, const double* y0m, const double* d0, void* stream) {
-    if (!h || !xhat0 || !y0m) return MPCQP_ERR_NULL;
+    if (!h || !xhat0) return MPCQP_ERR_NULL;
     if (h->d.nd > 0 && !d0) return MPCQP_ERR_NULL;
     if (!h->have_model || !h->have_kf) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
-    if (h->kf_tv) { int rc = kf_cov_launch(h, kf::COV_CORRECT, (hipStream_t)stream); if (rc) return rc; }
+    if (!y0m)       // ym = nothing: every estimator misses; x̂0, P̂ and K̂ stay, a time-varying handle records status 1
+        return h->kf_tv ? kf_cov_launch(h, kf::COV_NO_YM, nullptr, (hipStream_t)stream) : MPCQP_OK;
+    if (h->kf_tv) { int rc = kf_cov_launch(h, kf::COV_CORRECT, y0m, (hipStream_t)stream); if (rc) return rc; }
     HIPCHK(launch_kf_correct(h->d, h->m, h->kf, xhat0, y0m, d0, (hipStream_t)stream));
     return MPCQP_OK;
 }
@@ -1049,22 +1059,67 @@ int mpcqp_kf_predict_device(mpcqp_handle h, double* xhat0, const double* u0, con
     if (h->d.nxh > 64) return MPCQP_ERR_UNSUPPORTED;
     ON_DEVICE(h);
     HIPCHK(launch_kf_predict(h->d, h->m, xhat0, u0, d0, (hipStream_t)stream));
-    if (h->kf_tv) { int rc = kf_cov_launch(h, kf::COV_PREDICT, (hipStream_t)stream); if (rc) return rc; }
+    if (h->kf_tv) { int rc = kf_cov_launch(h, kf::COV_PREDICT, nullptr, (hipStream_t)stream); if (rc) return rc; }
     return MPCQP_OK;
 }
 
-static int kf_host(mpcqp_handle h, double* xhat0, const double* a, size_t na, const double* d0, bool correct) {
-    if (!h || !xhat0 || !a) return MPCQP_ERR_NULL;
+int mpcqp_kf_set_direct(mpcqp_handle h, int32_t direct) {
+    if (!h) return MPCQP_ERR_NULL;
+    if (direct != 0 && direct != 1) return MPCQP_ERR_ARG;
+    h->kf_direct = direct;
+    return MPCQP_OK;
+}
+
+// updatestate! of a direct = false estimator (kalman.jl:276-281, 520-525): correction, then prediction.  One covariance
+// launch (mode 3: P̂(k|k) stays in registers, bit-equal to modes 1 and 2 in turn), then the two state kernels.
+int mpcqp_kf_update_device(mpcqp_handle h, double* xhat0, const double* u0, const double* y0m, const double* d0, void* stream) {
+    if (!h || !xhat0 || !u0) return MPCQP_ERR_NULL;
+    if (h->d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    if (!h->have_model || !h->have_kf) return MPCQP_ERR_ORDER;
+    if (h->d.nxh > 64) return MPCQP_ERR_UNSUPPORTED;
+    ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (h->kf_tv) {
+        int rc = kf_cov_launch(h, (y0m ? kf::COV_CORRECT : kf::COV_NO_YM) | kf::COV_PREDICT, y0m, st);
+        if (rc) return rc;
+    }
+    if (y0m) HIPCHK(launch_kf_correct(h->d, h->m, h->kf, xhat0, y0m, d0, st));
+    HIPCHK(launch_kf_predict(h->d, h->m, xhat0, u0, d0, st));
+    return MPCQP_OK;
+}
+
+int mpcqp_kf_update(mpcqp_handle h, double* xhat0, const double* u0, const double* y0m, const double* d0) {
+    if (!h || !xhat0 || !u0) return MPCQP_ERR_NULL;
+    if (!h->have_model || !h->have_kf) return MPCQP_ERR_ORDER;
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
     ON_DEVICE(h);
     const size_t B = d.B, sz = sizeof(double);
     int rc = upload(h, h->kf_x, xhat0, B * d.nxh * sz);
-    if (!rc) rc = upload(h, correct ? h->kf_y : h->kf_u, a, B * na * sz);
+    if (!rc) rc = upload(h, h->kf_u, u0, B * d.nu * sz);
+    if (!rc && y0m) rc = upload(h, h->kf_y, y0m, B * (size_t)h->kf.nym * sz);
+    if (!rc && d.nd > 0) rc = upload(h, h->kf_d, d0, B * d.nd * sz);
+    if (rc) return rc;
+    rc = mpcqp_kf_update_device(h, (double*)h->kf_x.p, (const double*)h->kf_u.p, y0m ? (const double*)h->kf_y.p : nullptr,
+                                d.nd > 0 ? (const double*)h->kf_d.p : nullptr, h->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(xhat0, h->kf_x.p, B * d.nxh * sz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
+static int kf_host(mpcqp_handle h, double* xhat0, const double* a, size_t na, const double* d0, bool correct) {
+    if (!h || !xhat0 || (!a && !correct)) return MPCQP_ERR_NULL;      // (a correction without y0m: every estimator misses)
+    const Dims& d = h->d;
+    if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    ON_DEVICE(h);
+    const size_t B = d.B, sz = sizeof(double);
+    int rc = upload(h, h->kf_x, xhat0, B * d.nxh * sz);
+    if (!rc && a) rc = upload(h, correct ? h->kf_y : h->kf_u, a, B * na * sz);
     if (!rc && d.nd > 0) rc = upload(h, h->kf_d, d0, B * d.nd * sz);
     if (rc) return rc;
     const double* dd = d.nd > 0 ? (const double*)h->kf_d.p : nullptr;
-    rc = correct ? mpcqp_kf_correct_device(h, (double*)h->kf_x.p, (const double*)h->kf_y.p, dd, h->stream)
+    rc = correct ? mpcqp_kf_correct_device(h, (double*)h->kf_x.p, a ? (const double*)h->kf_y.p : nullptr, dd, h->stream)
                  : mpcqp_kf_predict_device(h, (double*)h->kf_x.p, (const double*)h->kf_u.p, dd, h->stream);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(xhat0, h->kf_x.p, B * d.nxh * sz, hipMemcpyDeviceToHost, h->stream));

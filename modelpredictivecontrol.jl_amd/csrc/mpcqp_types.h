@@ -42,7 +42,7 @@
 
 // Revision of the kernel sources / device structs: part of the name of cached on-demand
 // specialisations, so that objects built from older sources are never loaded.
-#define MPCQP_KERNEL_REV 14       // 14: one row per lane: a lane's own vector entries handed over in registers across the Newton solve (Step::lane_regs); 13: Model::stepc (per-handle step constants), one load phase for the set-up; 12: matrix-core operands of E'DE in registers (EtDE_add_mfma, register-operand form); 11: on-demand objects compiled with the pragma-unroll threshold lifted (no scratch arrays / flat accesses from eight tile rows on); 10: the row eps >= 0 rides in a Ŷ group (eps_host_group); 9: a blocked step (alpha < 1/2) no longer passes the last-step test; 8: MPCQP_FLAG_KEEP_ITERATE
+#define MPCQP_KERNEL_REV 15       // 15: StepIO::kf_late (predictor-form placement of the fused correction), NaN rule of the estimator corrections; 14: one row per lane: a lane's own vector entries handed over in registers across the Newton solve (Step::lane_regs); 13: Model::stepc (per-handle step constants), one load phase for the set-up; 12: matrix-core operands of E'DE in registers (EtDE_add_mfma, register-operand form); 11: on-demand objects compiled with the pragma-unroll threshold lifted (no scratch arrays / flat accesses from eight tile rows on); 10: the row eps >= 0 rides in a Ŷ group (eps_host_group); 9: a blocked step (alpha < 1/2) no longer passes the last-step test; 8: MPCQP_FLAG_KEEP_ITERATE
 
 namespace mpcqp {
 
@@ -152,12 +152,16 @@ struct StepIO {
                                // returned point is an accepted active-set polish (KKT conditions of the QP checked)
     // optional: the SteadyKalmanFilter steps on both sides of moveinput! inside the same launch
     // (mpcqp_loop_device): kf_y0m != null => preparestate! first, x̂0 += K̂ (y0m - Ĉm x̂0 - D̂dm d0);
-    // kf_predict != 0 => updatestate! last, x̂0 <- Â x̂0 + B̂u u0 + B̂d d0 + (f̂op - x̂op); both write xhat0_out
+    // kf_predict != 0 => updatestate! last, x̂0 <- Â x̂0 + B̂u u0 + B̂d d0 + (f̂op - x̂op); both write xhat0_out.  A NaN in a
+    // controller's y0m row is a missed measurement: its correction is skipped, its prediction runs (kf_correct_lds)
     const double* kf_K;        // [B][nym][nxh]
     const int* kf_iym;         // [nym]
     const double* kf_y0m;      // [B][nym]
     double* xhat0_out;         // [B][nxh]  (may alias xhat0)
     int kf_nym, kf_predict;
+    int kf_late;               // 0: the correction takes effect in front of the step (filter form, direct = true); 1: behind it,
+                               // directly in front of the prediction (predictor form, direct = false: the step sees x̂ as it
+                               // stands; needs kf_y0m, kf_predict and xhat0_out -- kf_correct_lds, mpcqp_bodies.h)
 };
 
 // Packed lower triangle, row-major.  Rows are grouped in fours; every row of group g = i/4 is padded

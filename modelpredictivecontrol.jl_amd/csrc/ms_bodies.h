@@ -335,32 +335,10 @@ struct MsStep : MsBlockBits<HAS_OPT> {
             }
         }
         w.sync();
-        if (io.kf_y0m) {
-            // fused control period (mpcqp_loop_device, round 6 on this kernel too): the SteadyKalmanFilter correction first
-            // (correct_estimate_obsv!, src/estimator/kalman.jl:284-295; same arithmetic order as kf_correct_lane and step_body)
-            double* xh = sm + c.x0;
-            const double* K = io.kf_K + (size_t)b * io.kf_nym * nx;
-            double acc[4];                                     // rows i = lane + 64 q (nx^ <= 256)
-            int nq = 0;
-            for (int i = w.lane; i < nx; i += WAVE, ++nq) {
-                double a_ = xh[i];
-                for (int mm = 0; mm < io.kf_nym; ++mm) {
-                    const int a = io.kf_iym[mm];
-                    double v = io.kf_y0m[(size_t)b * io.kf_nym + mm];
-                    for (int k = 0; k < nx; ++k) v -= gC[a + ny * k] * xh[k];
-                    for (int e = 0; e < nd; ++e) v -= m.Dd[(size_t)b * ny * nd + a + ny * e] * io.d0[(size_t)b * nd + e];
-                    a_ += K[i + nx * mm] * v;
-                }
-                acc[nq] = a_;
-            }
-            w.sync();
-            nq = 0;
-            for (int i = w.lane; i < nx; i += WAVE, ++nq) {
-                xh[i] = acc[nq];
-                if (!io.kf_predict) io.xhat0_out[(size_t)b * nx + i] = acc[nq];
-            }
-            w.sync();
-        }
+        // fused control period (mpcqp_loop_device, round 6 on this kernel too): the estimator correction (kf_correct_lds,
+        // mpcqp_bodies.h: the arithmetic of kf_correct_lane and step_body, NaN rule included) -- in place in the filter form,
+        // parked in xhat0_out until the step is done in the predictor form
+        if (io.kf_y0m) kf_correct_lds(w, d, m, io, b, sm + c.x0);
         for (int j = w.lane; j < Hc; j += WAVE) ctrl[jlt[j]] = j;
         // g_t = B^d d0(k+t) + (f^op - x^op): d0(k) for t = 0, D^0 block t-1 after (transcription.jl:386-389)
         for (int i = w.lane; i < nXt; i += WAVE) {
@@ -1782,6 +1760,8 @@ MPCQP_HD void ms_step_body_t(W& w, const Dims& d, const Model& m, const StepIO& 
             io.Yhat0[(size_t)b * d.nY + r] = acc;
         }
     }
+    // predictor form: the correction with y0m(k) takes effect now, in front of the prediction
+    if (io.kf_late) kf_restage_late(w, d, io, b, sm + st.c.x0);
     if (io.kf_predict) {
         // updatestate! (predict_estimate_obsv!, kalman.jl:298-309) with the input just computed: x^0 <- A^ x^0 + B^u u0 + B^d d0 + (f^op - x^op)
         const int nx = d.nxh, nu = d.nu, nd = d.nd;

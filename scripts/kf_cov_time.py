@@ -1,10 +1,12 @@
 """Timing of the time-varying KalmanFilter of the LinMPC loop on resident data (HIP event timing around the launches):
   * `cov`:    the covariance / gain kernel alone (csrc/kf_kernels.hip, mode 3: correction + prediction of one period),
   * `loop`:   the fused loop period (mpcqp_loop_device) with the steady gain and with the time-varying filter,
-  * `dare`:   the host-side alternative per model swap -- B SciPy DARE solves (steady_kalman_gain) plus the upload of K̂.
+  * `dare`:   the host-side alternative per model swap -- B SciPy DARE solves (steady_kalman_gain) plus the upload of K̂,
+  * `forms`:  the fused loop period in the predictor form (mpcqp_kf_set_direct(0): step, correction, prediction) on the same
+              data as `loop`, and kf_update_device (one covariance launch) against kf_correct_device + kf_predict_device (two).
 One JSON line per measurement.  A library without mpcqp_kf_set_covariances (an older build) gives the steady loop only, so
 the same script measures the yardstick on the parent commit.
-Usage: python scripts/kf_cov_time.py [cov] [loop] [dare] [B ...] [nxh16|nxh24|nxh32 ...]   (defaults: everything; C3 shapes at
+Usage: python scripts/kf_cov_time.py [cov] [loop] [dare] [forms] [B ...] [nxh16|nxh24|nxh32 ...]   (defaults: everything; C3 shapes at
 B = 65536 and 1024, nx̂ = 24 and 32 at B = 16384)."""
 import json
 import os
@@ -20,6 +22,7 @@ import mpcqp  # noqa: E402
 from mpcqp import synth  # noqa: E402
 
 HAVE_TV = hasattr(mpcqp.Handle, "kf_set_covariances")
+HAVE_DIRECT = hasattr(mpcqp.Handle, "kf_set_direct")
 WARM, REPS = 3, 10
 DEV = torch.device("cuda", 0)
 WIDE = {24: dict(nx=20, nym=4), 32: dict(nx=26, nym=6)}
@@ -89,9 +92,9 @@ def cov_alone(nxh, B):
                 gbytes_per_s=round(nbytes / max(dt, 1e-9) / 1e6, 1), dropped=bad)
 
 
-def loop_period(B):
+def loop_period(B, direct=True):
     """mpcqp_loop_device at C3 shapes, warm-started closed loop against the augmented model as the plant: steady gain and
-    time-varying filter on the same data."""
+    time-varying filter on the same data.  direct=False: the predictor form."""
     cfg, bt, A, Bu, C, ny = model(16, B)
     nxh, nu = cfg.nxh, cfg.nu
     rng = np.random.default_rng(1)
@@ -111,6 +114,8 @@ def loop_period(B):
             hd.kf_set_covariances(np.broadcast_to(Q[0], Q.shape), np.broadcast_to(R[0], R.shape), P0, np.arange(ny))
         else:
             hd.kf_set(mpcqp.colmajor(K), np.arange(ny))
+        if not direct:
+            hd.kf_set_direct(False)
         hd.prepare()
         Ad, Bd, Cd = T(bt["Ahat"]), T(bt["Bhu"]), T(bt["Chat"])
         xp = T(bt["xhat0"]).unsqueeze(2)
@@ -134,11 +139,36 @@ def loop_period(B):
                 ms.append(e0.elapsed_time(e1)); iters.append(float(it.double().mean()))
         res[tv] = dict(median_ms=round(float(np.median(ms)), 4), min_ms=round(float(np.min(ms)), 4), mean_iters=round(float(np.mean(iters)), 2),
                        not_optimal=int((st != 0).sum()))
-    out = dict(what="loop", workload=cfg.name, B=B, steady=res[False])
+    out = dict(what="loop" if direct else "loop_predictor_form", workload=cfg.name, B=B, steady=res[False])
     if True in res:
         out["time_varying"] = res[True]
         out["tv_over_steady"] = round(res[True]["median_ms"] / res[False]["median_ms"], 4)
     return out
+
+
+def update_vs_two_calls(B, nxh=16):
+    """updatestate! of the predictor form on a time-varying handle: kf_update_device (covariance mode 3, one launch) against
+    kf_correct_device + kf_predict_device (modes 1 and 2)."""
+    _, bt, A, Bu, C, ny = model(nxh, B)
+    nu = Bu.shape[2]
+    rng = np.random.default_rng(1)
+    Q, R, P0 = covariances(rng, B, nxh, ny)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    x, y, u = T(np.zeros((B, nxh))), T(rng.standard_normal((B, ny))), T(rng.standard_normal((B, nu)))
+    out = {}
+    for one in (False, True):
+        hd = mpcqp.Handle(B, nxh, nu, ny, 0, 2, 1)
+        hd.set_model(mpcqp.colmajor(A), mpcqp.colmajor(Bu), mpcqp.colmajor(C))
+        hd.kf_set_covariances(Q, R, P0, np.arange(ny))
+        def period(sp):
+            if one:
+                hd.kf_update_device(x.data_ptr(), u.data_ptr(), y.data_ptr(), stream=sp)
+            else:
+                hd.kf_correct_device(x.data_ptr(), y.data_ptr(), stream=sp)
+                hd.kf_predict_device(x.data_ptr(), u.data_ptr(), stream=sp)
+        out[one] = timed(period)
+    return dict(what="update", nxh=nxh, B=B, kf_update_ms=round(out[True][0], 4), correct_plus_predict_ms=round(out[False][0], 4),
+                ratio=round(out[True][0] / out[False][0], 4))
 
 
 def dare_alternative(B=1024):
@@ -159,7 +189,7 @@ def dare_alternative(B=1024):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    what = [a for a in args if a in ("cov", "loop", "dare")] or ["cov", "loop", "dare"]
+    what = [a for a in args if a in ("cov", "loop", "dare", "forms")] or ["cov", "loop", "dare", "forms"]
     Bs = [int(a) for a in args if a.isdigit()]
     sizes = [int(a[3:]) for a in args if a.startswith("nxh")] or [16, 24, 32]
     if "cov" in what and HAVE_TV:
@@ -171,3 +201,7 @@ if __name__ == "__main__":
             print(json.dumps(loop_period(B)), flush=True)
     if "dare" in what:
         print(json.dumps(dare_alternative()), flush=True)
+    if "forms" in what and HAVE_DIRECT:
+        for B in (Bs or [65536, 1024]):
+            print(json.dumps(loop_period(B, direct=False)), flush=True)
+        print(json.dumps(update_vs_two_calls((Bs or [65536])[0])), flush=True)
