@@ -279,7 +279,7 @@ int mpcqp_recondense_device(mpcqp_handle h, void* stream);
 #define MPCQP_GET_XHAT_MS   8   /* (nx̂,Hp,B): X̂0(k+1..k+Hp) of the last MultipleShooting step -- the second block of the
                                  * reference's decision vector Z = [ΔU; X̂0] (src/controller/transcription.jl:5-7) */
 #define MPCQP_GET_MS_DEFECT 9   /* (B): max |E_S Z + F_S| (defect of the model equations, transcription.jl:303-327) of it */
-#define MPCQP_GET_KF_COV    10  /* (nx̂,nx̂,B): P̂ of the time-varying KalmanFilter (MPCQP_ERR_ORDER on a steady gain) */
+#define MPCQP_GET_KF_COV    10  /* (nx̂,nx̂,B): P̂ of the time-varying KalmanFilter, P̂∞ after mpcqp_kf_set_steady (MPCQP_ERR_ORDER on a gain from mpcqp_kf_set) */
 #define MPCQP_GET_KF_GAIN   11  /* (nx̂,nym,B): K̂ the estimator steps use -- the steady gain or K̂(k) of the last correction */
 int mpcqp_get(mpcqp_handle h, int which, double* out);
 
@@ -350,8 +350,8 @@ int mpcqp_kf_update_device(mpcqp_handle h, double* xhat0, const double* u0, cons
  * handle keeps what it had).  Called again with P0 == NULL (same nym) it replaces Q̂ and R̂ and keeps P̂ and K̂ -- the Q̂, R̂
  * keywords of setmodel!.  A later mpcqp_kf_set returns the handle to the steady gain.
  * mpcqp_kf_set_state_covariance: P (nx̂,nx̂,B) replaces P̂ -- setstate!(estim, x̂, P̂).
- * mpcqp_kf_status: out [B], what became of the last correction attempt of each estimator (MPCQP_ERR_ORDER on a steady
- * gain, which keeps no status):
+ * mpcqp_kf_status: out [B], what became of the last correction attempt of each estimator (MPCQP_ERR_ORDER on a gain
+ * from mpcqp_kf_set, which keeps no status; after mpcqp_kf_set_steady: the outcome of the solve, see below):
  *       0  done.
  *       1  skipped for a missing measurement (see above): P̂ and K̂ keep their bits -- MPCQP_GET_KF_GAIN goes on showing
  *          the K̂ of the last correction that ran -- and the prediction of that period runs, P̂ <- Â P̂ Â' + Q̂.
@@ -359,12 +359,46 @@ int mpcqp_kf_update_device(mpcqp_handle h, double* xhat0, const double* u0, cons
  *          reference's cholesky! throws): P̂ and K̂ keep their values, and so does P̂ in the prediction of that period --
  *          only status 2 holds the covariance prediction back; the next correction that succeeds puts 0 back.
  * The other estimators of the batch and the LinMPC step statuses are unaffected.
- * mpcqp_kf_lanes_per_estimator: 0 on a steady gain, else 16 (max(nx̂, nym) <= 16: four estimators per wavefront) or 64. */
+ * mpcqp_kf_lanes_per_estimator: 0 on a gain from mpcqp_kf_set, else 16 (max(nx̂, nym) <= 16: four estimators per wavefront) or 64. */
 int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* Rhat, const double* P0,
                              const int32_t* i_ym, int32_t nym);
 int mpcqp_kf_set_state_covariance(mpcqp_handle h, const double* P);
 int mpcqp_kf_status(mpcqp_handle h, int32_t* out);
 int mpcqp_kf_lanes_per_estimator(mpcqp_handle h);
+
+/* ---- the SteadyKalmanFilter from Q̂ and R̂: the steady-state gain computed on the device ------------
+ * What the reference computes once per estimator on the host (kalman.jl:205-222) and refuses to redo after setmodel!
+ * (kalman.jl:229-232): here every estimator of the batch solves the discrete algebraic Riccati equation of the predictor
+ * form,  P = Â P Â' - Â P Ĉm' (Ĉm P Ĉm' + R̂)⁻¹ Ĉm P Â' + Q̂,  on the model that is resident, by the structure-preserving
+ * doubling iteration (csrc/kf_dare_bodies.h; at most 40 iterations, stopped when P moves by less than 1e-13 of
+ * max(1, max|P|)), and K̂ = P̂∞ Ĉm' (Ĉm P̂∞ Ĉm' + R̂)⁻¹, the filter-form gain of mpcqp_kf_set, lands in the gain buffer of
+ * the handle.  The iteration inverts H(k) (H(0) = Q̂) without pivoting: Q̂ has to be positive DEFINITE (R̂ too).  A
+ * semidefinite Q̂ gets status 2; compute its gain on the host and hand it to mpcqp_kf_set.
+ *
+ * mpcqp_kf_set_steady: Qhat (nx̂,nx̂,B), Rhat (nym,nym,B), i_ym [nym]: layouts, symmetry check (MPCQP_ERR_ARG) and i_ym
+ * validation of mpcqp_kf_set_covariances.  Needs the model (MPCQP_ERR_ORDER).  Stores Q̂ and R̂, fills K̂, P̂∞ and the
+ * status with zeros, and solves (host-synchronous).  max(nx̂, nym) > 32, or a build without the kernel:
+ * MPCQP_ERR_UNSUPPORTED, and the handle keeps what it had.  In every other respect the handle is then one with a steady
+ * gain: no launch is added to a period, and mpcqp_kf_correct / _predict / _update / mpcqp_loop_device are those of
+ * mpcqp_kf_set, in both forms of mpcqp_kf_set_direct.
+ * mpcqp_kf_solve_steady / _solve_steady_device: solve again on the model resident now (host-synchronous / enqueued on
+ * `stream`, ordered like every other *_device call).  mpcqp_set_model does NOT do this by itself: until the caller
+ * re-solves, the gain of the previous model stays in use.
+ * mpcqp_kf_steady_iters: out [B], doubling iterations of the last solve.
+ * On such a handle
+ *       mpcqp_kf_status   answers, per estimator, 0 solved; 1 not converged within the cap (the batch form of the
+ *                         reference's "Cannot compute the optimal Kalman gain": an undetectable pair); 2 broke down: a
+ *                         pivot of R̂, H(k) or H(k)⁻¹ + G(k) was outside (0, inf), or a value was not finite.  With 1 or 2
+ *                         the estimator's K̂ and P̂∞ keep their previous contents (zeros after mpcqp_kf_set_steady); the
+ *                         rest of the batch is unaffected, bit for bit;
+ *       MPCQP_GET_KF_COV  returns P̂∞;
+ *       mpcqp_kf_lanes_per_estimator answers 16 or 64.
+ * A later mpcqp_kf_set or mpcqp_kf_set_covariances leaves the mode: mpcqp_kf_solve_steady[_device] and
+ * mpcqp_kf_steady_iters then answer MPCQP_ERR_ORDER. */
+int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, const int32_t* i_ym, int32_t nym);
+int mpcqp_kf_solve_steady(mpcqp_handle h);
+int mpcqp_kf_solve_steady_device(mpcqp_handle h, void* stream);
+int mpcqp_kf_steady_iters(mpcqp_handle h, int32_t* out);
 
 
 /* ---- which kernel runs a step; building specialised kernels ahead of the control loop -----------

@@ -246,6 +246,41 @@ function pull_kalmanfilter(b::BatchLinMPC)
 end
 
 # ------------------------------------------------------------------------------------------------
+# SteadyKalmanFilter from Q̂ and R̂ behind the batch (include/mpcqp.h, "the SteadyKalmanFilter from Q̂ and R̂"): the steady-state
+# gain of every estimator is solved for on the device from the resident model, and solved again on request after a
+# setmodel! -> mpcqp_set_model (which the reference's SteadyKalmanFilter refuses).  Q̂ and R̂ positive definite,
+# max(nx̂, nym) <= 32.  pull_kalmanfilter reads K̂, P̂∞ and the status (0 solved, 1 not converged: undetectable, 2 broke down)
+# back.  Call sequence = BatchLinMPC.setestimator(steady=...) of api.py; these ccalls have not been run either.
+import ModelPredictiveControl: SteadyKalmanFilter
+
+"Q̂, R̂ of the batch's SteadyKalmanFilters to the device, and the first solve."
+function push_steadykalmanfilter!(b::BatchLinMPC)
+    es = [c.estim for c in b.mpcs]
+    all(e -> e isa SteadyKalmanFilter && e.direct == es[1].direct, es) || throw(ArgumentError("steady filter: SteadyKalmanFilters of one form (direct)"))
+    stack3(f) = cat((Matrix{Float64}(f(e)) for e in es)...; dims=3)          # (n, n, B)
+    Q̂, R̂ = stack3(e -> e.cov.Q̂), stack3(e -> e.cov.R̂)
+    i_ym = Cint.(es[1].i_ym .- 1)                                            # 0-based
+    GC.@preserve Q̂ R̂ i_ym check(ccall((:mpcqp_kf_set_steady, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Cint), b.h, Q̂, R̂, i_ym, length(i_ym)))
+    set_direct!(b, es[1].direct)
+    return b
+end
+
+"Solve again on the model resident now (after mpcqp_set_model): until then the gain of the previous model is in use."
+solve_steadykalmanfilter!(b::BatchLinMPC) = check(ccall((:mpcqp_kf_solve_steady, lib), Cint, (Ptr{Cvoid},), b.h))
+
+"The same, asynchronous on `stream`."
+solve_steadykalmanfilter_device!(b::BatchLinMPC, stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:mpcqp_kf_solve_steady_device, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), b.h, stream))
+
+"Doubling iterations of the last solve, per estimator."
+function steadykalmanfilter_iters(b::BatchLinMPC)
+    it = Vector{Cint}(undef, length(b.mpcs))
+    check(ccall((:mpcqp_kf_steady_iters, lib), Cint, (Ptr{Cvoid}, Ptr{Cint}), b.h, it))
+    return it
+end
+
+# ------------------------------------------------------------------------------------------------
 # Batch of linear MovingHorizonEstimator objects (include/mpcqp_mhe.h; SURVEY 8 row f2).  The estimators keep
 # their Julia fields; preparestate! / updatestate! of the BATCH run on the device.  Call sequence = the one of
 # modelpredictivecontrol.jl_amd/mhe.py (BatchMHE), which the GPU tests drive.

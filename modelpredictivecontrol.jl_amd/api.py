@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import types
 import warnings
 
 import numpy as np
@@ -33,6 +34,7 @@ STATUS_OPTIMAL, STATUS_ITERATION_LIMIT, STATUS_ERROR = 0, 1, 2
 GET_HESSIAN, GET_STEPRESP, GET_KMAT, GET_BVEC, GET_QTILDE, GET_FVEC, GET_AUDIT, GET_XHAT_MS, GET_MS_DEFECT = 1, 2, 3, 4, 5, 6, 7, 8, 9
 GET_KF_COV, GET_KF_GAIN = 10, 11
 KF_STATUS_OK, KF_STATUS_DROPPED = 0, 2
+KF_STEADY_OK, KF_STEADY_NOT_CONVERGED, KF_STEADY_BROKE_DOWN = 0, 1, 2      # mpcqp_kf_status after mpcqp_kf_set_steady
 EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_create",
            "mpcqp_destroy", "mpcqp_get_sizes", "mpcqp_set_model", "mpcqp_set_weights",
            "mpcqp_set_bounds", "mpcqp_step", "mpcqp_step_device", "mpcqp_loop_device", "mpcqp_recondense_device",
@@ -40,6 +42,7 @@ EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_cre
            "mpcqp_kf_correct", "mpcqp_kf_predict", "mpcqp_kf_correct_device", "mpcqp_kf_predict_device",
            "mpcqp_kf_set_covariances", "mpcqp_kf_set_state_covariance", "mpcqp_kf_status", "mpcqp_kf_lanes_per_estimator",
            "mpcqp_kf_set_direct", "mpcqp_kf_update", "mpcqp_kf_update_device",
+           "mpcqp_kf_set_steady", "mpcqp_kf_solve_steady", "mpcqp_kf_solve_steady_device", "mpcqp_kf_steady_iters",
            "mpcqp_set_output_weight_blocks", "mpcqp_set_dense_weights", "mpcqp_set_custom_constraints", "mpcqp_set_custom_bounds",
            "mpcqp_set_flags", "mpcqp_set_iteration_limit", "mpcqp_set_transcription", "mpcqp_transcription_supported", "mpcqp_set_current_setpoint", "mpcqp_prepare", "mpcqp_kernel_kind", "mpcqp_lds_bytes", "mpcqp_row_groups", "mpcqp_step_consts_builds", "mpcqp_prebuild",
            "mpcqp_last_build_error", "mpcqp_multi_create", "mpcqp_multi_destroy", "mpcqp_multi_ndev",
@@ -176,6 +179,11 @@ def load_library(path: str | None = None):
     lib.mpcqp_kf_set_direct.argtypes = [C.c_void_p, C.c_int32]
     lib.mpcqp_kf_update.argtypes = [C.c_void_p] * 5
     lib.mpcqp_kf_update_device.argtypes = [C.c_void_p] * 6
+    if hasattr(lib, "mpcqp_kf_set_steady"):        # (an older build of the library: Handle then has no kf_*_steady methods)
+        lib.mpcqp_kf_set_steady.argtypes = [C.c_void_p] * 4 + [C.c_int32]
+        lib.mpcqp_kf_solve_steady.argtypes = [C.c_void_p]
+        lib.mpcqp_kf_solve_steady_device.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mpcqp_kf_steady_iters.argtypes = [C.c_void_p, C.c_void_p]
     lib.mpcqp_set_current_setpoint.argtypes = [C.c_void_p, C.c_void_p]
     lib.mpcqp_prepare.argtypes = [C.c_void_p]
     lib.mpcqp_kernel_kind.argtypes = [C.c_void_p]
@@ -222,6 +230,35 @@ def colmajor(M):
     return _f64(np.asarray(M, float).transpose(0, 2, 1))
 
 
+# -- SteadyKalmanFilter from Q̂ and R̂: the gain solved for on the device (csrc/kf_dare_bodies.h).  Methods of Handle, bound
+# only when the library exports the entry points
+def _kf_set_steady(self, Qhat, Rhat, i_ym):
+    """Qhat (B,nx̂,nx̂), Rhat (B,nym,nym), symmetric positive definite.  Solves the Riccati equation of every member on the
+    resident model; kf_gain() / kf_covariance() / kf_status() / kf_steady_iters() read the result back."""
+    iy = np.ascontiguousarray(i_ym, dtype=np.int32)
+    _chk(self.lib, self.lib.mpcqp_kf_set_steady(self.h, _ptr(colmajor(Qhat)), _ptr(colmajor(Rhat)), _ptr(iy), int(iy.size)))
+    self.nym = int(iy.size)
+
+
+def _kf_solve_steady(self):
+    """Solve again on the model that is resident now (after set_model); host-synchronous."""
+    _chk(self.lib, self.lib.mpcqp_kf_solve_steady(self.h))
+
+
+def _kf_solve_steady_device(self, stream=0):
+    _chk(self.lib, self.lib.mpcqp_kf_solve_steady_device(self.h, C.c_void_p(stream)))
+
+
+def _kf_steady_iters(self):
+    """(B,) int32 doubling iterations of the last solve."""
+    out = np.empty(self.B, np.int32)
+    _chk(self.lib, self.lib.mpcqp_kf_steady_iters(self.h, _ptr(out)))
+    return out
+
+
+_STEADY_METHODS = {f.__name__[1:]: f for f in (_kf_set_steady, _kf_solve_steady, _kf_solve_steady_device, _kf_steady_iters)}
+
+
 class Handle:
     """Thin binding of the C-ABI; array arguments are already in ABI layout."""
 
@@ -242,6 +279,13 @@ class Handle:
         self.nZ, self.nDU, self.nU, self.nY, self.nD = s.nZ, s.nDU, s.nU, s.nY, s.nD
         self.flags = flags
         self._keep = []
+
+    def __getattr__(self, name):
+        # kf_set_steady, kf_solve_steady, kf_solve_steady_device, kf_steady_iters: there only when the library exports them
+        f = _STEADY_METHODS.get(name)
+        if f is not None and hasattr(self.__dict__.get("lib"), "mpcqp_kf_set_steady"):
+            return types.MethodType(f, self)
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:
@@ -730,6 +774,9 @@ class BatchLinMPC:
                           None if self.nd == 0 else colmajor(Bhd),
                           None if self.nd == 0 else colmajor(Dhd),
                           dopv if np.any(dopv != 0) else None)
+        if getattr(self, "kf_steady", False):      # SteadyKalmanFilter from Q̂ and R̂: the gain follows the model
+            self.hd.kf_solve_steady()
+            self._warn_steady()
 
     def setweights(self, Mwt=None, Nwt=None, Lwt=None, M_Hp=None, N_Hc=None, L_Hp=None):
         """Defaults of src/general.jl:3-6 (Mwt=1, Nwt=0.1, Lwt=0).  `M_Hp` (nY,nY), `N_Hc` (nΔU,nΔU), `L_Hp`
@@ -911,7 +958,7 @@ class BatchLinMPC:
         return self
 
     # -- estimator steps on both sides of moveinput! (SteadyKalmanFilter) ---------------------
-    def setestimator(self, Khat=None, i_ym=None, xhat0=None, *, covariances=None, direct=True):
+    def setestimator(self, Khat=None, i_ym=None, xhat0=None, *, covariances=None, steady=None, direct=True):
         """Attach a SteadyKalmanFilter: Khat (B,nx̂,nym) steady-state gain (see
         `steady_kalman_gain`), i_ym measured-output indices (default all).  The estimate x̂0
         (deviation, (B,nx̂)) is then carried by this object like `mpc.estim.x̂0`.
@@ -920,19 +967,27 @@ class BatchLinMPC:
         Q̂ (nx̂,nx̂), R̂ (nym,nym), P̂_0 (nx̂,nx̂), each shared or with a leading batch axis.  P̂ and K̂(k) then live on the
         device and follow `preparestate` / `updatestate` (and `setmodel`: the recursion reads the current model).
 
+        `steady=dict(Qhat=…, Rhat=…)` is the SteadyKalmanFilter as the reference constructs it, from Q̂ and R̂ (kalman.jl:205-222):
+        the steady-state gain of every member is solved for on the device (Q̂ and R̂ positive definite, max(nx̂, nym) <= 32;
+        `steady_kalman_gain` on the host is the path for a semidefinite Q̂), and `setmodel` solves again on the new model --
+        which the reference's SteadyKalmanFilter refuses.  Members whose equation has no solution (an undetectable pair) or
+        whose solve broke down keep a zero gain and are counted in one RuntimeWarning; `getinfo` shows `kf_status`.
+
         `direct=False` is the predictor form (kalman.jl:112): `preparestate` does nothing, `moveinput` works on x̂ₖ₋₁(k) and
         `updatestate(u, ym, d)` corrects and then predicts.  Khat is the FILTER-form gain in both forms (what
         `steady_kalman_gain` returns): the library applies x̂ <- Â (x̂ + K̂ v) + ... like `update_estimate!`.
 
         In both forms a member whose `ym` row holds a NaN, or every member when `ym` is None, skips the correction of that
         period (RuntimeWarning with the count); its prediction runs."""
+        if (Khat is not None) + (covariances is not None) + (steady is not None) > 1:
+            raise ValueError("give one of Khat (SteadyKalmanFilter), steady (SteadyKalmanFilter from Q̂ and R̂) or covariances (KalmanFilter)")
         if covariances is not None:
-            if Khat is not None:
-                raise ValueError("give either Khat (SteadyKalmanFilter) or covariances (KalmanFilter)")
             return self.setkalmanfilter(**covariances, i_ym=i_ym, xhat0=xhat0, direct=direct)
+        if steady is not None:
+            return self.setsteadykalmanfilter(**steady, i_ym=i_ym, xhat0=xhat0, direct=direct)
         if Khat is None:
-            raise ValueError("setestimator needs Khat or covariances")
-        self.kf_timevarying = False
+            raise ValueError("setestimator needs Khat, steady or covariances")
+        self.kf_timevarying = self.kf_steady = False
         self.i_ym = np.arange(self.ny) if i_ym is None else np.asarray(i_ym, int)
         Khat = np.asarray(Khat, float)
         if Khat.shape != (self.B, self.nxh, len(self.i_ym)):
@@ -971,14 +1026,39 @@ class BatchLinMPC:
         Qhat, Rhat, P0 = self._cov(Qhat, self.nxh, "Q̂"), self._cov(Rhat, nym, "R̂"), self._cov(P0, self.nxh, "P̂_0")
         self._set_direct(direct)
         self.hd.kf_set_covariances(Qhat, Rhat, P0, self.i_ym)
-        self.kf_timevarying = True
+        self.kf_timevarying, self.kf_steady = True, False
         self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
         return self
 
+    def setsteadykalmanfilter(self, Qhat, Rhat, i_ym=None, xhat0=None, direct=True):
+        """The `SteadyKalmanFilter` from Q̂ and R̂ (see `setestimator(steady=…)`)."""
+        if not hasattr(self.hd, "kf_set_steady"):
+            raise NotImplementedError("steady=dict(Qhat, Rhat): this handle has no mpcqp_kf_set_steady")
+        self.i_ym = np.arange(self.ny) if i_ym is None else np.asarray(i_ym, int)
+        Qhat, Rhat = self._cov(Qhat, self.nxh, "Q̂"), self._cov(Rhat, len(self.i_ym), "R̂")
+        self._set_direct(direct)
+        self.hd.kf_set_steady(Qhat, Rhat, self.i_ym)
+        self.kf_timevarying, self.kf_steady = False, True
+        self._warn_steady()
+        self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
+        return self
+
+    def _warn_steady(self):
+        """One warning for the members whose steady-state gain could not be computed (kalman.jl:211-221)."""
+        n = int(np.count_nonzero(self.hd.kf_status()))
+        if n:
+            warnings.warn("Cannot compute the optimal Kalman gain K̂ for the SteadyKalmanFilter: the pair is not detectable or "
+                          f"the solve broke down, the previous gain stays ({n} of {self.B} estimators)", RuntimeWarning)
+
     def setcovariances(self, Qhat, Rhat):
-        """The Q̂, R̂ keywords of `setmodel!` (KalmanFilter only): new noise covariances, P̂ and x̂0 stay."""
+        """The Q̂, R̂ keywords of `setmodel!`: new noise covariances.  KalmanFilter: P̂ and x̂0 stay.  SteadyKalmanFilter from Q̂
+        and R̂ (`setestimator(steady=…)`): the gain is solved for again."""
+        if getattr(self, "kf_steady", False):
+            self.hd.kf_set_steady(self._cov(Qhat, self.nxh, "Q̂"), self._cov(Rhat, len(self.i_ym), "R̂"), self.i_ym)
+            return self._warn_steady()
         if not getattr(self, "kf_timevarying", False):
-            raise ValueError("Q̂ and R̂ can only be replaced on a time-varying KalmanFilter (setestimator(covariances=…))")
+            raise ValueError("Q̂ and R̂ can only be replaced on a KalmanFilter (setestimator(covariances=…)) or a "
+                             "SteadyKalmanFilter built from them (setestimator(steady=…))")
         self.hd.kf_set_covariances(self._cov(Qhat, self.nxh, "Q̂"), self._cov(Rhat, len(self.i_ym), "R̂"), None, self.i_ym)
 
     def setstate(self, xhat, Phat=None):
@@ -1152,7 +1232,8 @@ class BatchLinMPC:
             X0 = self.hd.get(GET_XHAT_MS)
             x = X0[:, -1]
         info["x̂end"] = x + self.xhop
-        if getattr(self, "kf_timevarying", False):     # the estimator's covariance, gain and per-estimator status
+        if getattr(self, "kf_timevarying", False) or getattr(self, "kf_steady", False):
+            # the estimator's covariance (P̂∞ of a steady solve), gain and per-estimator status
             info["P̂"], info["K̂"], info["kf_status"] = self.hd.kf_covariance(), self.hd.kf_gain(), self.hd.kf_status()
         # decision vector in the transcription's layout: [ΔU; ϵ] or [ΔU; X̂0(k+1..k+Hp); ϵ] (get_nZ_mpc, transcription.jl:2-7)
         parts = [DU] + ([X0.reshape(self.B, -1)] if self.transcription == "MultipleShooting" else []) + ([eps[:, None]] if self.neps else [])

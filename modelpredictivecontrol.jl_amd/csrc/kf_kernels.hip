@@ -1,5 +1,7 @@
 // kf_kernels.hip -- gfx950 kernels of the covariance / gain recursion of the time-varying KalmanFilter (bodies:
-// kf_cov_bodies.h).  One wavefront per workgroup, persistent grid, the same split as the MovingHorizonEstimator:
+// kf_cov_bodies.h) and of the steady-state Riccati solve of the SteadyKalmanFilter (k_kf_dare<NX>, k_kf_dare_wide<NX>, the
+// same families; body: kf_dare_bodies.h).  One wavefront per workgroup, persistent grid, the same split as the
+// MovingHorizonEstimator:
 //   k_kf_cov<NX>,      NX = 4, 8, 12, 16: max(nx̂, nym) <= 16, four estimators per wavefront (one per DPP row, MheDevWave);
 //   k_kf_cov_wide<NX>, NX = 24, 32: 16 < max(nx̂, nym) <= 32, one estimator per wavefront, the NX^3 products on the
 //                      matrix cores through the LDS staging buffer of Ops::mm_staged.
@@ -7,6 +9,8 @@
 
 #include "kf_cov_bodies.h"
 #include "kf_cov_launch.h"
+#include "kf_dare_bodies.h"
+#include "kf_dare_launch.h"
 #include "mhe_devwave.h"
 #include "mhe_wide_devwave.h"
 #include "mpcqp_launch.h"
@@ -57,6 +61,38 @@ int kf_cov_waves_for(int device, int B, int NX) {
     const int cap = cus * (wide ? 4 : 8);
     return groups < cap ? groups : cap;
 }
+
+// ---- steady-state gain from Q̂ and R̂ (once per model, not per period).  Seven rows of NX doubles stay in registers over
+// the iterations: the wide kernels spill (lib/isa_resources.txt), which a solve per model swap can afford.
+template <int NX>
+__global__ __launch_bounds__(64) void k_kf_dare(DareArgs a) {
+    MheDevWave w{(int)threadIdx.x};
+    kf_dare_body<MheDevWave, NX>(w, a, (int)blockIdx.x);
+}
+template <int NX>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_kf_dare_wide(DareArgs a) {
+    WideWave w;
+    w.lane = (int)threadIdx.x;
+    w.stage = mpcqp_smem;
+    kf_dare_body<WideWave, NX>(w, a, (int)blockIdx.x);
+}
+
+hipError_t launch_kf_dare(const DareArgs& a, hipStream_t st) {
+    if (a.B < 1 || a.nwaves < 1 || a.nx < 1 || a.nym < 1 || a.nx > a.NX || a.nym > a.NX) return hipErrorInvalidValue;
+    switch (a.NX) {
+        case 4: hipLaunchKernelGGL(k_kf_dare<4>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
+        case 8: hipLaunchKernelGGL(k_kf_dare<8>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
+        case 12: hipLaunchKernelGGL(k_kf_dare<12>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
+        case 16: hipLaunchKernelGGL(k_kf_dare<16>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
+        case 24: hipLaunchKernelGGL(k_kf_dare_wide<24>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a); break;
+        case 32: hipLaunchKernelGGL(k_kf_dare_wide<32>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// the grid of the covariance kernels: what is not resident at once queues behind what is
+int kf_dare_waves_for(int device, int B, int NX) { return kf_cov_waves_for(device, B, NX); }
 
 }  // namespace kf
 }  // namespace mpcqp

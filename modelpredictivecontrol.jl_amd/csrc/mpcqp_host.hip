@@ -12,6 +12,7 @@
 
 #include "../../include/mpcqp.h"
 #include "kf_cov_launch.h"
+#include "kf_dare_launch.h"
 #include "mpcqp_hostutil.h"
 #include "mpcqp_launch.h"
 #include "ms_bodies.h"
@@ -69,6 +70,11 @@ struct mpcqp_handle_s {
     bool kf_tv = false;
     DBuf kf_Q, kf_R, kf_P, kf_st;
     int kf_NX = 0, kf_waves = 0;   // register columns and persistent grid of the covariance kernel
+    // SteadyKalmanFilter from Q̂ and R̂ (mpcqp_kf_set_steady): kf_K holds the gain the Riccati kernel (kf_dare_bodies.h) solved
+    // for, kf_P its P̂∞, kf_st / kf_it the status and iteration count of the last solve; kf_tv stays false
+    bool kf_steady = false;
+    DBuf kf_it;
+    int kf_dare_waves = 0;
     // mpcqp_kf_set_direct: 1 filter form (mpcqp_loop_device: correction, step, prediction), 0 predictor form (step, correction,
     // prediction).  A property of the handle: the setters of the gain and of the covariances leave it alone
     int kf_direct = 1;
@@ -919,7 +925,7 @@ int mpcqp_get(mpcqp_handle h, int which, double* out) {
             HIPCHK(hipMemcpy(out, h->audit.p, B * 4 * sizeof(double), hipMemcpyDeviceToHost));
             return MPCQP_OK;
         case MPCQP_GET_KF_COV:
-            if (!h->have_kf || !h->kf_tv) return MPCQP_ERR_ORDER;
+            if (!h->have_kf || !(h->kf_tv || h->kf_steady)) return MPCQP_ERR_ORDER;
             HIPCHK(hipMemcpy(out, h->kf_P.p, B * d.nxh * d.nxh * sizeof(double), hipMemcpyDeviceToHost));
             return MPCQP_OK;
         case MPCQP_GET_KF_GAIN:
@@ -957,6 +963,7 @@ int mpcqp_kf_set(mpcqp_handle h, const double* Khat, const int32_t* i_ym, int32_
     h->kf.nym = nym;
     h->have_kf = true;
     h->kf_tv = false;           // (back to the steady gain: the covariance kernel no longer runs)
+    h->kf_steady = false;       // (a gain of the caller's: nothing to re-solve)
     return MPCQP_OK;
 }
 
@@ -1009,6 +1016,84 @@ int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* R
     h->kf_waves = kf::kf_cov_waves_for(h->device, d.B, h->kf_NX);
     h->have_kf = true;
     h->kf_tv = true;
+    h->kf_steady = false;
+    return MPCQP_OK;
+}
+
+// One Riccati solve of a handle in steady mode (kf_kernels.hip: k_kf_dare*) on the model that is resident now.
+static int kf_dare_launch(mpcqp_handle h, hipStream_t st) {
+    if (!kf::kf_dare_available()) return MPCQP_ERR_UNSUPPORTED;
+    ON_DEVICE(h);
+    const Dims& d = h->d;
+    kf::DareArgs a{};
+    a.Ahat = h->m.Ahat; a.C = h->m.C; a.i_ym = h->kf.i_ym;
+    a.Q = (const double*)h->kf_Q.p; a.R = (const double*)h->kf_R.p;
+    a.K = (double*)h->kf_K.p; a.P = (double*)h->kf_P.p;
+    a.status = (int32_t*)h->kf_st.p; a.iters = (int32_t*)h->kf_it.p;
+    a.B = d.B; a.nx = d.nxh; a.ny = d.ny; a.nym = h->kf.nym;
+    a.NX = h->kf_NX; a.nwaves = h->kf_dare_waves;
+    HIPCHK(kf::launch_kf_dare(a, st));
+    return MPCQP_OK;
+}
+
+int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, const int32_t* i_ym, int32_t nym) {
+    if (!h || !Qhat || !Rhat || !i_ym) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    if (nym < 1 || nym > d.ny) return MPCQP_ERR_DIMS;
+    for (int i = 0; i < nym; ++i) {
+        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;     // validate_ym, construct.jl:190-196
+        for (int j = 0; j < i; ++j)
+            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
+    }
+    if (std::max(d.nxh, (int)nym) > mhe::NX_MAX || !kf::kf_dare_available()) return MPCQP_ERR_UNSUPPORTED;
+    const size_t B = d.B, nn = (size_t)d.nxh * d.nxh, nk = (size_t)d.nxh * nym, sz = sizeof(double);
+    if (!kf_symmetric(Qhat, B, d.nxh) || !kf_symmetric(Rhat, B, nym)) return MPCQP_ERR_ARG;
+    if (!h->have_model) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    int rc = upload(h, h->kf_Q, Qhat, B * nn * sz);
+    if (!rc) rc = upload(h, h->kf_R, Rhat, B * (size_t)nym * nym * sz);
+    if (!rc) rc = upload(h, h->kf_iym, i_ym, (size_t)nym * sizeof(int32_t));
+    if (!rc) rc = dev_alloc(h, h->kf_P, B * nn * sz);
+    if (!rc) rc = dev_alloc(h, h->kf_K, B * nk * sz);
+    if (!rc) rc = dev_alloc(h, h->kf_st, B * sizeof(int32_t));
+    if (!rc) rc = dev_alloc(h, h->kf_it, B * sizeof(int32_t));
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(h->kf_P.p, 0, B * nn * sz, h->stream));
+    HIPCHK(hipMemsetAsync(h->kf_K.p, 0, B * nk * sz, h->stream));
+    HIPCHK(hipMemsetAsync(h->kf_st.p, 0, B * sizeof(int32_t), h->stream));
+    HIPCHK(hipMemsetAsync(h->kf_it.p, 0, B * sizeof(int32_t), h->stream));
+    h->kf.Khat = (const double*)h->kf_K.p;
+    h->kf.i_ym = (const int*)h->kf_iym.p;
+    h->kf.nym = nym;
+    h->kf_NX = kf::kf_cov_columns_for(std::max(d.nxh, (int)nym));
+    h->kf_dare_waves = kf::kf_dare_waves_for(h->device, d.B, h->kf_NX);
+    h->have_kf = true;
+    h->kf_tv = false;
+    h->kf_steady = true;
+    return mpcqp_kf_solve_steady(h);
+}
+
+int mpcqp_kf_solve_steady_device(mpcqp_handle h, void* stream) {
+    if (!h) return MPCQP_ERR_NULL;
+    if (!h->kf_steady || !h->have_model) return MPCQP_ERR_ORDER;
+    return kf_dare_launch(h, (hipStream_t)stream);
+}
+
+int mpcqp_kf_solve_steady(mpcqp_handle h) {
+    if (!h) return MPCQP_ERR_NULL;
+    int rc = mpcqp_kf_solve_steady_device(h, h->stream);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
+int mpcqp_kf_steady_iters(mpcqp_handle h, int32_t* out) {
+    if (!h || !out) return MPCQP_ERR_NULL;
+    if (!h->kf_steady) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, h->kf_it.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
     return MPCQP_OK;
 }
 
@@ -1027,7 +1112,7 @@ int mpcqp_kf_set_state_covariance(mpcqp_handle h, const double* P) {
 
 int mpcqp_kf_status(mpcqp_handle h, int32_t* out) {
     if (!h || !out) return MPCQP_ERR_NULL;
-    if (!h->kf_tv) return MPCQP_ERR_ORDER;
+    if (!h->kf_tv && !h->kf_steady) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipDeviceSynchronize());
@@ -1037,7 +1122,7 @@ int mpcqp_kf_status(mpcqp_handle h, int32_t* out) {
 
 int mpcqp_kf_lanes_per_estimator(mpcqp_handle h) {
     if (!h) return MPCQP_ERR_NULL;
-    return h->kf_tv ? kf::kf_cov_lanes_for(h->kf_NX) : 0;
+    return (h->kf_tv || h->kf_steady) ? kf::kf_cov_lanes_for(h->kf_NX) : 0;
 }
 
 int mpcqp_kf_correct_device(mpcqp_handle h, double* xhat0, const double* y0m, const double* d0, void* stream) {
