@@ -1,7 +1,7 @@
 // kf_cov_launch.h -- arguments and host-side launch entry points of the covariance / gain recursion of the time-varying
 // KalmanFilter of the LinMPC loop (kf_kernels.hip; bodies: kf_cov_bodies.h).  WEAK declarations, as in mhe_wide_launch.h:
-// a library linked without that unit (the stock CPU emulator of tests/emu) still links, and mpcqp_kf_set_covariances
-// answers MPCQP_ERR_UNSUPPORTED (kf_cov_available()).
+// a library linked without that unit (the stock CPU emulator tests/emu/libmpcqp_emu.so; libmpcqp_emu_est.so has the launchers
+// of tests/emu/emu_kf_cov.cpp) still links, and mpcqp_kf_set_covariances answers MPCQP_ERR_UNSUPPORTED (kf_cov_available()).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,6 +33,8 @@ struct CovArgs {
     const double* y0m;           // [B][nym] measurements of a COV_CORRECT launch (any(isnan) of a row: that estimator's
                                  // correction is missed), or null: every correction runs
 };
+// what every launcher (kf_kernels.hip, tests/emu/emu_kf_cov.cpp) checks before it picks a kernel for a.NX
+inline bool kf_cov_args_ok(const CovArgs& a) { return a.B >= 1 && a.nwaves >= 1 && a.nx >= 1 && a.nym >= 1 && a.nx <= a.NX && a.nym <= a.NX; }
 
 __attribute__((weak)) hipError_t launch_kf_cov(const CovArgs& a, int mode, hipStream_t st);
 __attribute__((weak)) int kf_cov_waves_for(int device, int B, int NX);      // size of the persistent grid

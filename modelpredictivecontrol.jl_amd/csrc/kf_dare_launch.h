@@ -1,7 +1,7 @@
 // kf_dare_launch.h -- arguments and host-side launch entry points of the steady-state Riccati solve of the
 // SteadyKalmanFilter (kf_kernels.hip; body: kf_dare_bodies.h).  WEAK declarations, as in kf_cov_launch.h: a library linked
-// without the launcher (the stock CPU emulator of tests/emu) still links, and mpcqp_kf_set_steady answers
-// MPCQP_ERR_UNSUPPORTED (kf_dare_available()).
+// without the launcher (the stock CPU emulator tests/emu/libmpcqp_emu.so; libmpcqp_emu_est.so has the one of
+// tests/emu/emu_kf_dare.cpp) still links, and mpcqp_kf_set_steady answers MPCQP_ERR_UNSUPPORTED (kf_dare_available()).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,6 +36,8 @@ struct DareArgs {
     int NX;                      // register columns: kf_cov_columns_for(max(nx, nym))
     int nwaves;                  // wavefronts launched (each loops over groups of GPW estimators)
 };
+// what every launcher (kf_kernels.hip, tests/emu/emu_kf_dare.cpp) checks before it picks a kernel for a.NX
+inline bool kf_dare_args_ok(const DareArgs& a) { return a.B >= 1 && a.nwaves >= 1 && a.nx >= 1 && a.nym >= 1 && a.nx <= a.NX && a.nym <= a.NX; }
 
 __attribute__((weak)) hipError_t launch_kf_dare(const DareArgs& a, hipStream_t st);
 __attribute__((weak)) int kf_dare_waves_for(int device, int B, int NX);     // size of the persistent grid

@@ -37,7 +37,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void
 }
 
 hipError_t launch_kf_cov(const CovArgs& a, int mode, hipStream_t st) {
-    if (a.B < 1 || a.nwaves < 1 || a.nx < 1 || a.nym < 1 || a.nx > a.NX || a.nym > a.NX) return hipErrorInvalidValue;
+    if (!kf_cov_args_ok(a)) return hipErrorInvalidValue;
     switch (a.NX) {
         case 4: hipLaunchKernelGGL(k_kf_cov<4>, dim3(a.nwaves), dim3(WAVE), 0, st, a, mode); break;
         case 8: hipLaunchKernelGGL(k_kf_cov<8>, dim3(a.nwaves), dim3(WAVE), 0, st, a, mode); break;
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void
 }
 
 hipError_t launch_kf_dare(const DareArgs& a, hipStream_t st) {
-    if (a.B < 1 || a.nwaves < 1 || a.nx < 1 || a.nym < 1 || a.nx > a.NX || a.nym > a.NX) return hipErrorInvalidValue;
+    if (!kf_dare_args_ok(a)) return hipErrorInvalidValue;
     switch (a.NX) {
         case 4: hipLaunchKernelGGL(k_kf_dare<4>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
         case 8: hipLaunchKernelGGL(k_kf_dare<8>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;

@@ -1,7 +1,8 @@
 // mhe_wide_launch.h -- host-side launch entry points of the wide kernels (mhe_wide_kernels.hip: one estimator per
-// wavefront, 16 < max(nx̂, nym) <= 32).  WEAK declarations: a library linked without that unit (the CPU emulator of
-// tests/emu, which defines the entry points of mhe_launch.h only) still links, and mpcqp_mhe_create refuses the
-// dimensions these kernels would serve (wide_available()).
+// wavefront, 16 < max(nx̂, nym) <= 32).  WEAK declarations: a library linked without that unit (the stock CPU emulator
+// tests/emu/libmpcqp_emu.so, which defines the entry points of mhe_launch.h only; libmpcqp_emu_est.so has the wide ones of
+// tests/emu/emu_mhe_wide.cpp) still links, and mpcqp_mhe_create refuses the dimensions these kernels would serve
+// (wide_available()).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,114 +1,21 @@
 // TEST INFRASTRUCTURE ONLY: the covariance / gain recursion of the time-varying KalmanFilter (csrc/kf_cov_bodies.h) on the
-// CPU.  Defines the launchers that csrc/kf_cov_launch.h declares weak, over the emulated wavefront of emu_fiber.h: four
-// estimators per wavefront on 16-lane rows (max(nx̂, nym) <= 16) or one on the 64 lanes with the staged products (plain-loop
-// side of Ops::mm_staged).  Linked only into libmpcqp_emu_kf.so (tests/kf_util.py); the stock emulator library has no such
+// CPU.  Defines the launchers that csrc/kf_cov_launch.h declares weak, over the waves of emu_rowwave.h: four estimators per
+// wavefront on 16-lane rows (max(nx̂, nym) <= 16) or one on the 64 lanes with the staged products (plain-loop side of
+// Ops::mm_staged).  Linked only into libmpcqp_emu_est.so (tests/emu/Makefile); the stock emulator library has no such
 // launcher and answers MPCQP_ERR_UNSUPPORTED to mpcqp_kf_set_covariances.
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "emu_fiber.h"
+#include "emu_rowwave.h"
 #include "kf_cov_bodies.h"
 #include "kf_cov_launch.h"
 
 namespace mpcqp {
 namespace kf {
 
-namespace {
-
-struct Shared {
-    LaneFibers& bar = lane_fibers();
-    double xd[2][WAVE];
-    unsigned cn[2][WAVE];                // index of the cross-lane operation every lane is in
-};
-
-// GLV lanes per estimator: a broadcast reads lane C of this lane's group, a reduction runs over the group.  Every
-// cross-lane operation writes buffer (n % 2) of its n-th call, waits once, reads (see EmuWave of emu_mhe.cpp).
-template <int GLV>
-struct EmuKfWave {
-    static constexpr int GL = GLV, GPW = WAVE / GLV;
-    int lane;
-    Shared* sh;
-    unsigned n = 0;
-    void sync() { sh->bar.arrive_and_wait(); }
-    double* xchg(double v) {
-        sh->cn[n & 1][lane] = n;
-        double* buf = sh->xd[n++ & 1];
-        buf[lane] = v;
-        sh->bar.arrive_and_wait();
-        for (int i = 0; i < WAVE; ++i)
-            if (sh->cn[(n - 1) & 1][i] != n - 1) {
-                fprintf(stderr, "[emu kf] lanes disagree on the sequence of cross-lane operations: lane %d in operation %u, lane %d in %u\n",
-                        lane, n - 1, i, sh->cn[(n - 1) & 1][i]);
-                fflush(stderr);
-                abort();
-            }
-        return buf;
-    }
-    template <int C>
-    double rowbc(double v) { return xchg(v)[(lane & ~(GLV - 1)) + C]; }
-    template <int L0, int L1, int L2, int L3>
-    void fmabc4(double& acc, double x0, double x1, double x2, double x3, double y0, double y1, double y2, double y3) {
-        acc = fma(rowbc<L0>(x0), y0, acc); acc = fma(rowbc<L1>(x1), y1, acc);
-        acc = fma(rowbc<L2>(x2), y2, acc); acc = fma(rowbc<L3>(x3), y3, acc);
-    }
-    template <int L0, int L1, int L2, int L3>
-    void fmsbc4(double& acc, double x0, double x1, double x2, double x3, double y0, double y1, double y2, double y3) {
-        acc = fma(rowbc<L0>(x0), -y0, acc); acc = fma(rowbc<L1>(x1), -y1, acc);
-        acc = fma(rowbc<L2>(x2), -y2, acc); acc = fma(rowbc<L3>(x3), -y3, acc);
-    }
-    template <int K>
-    void gjacc4(double& a0, double& a1, double& a2, double& a3, double g) {
-        const double b0 = rowbc<K>(a0), b1 = rowbc<K>(a1), b2 = rowbc<K>(a2), b3 = rowbc<K>(a3);
-        a0 = fma(b0, g, a0); a1 = fma(b1, g, a1); a2 = fma(b2, g, a2); a3 = fma(b3, g, a3);
-    }
-    double rmin(double v) {
-        const double* buf = xchg(v);
-        const int r0 = lane & ~(GLV - 1);
-        double s = buf[r0];
-        for (int i = 1; i < GLV; ++i) s = fmin(s, buf[r0 + i]);
-        return s;
-    }
-};
-
-// the wide interface carries the "LDS" of the staged products; without a `stage` member the 16-lane one keeps the
-// row-broadcast products (mhe::WaveStaged)
-struct EmuKfRowWave : EmuKfWave<mhe::RL> {};
-struct EmuKfWideWave : EmuKfWave<mhe::WIDE_RL> {
-    double* stage = nullptr;
-};
-
-template <class W, int NX>
-void run_cov(const CovArgs& a, int mode) {
-    std::vector<double> smem(mhe::stage_doubles() + 16, 0.0);
-    Shared sh;
-    int perm[64];
-    emu_lane_order(perm);
-    sh.bar.run([&](int fiber) {
-        W w{};
-        w.lane = perm[fiber]; w.sh = &sh;
-        if constexpr (mhe::WaveStaged<W>::value) w.stage = smem.data();
-        for (int wv = 0; wv < a.nwaves; ++wv) {
-            kf_cov_body<W, NX>(w, a, mode, wv);
-            w.sync();
-        }
-    });
-}
-
-}  // namespace
-
 hipError_t launch_kf_cov(const CovArgs& a, int mode, hipStream_t) {
-    if (a.B < 1 || a.nwaves < 1 || a.nx > a.NX || a.nym > a.NX) return hipErrorInvalidValue;
-    switch (a.NX) {
-        case 4: run_cov<EmuKfRowWave, 4>(a, mode); break;
-        case 8: run_cov<EmuKfRowWave, 8>(a, mode); break;
-        case 12: run_cov<EmuKfRowWave, 12>(a, mode); break;
-        case 16: run_cov<EmuKfRowWave, 16>(a, mode); break;
-        case 24: run_cov<EmuKfWideWave, 24>(a, mode); break;
-        case 32: run_cov<EmuKfWideWave, 32>(a, mode); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipSuccess;
+    if (!kf_cov_args_ok(a)) return hipErrorInvalidValue;
+    return mhe::dispatch_nx<mhe::NX_NARROW | mhe::NX_WIDE>(a.NX, [&]<int NX>(mhe::Cols<NX>) {
+        using W = mhe::EmuRowWaveFor<NX>;
+        mhe::run_row_waves<W>(a.nwaves, 0, [&](W& w, int wv, double*) { kf_cov_body<W, NX>(w, a, mode, wv); });
+    });
 }
 // two "persistent" wavefronts: the grid-stride loop is exercised
 int kf_cov_waves_for(int, int B, int NX) {

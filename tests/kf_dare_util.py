@@ -1,9 +1,7 @@
-"""Helpers of the steady-state Riccati solve tests (csrc/kf_dare_bodies.h behind mpcqp_kf_set_steady): the recipe of the
-fourth CPU emulator library (the objects of tests/kf_util.build_kf_emulib + emu_kf_cov.o + tests/emu/emu_kf_dare.cpp), SciPy's
-solution of the predictor DARE as the reference, and the case runners that tests/test_kf_dare.py (emulator) and
-tests/test_gpu_kf_dare.py (HIP library) share."""
-import os
-import subprocess
+"""Helpers of the steady-state Riccati solve tests (csrc/kf_dare_bodies.h behind mpcqp_kf_set_steady): SciPy's
+solution of the predictor DARE as the reference, and the case runners that tests/test_kf_dare.py (emulator: the launcher of
+tests/emu/emu_kf_dare.cpp in tests/emu/libmpcqp_emu_est.so, tests/emu_util.py) and tests/test_gpu_kf_dare.py (HIP library)
+share."""
 import warnings
 
 import numpy as np
@@ -12,23 +10,7 @@ import mpcqp
 from mpcqp import synth
 from tests import kf_util as ku
 
-EMU, CSRC = ku.EMU, ku.CSRC
 MAX_ITER = 40           # DARE_MAX_ITER of csrc/kf_dare_launch.h
-
-
-def build_kf_dare_emulib():
-    """tests/emu/libmpcqp_emu_kf_dare.so: the objects of libmpcqp_emu_kf.so plus the Riccati launchers."""
-    ku.build_kf_emulib()
-    objs = [os.path.join(EMU, o) for o in ("emu_launch.o", "emu_mhe.o", "emu_ms.o", "host.o", "mhe_host.o", "emu_kf_cov.o")]
-    src, obj, so = (os.path.join(EMU, n) for n in ("emu_kf_dare.cpp", "emu_kf_dare.o", "libmpcqp_emu_kf_dare.so"))
-    deps = [src, os.path.join(EMU, "emu_fiber.h")] + [os.path.join(CSRC, h) for h in (
-        "kf_dare_bodies.h", "kf_dare_launch.h", "kf_cov_bodies.h", "kf_cov_launch.h", "mhe_bodies.h", "mhe_types.h", "mpcqp_types.h")]
-    cxx = ["g++", "-std=c++20", "-O2", "-g", "-fPIC", "-pthread", "-I" + os.path.join(EMU, "fakehip"), "-I" + CSRC]
-    if ku._stale(obj, deps):
-        subprocess.check_call(cxx + ["-c", src, "-o", obj])
-    if ku._stale(so, objs + [obj]):
-        subprocess.check_call(cxx + ["-shared"] + objs + [obj, "-o", so])
-    return so
 
 
 def scipy_dare(sh):

@@ -1,9 +1,8 @@
 """Helpers of the time-varying KalmanFilter tests (covariance / gain recursion of csrc/kf_cov_bodies.h behind the LinMPC
 loop): a NumPy batch recursion written from the reference (src/estimator/kalman.jl:1235-1264 correct_estimate_kf!,
-1275-1290 predict_estimate_kf!) with the drop policy of include/mpcqp.h, the recipe of the third CPU emulator library (stock
-objects of tests/emu/Makefile + tests/emu/emu_kf_cov.cpp), the shapes of the tests and their case runners."""
+1275-1290 predict_estimate_kf!) with the drop policy of include/mpcqp.h, the shapes of the tests and their case runners.  On the CPU
+the launcher is tests/emu/emu_kf_cov.cpp in tests/emu/libmpcqp_emu_est.so (tests/emu_util.py)."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,27 +14,7 @@ if ROOT not in sys.path:
 import mpcqp  # noqa: E402
 from mpcqp import synth  # noqa: E402
 
-EMU = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "modelpredictivecontrol.jl_amd", "csrc")
 BAR = 1e-11         # K̂ and P̂ against the NumPy recursion, relative to max(1, max|.|) (see tests/test_gpu_kf_cov.py)
-
-
-def _stale(target, deps):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in deps)
-
-
-def build_kf_emulib():
-    """tests/emu/libmpcqp_emu_kf.so: the objects of the stock emulator library plus the covariance launchers."""
-    subprocess.check_call(["make", "-s", "-C", EMU])
-    objs = [os.path.join(EMU, o) for o in ("emu_launch.o", "emu_mhe.o", "emu_ms.o", "host.o", "mhe_host.o")]
-    src, obj, so = (os.path.join(EMU, n) for n in ("emu_kf_cov.cpp", "emu_kf_cov.o", "libmpcqp_emu_kf.so"))
-    deps = [src, os.path.join(EMU, "emu_fiber.h")] + [os.path.join(CSRC, h) for h in ("kf_cov_bodies.h", "kf_cov_launch.h", "mhe_bodies.h", "mhe_types.h", "mpcqp_types.h")]
-    cxx = ["g++", "-std=c++20", "-O2", "-g", "-fPIC", "-pthread", "-I" + os.path.join(EMU, "fakehip"), "-I" + CSRC]
-    if _stale(obj, deps):
-        subprocess.check_call(cxx + ["-c", src, "-o", obj])
-    if _stale(so, objs + [obj]):
-        subprocess.check_call(cxx + ["-shared"] + objs + [obj, "-o", so])
-    return so
 
 
 class NumpyKalmanCov:

@@ -1,10 +1,9 @@
-"""Helpers of the wide MovingHorizonEstimator tests (16 < max(nx̂, nym) <= 32, one estimator per wavefront): the recipe of the
-second CPU emulator library (stock objects of tests/emu/Makefile + tests/emu/emu_mhe_wide.cpp), window-long bounds on a
-given configuration, randomised wide families, and the cases of tests/test_mhe_wide.py (also runnable in a child
+"""Helpers of the wide MovingHorizonEstimator tests (16 < max(nx̂, nym) <= 32, one estimator per wavefront; on the CPU: the
+launchers of tests/emu/emu_mhe_wide.cpp in tests/emu/libmpcqp_emu_est.so, tests/emu_util.py): window-long bounds on a given
+configuration, randomised wide families, and the cases of tests/test_mhe_wide.py (also runnable in a child
 process: `python -m tests.mhe_wide_util <library>` prints them as JSON, which is how the lane orders are compared)."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -18,26 +17,6 @@ from mpcqp import synth  # noqa: E402
 from tests import mhe_util  # noqa: E402
 
 TOL = 2e-6          # tests/test_gpu_mhe.py: this interior-point method against the exact active-set optimum
-
-
-def _stale(target, deps):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in deps)
-
-
-def build_wide_emulib():
-    """tests/emu/libmpcqp_emu_wide.so: the objects of the stock emulator library plus the wide launchers."""
-    d = os.path.join(ROOT, "tests", "emu")
-    csrc = os.path.join(ROOT, "modelpredictivecontrol.jl_amd", "csrc")
-    subprocess.check_call(["make", "-s", "-C", d])
-    objs = [os.path.join(d, o) for o in ("emu_launch.o", "emu_mhe.o", "emu_ms.o", "host.o", "mhe_host.o")]
-    src, obj, so = (os.path.join(d, n) for n in ("emu_mhe_wide.cpp", "emu_mhe_wide.o", "libmpcqp_emu_wide.so"))
-    deps = [src, os.path.join(d, "emu_fiber.h")] + [os.path.join(csrc, h) for h in ("mhe_bodies.h", "mhe_types.h", "mhe_wide_launch.h", "mpcqp_types.h")]
-    cxx = ["g++", "-std=c++20", "-O2", "-g", "-fPIC", "-pthread", "-I" + os.path.join(d, "fakehip"), "-I" + csrc]
-    if _stale(obj, deps):
-        subprocess.check_call(cxx + ["-c", src, "-o", obj])
-    if _stale(so, objs + [obj]):
-        subprocess.check_call(cxx + ["-shared"] + objs + [obj, "-o", so])
-    return so
 
 
 def window_long_bounds(cfg, lib=None, B=3, seed=21, soft=False, nper=9, csoft=False, eps_seen=None, oracle_only=False):
@@ -177,7 +156,7 @@ SOFT20 = dict(c_xhatmin=[1.0] * 20, c_xhatmax=[1.0] * 20, c_whatmin=[0.5] * 20, 
 
 
 def emulator_cases(lib):
-    """The three cases of tests/test_mhe_wide.py on the wide emulator library: worst relative errors per case."""
+    """The three cases of tests/test_mhe_wide.py on an emulator library with the wide launchers: worst relative errors per case."""
     out = {}
     # hard x̂ bounds, nx̂ = 17 (NX = 24): first row of the GPU table
     cfg = synth.MheConfig("w17", nx=14, nu=2, nym=3, nd=0, He=4, xabs=1.2)

@@ -14,6 +14,7 @@ import pytest
 import mpcqp
 from mpcqp import synth
 from oracle import condense as cd, estim as es
+from tests import emu_util
 from tests.parity_util import make_oracle, oracle_batch, rel_err, run_batch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,7 +46,7 @@ def test_c_client_runs_a_step_on_cpu_emulator(tmp_path, emulib):
     import subprocess
     from tests.parity_util import build_c_client, write_c_fixture
     exe, fx = str(tmp_path / "abi_c_client_emu"), str(tmp_path / "c2.bin")
-    build_c_client(exe, os.path.join(ROOT, "tests", "emu", "libmpcqp_emu.so"), ROOT)
+    build_c_client(exe, emu_util.build(), ROOT)
     write_c_fixture(fx, "C2", 4)
     out = subprocess.run([exe, "run", fx], capture_output=True, text=True)
     assert out.returncode == 0 and "run ok" in out.stdout, out.stdout + out.stderr
@@ -71,9 +72,7 @@ def test_move_blocking_matches_reference_rules():
 
 @pytest.fixture(scope="session")
 def emulib():
-    d = os.path.join(ROOT, "tests", "emu")
-    subprocess.check_call(["make", "-s", "-C", d])
-    lib = mpcqp.api.load_library(os.path.join(d, "libmpcqp_emu.so"))
+    lib = mpcqp.api.load_library(emu_util.build())
     yield lib
     mpcqp.api._lib = None
 

@@ -12,6 +12,7 @@ import mpcqp
 from mpcqp import synth
 from oracle import estim as es
 from oracle import mhe as om
+from tests import emu_util
 from tests import kf_util as ku
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,7 +54,7 @@ def test_numpy_recursion_drops_an_indefinite_update():
 
 @pytest.fixture(scope="module")
 def kflib():
-    lib = mpcqp.api.load_library(ku.build_kf_emulib())
+    lib = mpcqp.api.load_library(emu_util.build(emu_util.EST))
     yield lib
     mpcqp.api._lib = None
 
@@ -112,8 +113,7 @@ def test_emulator_fused_modes_and_dropped_update(kflib):
 
 def test_stock_emulator_refuses_the_time_varying_filter():
     """A library without the kernel unit links (weak launcher) and answers MPCQP_ERR_UNSUPPORTED; the steady gain still works."""
-    subprocess.check_call(["make", "-s", "-C", ku.EMU])
-    lib = mpcqp.api.load_library(os.path.join(ku.EMU, "libmpcqp_emu.so"))
+    lib = mpcqp.api.load_library(emu_util.build())
     try:
         sh = ku.shape_c2(B=2)
         h = mpcqp.api.Handle(2, sh["nxh"], sh["nu"], sh["ny"], 0, 2, 1, lib=lib)
@@ -162,13 +162,10 @@ def test_mirror_validates_like_the_reference():
 def test_host_code_under_sanitizers(tmp_path):
     """csrc/mpcqp_host.hip compiled for the host with -fsanitize=address,undefined into tests/kf_asan_main.cpp (its own main):
     covariances set, three periods on the emulator objects, read-backs, handle destroyed.  No sanitizer goes into Python."""
-    ku.build_kf_emulib()
-    emu = ku.EMU
-    objs = [os.path.join(emu, o) for o in ("emu_launch.o", "emu_mhe.o", "emu_ms.o", "mhe_host.o", "emu_kf_cov.o")]
+    emu_util.build(emu_util.EST)
     exe = str(tmp_path / "kf_asan")
-    cxx = ["g++", "-std=c++20", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-I" + os.path.join(emu, "fakehip"), "-I" + ku.CSRC]
-    subprocess.check_call(cxx + ["-x", "c++", os.path.join(ku.CSRC, "mpcqp_host.hip"), os.path.join(ROOT, "tests", "kf_asan_main.cpp"),
-                                 "-x", "none"] + objs + ["-ldl", "-o", exe])
+    subprocess.check_call(emu_util.SANITIZER_CXX + ["-x", "c++", os.path.join(emu_util.CSRC, "mpcqp_host.hip"),
+                                                    os.path.join(ROOT, "tests", "kf_asan_main.cpp"), "-x", "none"]
+                          + emu_util.SANITIZER_OBJS + ["-ldl", "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert out.returncode == 0 and "kf asan ok" in out.stdout, out.stdout + out.stderr

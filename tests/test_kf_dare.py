@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import mpcqp
+from tests import emu_util
 from tests import kf_dare_util as du
 from tests import kf_util as ku
 
@@ -20,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def darelib():
-    lib = mpcqp.api.load_library(du.build_kf_dare_emulib())
+    lib = mpcqp.api.load_library(emu_util.build(emu_util.EST))
     yield lib
     mpcqp.api._lib = None
 
@@ -128,8 +129,7 @@ def test_refused_beyond_32_states(darelib):
 
 def test_stock_emulator_refuses_the_steady_solve():
     """A library without the launcher links (weak declaration) and answers MPCQP_ERR_UNSUPPORTED; a kf_set gain still works."""
-    subprocess.check_call(["make", "-s", "-C", ku.EMU])
-    lib = mpcqp.api.load_library(os.path.join(ku.EMU, "libmpcqp_emu.so"))
+    lib = mpcqp.api.load_library(emu_util.build())
     try:
         sh = ku.shape_c2(B=2)
         h = du.make_handle(sh, lib=lib, steady=False)
@@ -170,13 +170,11 @@ def test_host_code_under_sanitizers(tmp_path):
     """csrc/mpcqp_host.hip compiled for the host with -fsanitize=address,undefined into tests/kf_dare_asan_main.cpp (its own
     main), with the emulator launcher compiled the same way: set, solve again after a model swap, read-backs, the refusals,
     handle destroyed.  No sanitizer goes into Python."""
-    du.build_kf_dare_emulib()
-    emu = ku.EMU
-    objs = [os.path.join(emu, o) for o in ("emu_launch.o", "emu_mhe.o", "emu_ms.o", "mhe_host.o", "emu_kf_cov.o")]
+    emu_util.build(emu_util.EST)
     exe = str(tmp_path / "kf_dare_asan")
-    cxx = ["g++", "-std=c++20", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-I" + os.path.join(emu, "fakehip"), "-I" + ku.CSRC]
-    subprocess.check_call(cxx + ["-x", "c++", os.path.join(ku.CSRC, "mpcqp_host.hip"), os.path.join(emu, "emu_kf_dare.cpp"),
-                                 os.path.join(ROOT, "tests", "kf_dare_asan_main.cpp"), "-x", "none"] + objs + ["-ldl", "-o", exe])
+    subprocess.check_call(emu_util.SANITIZER_CXX + ["-x", "c++", os.path.join(emu_util.CSRC, "mpcqp_host.hip"),
+                                                    os.path.join(emu_util.EMU, "emu_kf_dare.cpp"),
+                                                    os.path.join(ROOT, "tests", "kf_dare_asan_main.cpp"), "-x", "none"]
+                          + emu_util.SANITIZER_OBJS + ["-ldl", "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert out.returncode == 0 and "kf dare asan ok" in out.stdout, out.stdout + out.stderr

@@ -11,13 +11,14 @@ import numpy as np
 import pytest
 
 import mpcqp
+from tests import emu_util
 from tests import kf_direct_util as kd
 from tests import kf_util as ku
 
 
 @pytest.fixture(scope="module")
 def kflib():
-    lib = mpcqp.api.load_library(ku.build_kf_emulib())
+    lib = mpcqp.api.load_library(emu_util.build(emu_util.EST))
     yield lib
     mpcqp.api._lib = None
 

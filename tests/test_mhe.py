@@ -14,16 +14,14 @@ import pytest
 import mpcqp
 from mpcqp import mhe as pm
 from mpcqp import synth
-from tests import mhe_util
+from tests import emu_util, mhe_util
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def emulib():
-    d = os.path.join(ROOT, "tests", "emu")
-    subprocess.check_call(["make", "-s", "-C", d])
-    return mpcqp.api.load_library(os.path.join(d, "libmpcqp_emu.so"))
+    return mpcqp.api.load_library(emu_util.build())
 
 
 def test_library_exports_every_declared_mhe_symbol():

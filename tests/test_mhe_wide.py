@@ -1,7 +1,7 @@
 """The wide MovingHorizonEstimator kernels (16 < max(nx̂, nym) <= 32, one estimator per wavefront) on the CPU: the bodies of
 csrc/mhe_bodies.h with the 64-lane geometry, the plain-loop side of the staged products and the host's lane-stride handling,
-run on a second emulator library (tests/emu/libmpcqp_emu_wide.so: the stock objects + tests/emu/emu_mhe_wide.cpp) against
-oracle/mhe.py.  The stock emulator library has no wide launchers and keeps refusing such handles (tests/test_mhe.py).  The
+run on the emulator library with the estimator launchers (tests/emu/libmpcqp_emu_est.so: the stock objects +
+tests/emu/emu_mhe_wide.cpp and the Kalman-filter launchers) against oracle/mhe.py.  The stock emulator library has no wide launchers and keeps refusing such handles (tests/test_mhe.py).  The
 GPU tests are in test_gpu_mhe_wide.py."""
 import json
 import os
@@ -13,6 +13,7 @@ import pytest
 import mpcqp
 from mpcqp import mhe as pm
 from mpcqp import synth
+from tests import emu_util
 from tests import mhe_wide_util as wu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,7 +23,7 @@ CASES = ["xhat17", "soft20", "what+vhat18"]
 
 @pytest.fixture(scope="module")
 def widelib_path():
-    return wu.build_wide_emulib()
+    return emu_util.build(emu_util.EST)
 
 
 @pytest.fixture(scope="module")

@@ -1,8 +1,6 @@
 """MultipleShooting LinMPC without a GPU: the dense MultipleShooting oracle (oracle/ms.py) against the
 SingleShooting oracle and the reference's known answers, and the stage-structured kernel body (csrc/ms_bodies.h) on the
 CPU wave emulator against the oracle.  The GPU runs of the same cases are in tests/test_gpu_ms.py."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,16 +8,14 @@ import pytest
 import mpcqp
 from mpcqp import api
 from oracle import condense as cd, estim as es, ms, qp
+from tests import emu_util
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU = os.path.join(ROOT, "tests", "emu", "libmpcqp_emu.so")
 TOL = 1e-5
 
 
 @pytest.fixture(scope="module")
 def emulib():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emu")])
-    return api.load_library(EMU)
+    return api.load_library(emu_util.build())
 
 
 def _plant(rng, nx, nu, ny):

@@ -1,8 +1,6 @@
 """Custom linear constraints (Wy, Wu, Wd, Wr; construct.jl:1138-1160, execute.jl:337-364) on the stage-structured
 MultipleShooting kernel (csrc/ms_bodies.h), without a GPU: the kernel body on the CPU wave emulator against the condensed
 oracle (both transcriptions solve the same QP).  The GPU runs are in tests/test_gpu_ms_custom.py."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,17 +8,15 @@ import pytest
 import mpcqp
 from mpcqp import api
 from oracle import condense as cd
+from tests import emu_util
 from tests import ms_custom_util as mcu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU = os.path.join(ROOT, "tests", "emu", "libmpcqp_emu.so")
 TOL = 1e-5
 
 
 @pytest.fixture(scope="module")
 def emulib():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emu")])
-    return api.load_library(EMU)
+    return api.load_library(emu_util.build())
 
 
 def test_t9_under_multiple_shooting_runs_on_the_stage_kernel(emulib):

@@ -2,26 +2,22 @@
 stage-separable Hermitian weight blocks (M_Hp, N_Hc, L_Hp), MPCQP_FLAG_WARM_DUAL and MPCQP_FLAG_KEEP_QP -- the kernel body
 on the CPU wave emulator against the condensed oracle (both transcriptions solve the same QP).  The GPU runs are in
 tests/test_gpu_ms_options.py."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from mpcqp import api, synth
+from tests import emu_util
 from tests import ms_options_util as mou
 from tests.parity_util import rel_err
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU = os.path.join(ROOT, "tests", "emu", "libmpcqp_emu.so")
 TOL = 1e-5
 KEEP_TOL = mou.KEEP_TOL
 
 
 @pytest.fixture(scope="module")
 def emulib():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emu")])
-    return api.load_library(EMU)
+    return api.load_library(emu_util.build())
 
 
 def test_the_blocks_move_the_optimum_on_the_oracle():

@@ -16,8 +16,9 @@ import torch.multiprocessing as mp
 
 import mpcqp
 from mpcqp import sharding, synth
+from tests import emu_util
 
-EMU = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu", "libmpcqp_emu.so")
+EMU = os.path.join(emu_util.EMU, emu_util.STOCK)
 CFG = synth.Config("shard", nx=3, nu=2, ny=2, Hp=8, Hc=3, umin=-0.6, umax=0.7, ymax=0.9)
 
 
@@ -74,10 +75,7 @@ def _worker(rank, world, port, B, q):
 
 @pytest.fixture(scope="module")
 def emulib():
-    if not os.path.exists(EMU):
-        import subprocess
-        subprocess.check_call(["make", "-s", "-C", os.path.dirname(EMU)])
-    return mpcqp.api.load_library(EMU)
+    return mpcqp.api.load_library(emu_util.build())
 
 
 def test_shard_range_partitions_the_batch():

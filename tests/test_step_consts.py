@@ -25,9 +25,9 @@ import pytest
 import mpcqp
 from mpcqp import synth
 from oracle import condense as cd, qp
+from tests import emu_util
 from tests import team_util as tu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B = 64
 TOL = 1e-5          # the oracle tolerance of tests/test_gpu_parity.py (relative dU error of a solve)
 OUT = ("Z", "u0", "status", "iters", "Yhat")
@@ -248,16 +248,14 @@ def test_updated_handle_equals_fresh_handle_team_of_two(hiplib, monkeypatch, tmp
 # ---- 5. the CPU emulator: linked without the block's kernel, the handle never carries the block
 @pytest.fixture(scope="module")
 def emulib():
-    d = os.path.join(ROOT, "tests", "emu")
-    subprocess.check_call(["make", "-s", "-C", d])
-    lib = mpcqp.api.load_library(os.path.join(d, "libmpcqp_emu.so"))
+    lib = mpcqp.api.load_library(emu_util.build())
     yield lib
     mpcqp.api._lib = None
 
 
 @pytest.mark.slow
 def test_updated_handle_equals_fresh_handle_on_cpu_emulator(emulib):
-    syms = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "tests", "emu", "libmpcqp_emu.so")],
+    syms = subprocess.run(["nm", "-D", "--defined-only", emu_util.build()],
                           capture_output=True, text=True).stdout
     assert "launch_step_consts" not in syms         # the emulator keeps the path that forms the values inside the step
     fresh_versus_updated(synth.C3, C3_NB, emulib, B=6, block=False)
