@@ -270,6 +270,25 @@ MPCQP_HD constexpr bool one_row_per_lane() {
     else return false;
 }
 
+// Layout of Phi in LDS: column-block-major (phi(), mpcqp_types.h) in the device code of the one-row-per-lane kernels that run on
+// one wavefront; row-major packed (pk()) in the runtime-dimension, several-rows-per-lane and team kernels and in the CPU
+// emulator.  Packed H̃ in GLOBAL memory (Model::Hpk) is pk() everywhere.
+template <class W, class DM>
+MPCQP_HD constexpr bool phi_layout() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (DM::is_static) return DM::nZ <= WAVE && W::NTEAM == 1;
+    else return false;
+#else
+    return false;
+#endif
+}
+// index of entry (i, j), i >= j (or a pad of row i), of Phi in LDS
+template <class W, class DM>
+MPCQP_HD constexpr int phi_ix(int i, int j) {
+    if constexpr (phi_layout<W, DM>()) return phi(DM::nZ, i, j);
+    else return pk(i, j);
+}
+
 // Ŷ-row slots per lane whose output weights a one-row-per-lane kernel keeps in registers (Step::hwy_; 0: not cached)
 template <class DM>
 MPCQP_HD constexpr int hwq_() {
@@ -913,20 +932,25 @@ struct Qp {
     }
     // ow: P is OVERWRITTEN with (Hg ? H̃ : 0) + scale * E'DE on the whole stored triangle (Hg == nullptr: the weights of H̃
     // ride in dd, Step::fold_H)
+    // PH: P is Phi of a kernel with the column-block-major layout (phi_layout(); Hg stays pk())
+    template <bool PH = false>
     __device__ __forceinline__ int EtDE_add_mfma(const double* dd, double* P, double scale, const double* tb,
                                                  const double* Hg = nullptr, bool ow = false) {
         // (a team of wavefronts splits the passes over the tile rows: W::NTEAM, mpcqp_devwave.h)
         if constexpr (W::NTEAM > 1) { static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_ETDE, (int)(dd - sm), (int)(P - sm), tb ? (int)(tb - sm) : 0, (ow ? 1 : 0) | (Hg ? 2 : 0) | (tb ? 4 : 0), scale); }
-        const int e = EtDE_share(dd, P, scale, tb ? tb : dd, Hg, ow, tb != nullptr);
+        const int e = EtDE_share<PH>(dd, P, scale, tb ? tb : dd, Hg, ow, tb != nullptr);
         if constexpr (W::NTEAM > 1) w.join();
         return e;
     }
     // (a forwarding layer of its own: merged into EtDE_share_, the compiler schedules the E'DE assembly differently)
+    template <bool PH = false>
     __device__ __forceinline__ int EtDE_share(const double* dd, double* P, double scale, const double* tb, const double* Hg, bool ow, bool has_tb) {
-        return EtDE_share_(dd, P, scale, tb, Hg, ow, has_tb);
+        return EtDE_share_<PH>(dd, P, scale, tb, Hg, ow, has_tb);
     }
     // (tb: a pointer into LDS also when there is no ϵ row to ride -- has_tb says so: a select with nullptr makes the pointer generic)
+    template <bool PH>
     __device__ __forceinline__ int EtDE_share_(const double* dd, double* P, double scale, const double* tb, const double* Hg, bool ow, bool has_tb) {
+        static_assert(!PH || phi_layout<W, DM>(), "column-block-major Phi outside its kernels");
         ow = ow || Hg != nullptr;
         constexpr int NU = DM::nu, NY = DM::ny, NDU = DM::nDU, NYR = DM::nY, SP = DM::sp, RS = DM::rs;
         constexpr int NT = (NDU + 15) / 16, NK = (NYR + 3) / 4;
@@ -1000,9 +1024,27 @@ struct Qp {
                 const bool low = J < I || li <= il;
                 return colok && ((rowok && low) || (eI && il == LE));
             };
-            auto entry_idx = [&](int I, int J, int reg) {
+            auto entry_idx_pk = [&](int I, int J, int reg) {
                 const int G = 4 * I + reg;
                 return 8 * G * (G + 1) + 16 * J + 4 * (G + 1) * lk + li;
+            };
+            // column-block-major Phi: phi(i, ip) = [phi_col(16 J + li) + 4 lk] + 64 I + 16 reg -- one per-lane base per tile
+            // column, the rest an immediate
+            // (eb[J], formed once per pass in front of the write-back: written out per entry, the quadratic column offset is
+            //  recomputed inside the conditional block of every entry.  With q = li >> 2 the tile columns differ by a
+            //  constant and a multiple of q: phi_col(16 J + li) = phi_col(li) + 16 J (n - 2 - 8 J) - 64 J q)
+            int eb[MAXT];
+            auto entry_base = [&]() {
+                if constexpr (PH) {
+                    const int q_ = li >> 2;
+                    const int eb0 = 4 * q_ * (DM::nZ - 2 - 2 * q_) + (li & 3) + 4 * lk;      // phi_col(li) + 4 lk
+                    MPCQP_UNROLL
+                    for (int J = 0; J <= I1; ++J) eb[J] = eb0 + 16 * J * (DM::nZ - 2 - 8 * J) - 64 * J * q_;
+                }
+            };
+            auto entry_idx = [&](int I, int J, int reg) {
+                if constexpr (PH) return eb[J] + 64 * I + 16 * reg;
+                else return entry_idx_pk(I, J, reg);
             };
             // H̃ in the accumulator layout, requested now and consumed by the write-back
             // (register-operand form: requested after the K loop instead -- 24 more doubles live next to V, the accumulators and
@@ -1015,7 +1057,7 @@ struct Qp {
                     for (int J = 0; J <= I; ++J) {
                         MPCQP_UNROLL
                         for (int reg = 0; reg < 4; ++reg)
-                            hreg[I - I0][J][reg] = Hg[entry_ok(I, J, reg) ? (unsigned)entry_idx(I, J, reg) : 0u];
+                            hreg[I - I0][J][reg] = Hg[entry_ok(I, J, reg) ? (unsigned)entry_idx_pk(I, J, reg) : 0u];
                     }
                 }
             };
@@ -1150,6 +1192,7 @@ struct Qp {
             }
             }
             if (Hg && VREG) hload();
+            entry_base();
             if (ow) {
                 // plain stores of H̃ + scale acc (or scale acc alone) on the stored triangle
                 MPCQP_UNROLL
@@ -1185,21 +1228,22 @@ struct Qp {
             }
         };
         etde_passes<0, NT>(pass);
+        auto pix = [](int i, int j) { if constexpr (PH) return phi(DM::nZ, i, j); else return pk(i, j); };
         if constexpr (DM::neps != 0 && W::WV == 0) {
             if (ow && !Hg) {             // (same as below with H̃'s ϵ row: zero off the diagonal; the caller adds 2 C to the diagonal)
                 if constexpr (IE >= NT) {
-                    for (int k = w.lane; k < NDU; k += WAVE) P[pk(NDU, k)] = 0.0;
+                    for (int k = w.lane; k < NDU; k += WAVE) P[pix(NDU, k)] = 0.0;
                 }
-                if (w.lane == 0) P[pk(NDU, NDU)] = 0.0;
+                if (w.lane == 0) P[pix(NDU, NDU)] = 0.0;
             } else if (Hg) {
                 // nDU a multiple of 16: the ϵ row (index nDU) starts a tile row of its own that no pass covers -- in
                 // the overwrite mode nothing else initialises it (the caller adds E'tb to it: eps_t0 stays -1), and the
                 // row would keep the previous factor's entries: a wrong Newton matrix, twice the iterations and
                 // failed solves on every shape with nu Hc = 16, 32, 48, .. (found at nZ~ = 81, round 3)
                 if constexpr (IE >= NT) {
-                    for (int k = w.lane; k < NDU; k += WAVE) P[pk(NDU, k)] = Hg[pk(NDU, k)];
+                    for (int k = w.lane; k < NDU; k += WAVE) P[pix(NDU, k)] = Hg[pk(NDU, k)];
                 }
-                if (w.lane == 0) P[pk(NDU, NDU)] = Hg[pk(NDU, NDU)];     // Ñ's slack weight (construct.jl:842)
+                if (w.lane == 0) P[pix(NDU, NDU)] = Hg[pk(NDU, NDU)];     // Ñ's slack weight (construct.jl:842)
             }
         }
         return eps_t0;
@@ -1209,10 +1253,11 @@ struct Qp {
     // P[pk(i,i')] += scale * sum_r E[r,i] dd[r] E[r,i']   (i >= i' < nDU).  When `tb` is given
     // and the matrix-core path runs, the ϵ row P[pk(nDU, i')] += sum_r tb[r] E[r,i'] is added for the
     // rows of the steps t >= the returned value; the caller adds the rest (Et_apply_add; -1: all of it).
+    template <bool PH = false>
     MPCQP_HD int EtDE_add(const double* dd, double* P, double scale = 1.0, const double* tb = nullptr,
                           const double* Hg = nullptr, bool ow = false) {
 #if defined(__HIP_DEVICE_COMPILE__)
-        if constexpr (DM::is_static) return EtDE_add_mfma(dd, P, scale, tb, Hg, ow);
+        if constexpr (DM::is_static) return EtDE_add_mfma<PH>(dd, P, scale, tb, Hg, ow);
 #endif
         // Strips of four: the packed layout (pk) stores row i as (i/4 + 1) aligned chunks of four
         // columns, chunk s of the whole triangle at P[4s..4s+3].  A lane takes a strip (i, ip0..ip0+3):
@@ -1759,6 +1804,13 @@ struct Step {
         for (int q_ = 1; q_ < HWQ; ++q_) v = (k >= WAVE * q_) ? hwy_[q_] : v;
         return v;
     }
+
+    // Phi in LDS: column-block-major in the one-row-per-lane kernels on one wavefront, pk() everywhere else (phi_layout())
+    static constexpr bool PHL = phi_layout<W, DM>();
+    MPCQP_HD static constexpr int ix(int i, int j) { return phi_ix<W, DM>(i, j); }
+    // PHL: phi(i, j) = rowoff(i) + coloff(j); with j a constant the second term is an immediate of the LDS instruction
+    MPCQP_HD static constexpr int rowoff(int i) { if constexpr (PHL) return 4 * i; else return pk(i, 0); }
+    MPCQP_HD static constexpr int coloff(int j) { if constexpr (PHL) return phi_col(DM::nZ, j); else return j; }
 
     MPCQP_HD Step(Qp<W, DM>& qp_)
         : qp(qp_), w(qp_.w), d(qp_.d), m(qp_.m), b(qp_.b), sm(qp_.sm), c(qp_.c),
@@ -2471,6 +2523,26 @@ struct Step {
     MPCQP_HD void load_H_share() {
         const double* H = m.Hpk + (size_t)b * d.npk;
         constexpr int NB = 8;
+        if constexpr (PHL) {
+            // the global image is pk(): slot s of the column-block layout is entry (i, j) of block cb (pads included: both
+            // layouts hold the same entries), fetched from pk(i, j)
+            constexpr int n_ = DM::nZ, G_ = (n_ + 3) / 4, NPK = pk_size(n_);
+            for (int i0 = 0; i0 < NPK; i0 += NB * WAVE) {
+                double v[NB];
+                MPCQP_UNROLL
+                for (int q_ = 0; q_ < NB; ++q_) {
+                    const int s_ = i0 + w.lane + WAVE * q_, ss = s_ < NPK ? s_ : 0;
+                    int cb = 0;
+                    MPCQP_UNROLL
+                    for (int c2 = 1; c2 < G_; ++c2) cb += (ss >= phi_blk(n_, c2)) ? 1 : 0;
+                    const int o = ss - phi_blk(n_, cb);
+                    v[q_] = H[pk(4 * cb + (o >> 2), 4 * cb + (o & 3))];
+                }
+                MPCQP_UNROLL
+                for (int q_ = 0; q_ < NB; ++q_) { const int s_ = i0 + w.lane + WAVE * q_; if (s_ < NPK) Phi[s_] = v[q_]; }
+            }
+            return;
+        }
         const int n = d.npk, stride = WAVE * W::NTEAM;
         for (int i0 = WAVE * W::WV; i0 < n; i0 += NB * stride) {
             double v[NB];
@@ -2509,7 +2581,7 @@ struct Step {
             const int j = k / nu, cc = k - j * nu;
             const double suf = tU[k];
             MPCQP_PRAGMA(unroll MPCQP_URMW_UNROLL)
-            for (int j2 = 0; j2 <= j; ++j2) Phi[pk(k, j2 * nu + cc)] += suf;
+            for (int j2 = 0; j2 <= j; ++j2) Phi[ix(k, j2 * nu + cc)] += suf;
         }
     }
     // terminal rows: ex̂' dX ex̂
@@ -2521,7 +2593,7 @@ struct Step {
             Qp<W, DM>::unpack_idx(idx, i, ip);
             double acc = 0.0;
             for (int r = 0; r < d.nxh; ++r) acc += qp.Xat(r, i) * tX[r] * qp.Xat(r, ip);
-            Phi[pk(i, ip)] += acc;
+            Phi[ix(i, ip)] += acc;
         }
     }
     // custom rows: E_w' dW E_w, rows formed on the fly (set-up-grade path)
@@ -2539,7 +2611,7 @@ struct Step {
                         const double dk = dW[t * nw + iw];
                         if (dk != 0.0) acc += dk * qp.Ew_at(t, iw, j, cc) * qp.Ew_at(t, iw, j2, c2);
                     }
-                Phi[pk(i, ip)] += acc;
+                Phi[ix(i, ip)] += acc;
             }
         }
     }
@@ -2583,7 +2655,7 @@ struct Step {
         int eps_t0 = -1;          // first step whose Ŷ rows the matrix-core path put into the ϵ row
         if (qp.pair_on(P_Y)) {
             MPCQP_TIC();
-            eps_t0 = qp.EtDE_add(sm + c.tA[P_Y], Phi, 1.0, d.neps ? sm + c.tB[P_Y] : nullptr,
+            eps_t0 = qp.template EtDE_add<PHL>(sm + c.tA[P_Y], Phi, 1.0, d.neps ? sm + c.tB[P_Y] : nullptr,
                                  (phi_direct() && !fold_H) ? m.Hpk + (size_t)b * d.npk : nullptr, fold_H && etde_overwrites());
             w.sync();      // the MFMA write-back uses its own entry->lane map
             MPCQP_TOC(4);
@@ -2599,21 +2671,30 @@ struct Step {
             const int j = k / nu, cc = k - j * nu;
             const double suf = qp.block_suffix(w.lane < nDU ? tU[k] : 0.0);
             double* const trash = sm + c.zero + 4;
-            double* const row = Phi + pk(k, cc);
+            double* const row = Phi + (PHL ? 0 : pk(k, cc));
+            // entry (k, j2 nu + cc) of the lane's row (PHL with nu = 4: column block j2, 4 k + cc plus an immediate)
+            auto urow = [&](int j2) -> double* {
+                if constexpr (PHL) {
+                    if constexpr (DM::nu == 4) return Phi + 4 * k + cc + phi_col(DM::nZ, 4 * j2);
+                    else return Phi + ix(k, j2 * nu + cc);
+                } else {
+                    return row + j2 * nu;
+                }
+            };
             if constexpr (DM::is_static) {
                 // all reads, then all writes (entry by entry the trash slot's possible aliasing serialises Hc LDS round trips)
                 double* q_[DM::Hc];
                 double old_[DM::Hc];
                 MPCQP_UNROLL
                 for (int j2 = 0; j2 < DM::Hc; ++j2) {
-                    q_[j2] = (j2 <= j && w.lane < nDU) ? row + j2 * nu : trash;
+                    q_[j2] = (j2 <= j && w.lane < nDU) ? urow(j2) : trash;
                     old_[j2] = *q_[j2];
                 }
                 MPCQP_UNROLL
                 for (int j2 = 0; j2 < DM::Hc; ++j2) *q_[j2] = old_[j2] + suf;
             } else {
                 for (int j2 = 0; j2 < d.Hc; ++j2) {
-                    double* const q_ = (j2 <= j && w.lane < nDU) ? row + j2 * nu : trash;
+                    double* const q_ = (j2 <= j && w.lane < nDU) ? urow(j2) : trash;
                     *q_ += suf;
                 }
             }
@@ -2646,7 +2727,7 @@ struct Step {
             if (k < nDU && qp.pair_on(P_DU)) acc += sm[c.tA[P_DU] + k];
             if (k == nZ - 1 && d.neps) acc += ee;
             if (fold_H) acc += one_row_per_lane<DM>() ? h2n_ : H2N_load(k);
-            Phi[pk(k, k)] += acc;
+            Phi[ix(k, k)] += acc;
         }
         // ϵ row: Phi[eps, k] += sum_pairs L_P' tB     (staged in dz, which is free here)
         if (d.neps) {
@@ -2670,7 +2751,7 @@ struct Step {
                 st[k] = acc;
             }
             if (epsY && eps_t0 != 0) qp.Et_apply_add(sm + c.tB[P_Y], st, 1.0, eps_t0);   // same lane owns st[k]
-            for (int k = w.lane; k < nDU; k += WAVE) Phi[pk(nZ - 1, k)] += st[k];
+            for (int k = w.lane; k < nDU; k += WAVE) Phi[ix(nZ - 1, k)] += st[k];
         }
         w.sync();
         MPCQP_TOCK(5, tic5_);
@@ -2732,23 +2813,34 @@ struct Step {
             MPCQP_UNROLL
             for (int I = P; I < NT; ++I) {
                 const int row = 16 * I + li < n ? 16 * I + li : n - 1;
-                X[I] = Phi + pk(row, 0) + lk;
+                if constexpr (!PHL) X[I] = Phi + pk(row, 0) + lk;
                 acc[I] = v4d_{0.0, 0.0, 0.0, 0.0};
             }
+            // PHL: operand (row tile I, K step kk) = xop(I)[coloff(4 kk) + 64 I] -- ONE per-lane register (row li of tile 0,
+            // column lk) plus an immediate; the clamped rows of a ragged last tile keep a second one
+            const double* const xb = Phi + 4 * li + lk;
+            const int lrow = 16 * (NT - 1) + li < n ? 16 * (NT - 1) + li : n - 1;
+            const double* const xl = (n % 16 == 0) ? xb : Phi + 4 * lrow + lk - 64 * (NT - 1);
+            auto Xop = [&](int I, int kk) -> double {
+                if constexpr (PHL) return (I == NT - 1 ? xl : xb)[coloff(4 * kk) + 64 * I];
+                else return X[I][4 * kk];
+            };
             if constexpr (team_any_mfma<W>(NT - P)) {
             MPCQP_PRAGMA(unroll MPCQP_PANEL_UNROLL)
             for (int kk = 0; kk < 4 * P; ++kk) {
-                const double bb = X[P][4 * kk];
+                const double bb = Xop(P, kk);
                 // (one row per lane, M D M' form: one operand carries d of its column, the d vector sits in gt; the
                 //  several-rows-per-lane factorisation that shares this function is LL')
                 const double bs = one_row_per_lane<DM>() ? bb * gt[4 * kk + lk] : bb;
                 if (mine(P)) acc[P] = __builtin_amdgcn_mfma_f64_16x16x4f64(bb, bs, acc[P], 0, 0, 0);
                 MPCQP_UNROLL
                 for (int I = P + 1; I < NT; ++I)
-                    if (mine(I)) acc[I] = __builtin_amdgcn_mfma_f64_16x16x4f64(X[I][4 * kk], bs, acc[I], 0, 0, 0);
+                    if (mine(I)) acc[I] = __builtin_amdgcn_mfma_f64_16x16x4f64(Xop(I, kk), bs, acc[I], 0, 0, 0);
             }
             }
             double* const trash = sm + c.zero + 4;        // unconditional write-back, see EtDE_add_mfma
+            // PHL: entry (16 I + lk + 4 reg, 16 P + li) = wb[64 I + 16 reg]: the column block depends on the lane, one base per call
+            double* const wb = Phi + (PHL ? phi_col(n, 16 * P + li) + 4 * lk : 0);
             MPCQP_UNROLL
             for (int I = P; I < NT; ++I) {
                 if (!mine(I)) continue;
@@ -2757,7 +2849,12 @@ struct Step {
                 MPCQP_UNROLL
                 for (int reg = 0; reg < 4; ++reg) {
                     const int row = 16 * I + lk + 4 * reg, col = 16 * P + li;
-                    pp_[reg] = (row < n && col <= row) ? Phi + pk(row, col) : trash;
+                    if constexpr (PHL) {
+                        const bool ok = (16 * I + 15 < n || row < n) && (I > P || col <= row);
+                        pp_[reg] = ok ? wb + 64 * I + 16 * reg : trash;
+                    } else {
+                        pp_[reg] = (row < n && col <= row) ? Phi + pk(row, col) : trash;
+                    }
                     old_[reg] = *pp_[reg];
                 }
                 MPCQP_UNROLL
@@ -2794,10 +2891,19 @@ struct Step {
         constexpr int n = DM::nZ, NT = (n + 15) / 16, K0 = 16 * P + 4 * Bk;
         const int li = w.lane & 15, lk = w.lane >> 4;
         double x[NT];
+        // PHL: every address below is ONE per-lane register (row li of tile 0, column lk of a block) plus an immediate; the
+        // clamped rows of a ragged last tile keep a second one
+        double* const xb = Phi + 4 * li + lk;
+        const int lrow = 16 * (NT - 1) + li < n ? 16 * (NT - 1) + li : n - 1;
+        const double* const xl = (n % 16 == 0) ? xb : Phi + 4 * lrow + lk - 64 * (NT - 1);
         MPCQP_UNROLL
         for (int T = P; T < NT; ++T) {
-            const int row = 16 * T + li < n ? 16 * T + li : n - 1;
-            x[T] = Phi[pk(row, 0) + K0 + lk];
+            if constexpr (PHL) {
+                x[T] = (T == NT - 1 ? xl : xb)[coloff(K0) + 64 * T];
+            } else {
+                const int row = 16 * T + li < n ? 16 * T + li : n - 1;
+                x[T] = Phi[pk(row, 0) + K0 + lk];
+            }
         }
         const double xPs = one_row_per_lane<DM>() ? x[P] * gt[K0 + lk] : x[P];   // (M D M': d of the block's columns, written by chol_static)
         double* const trash = sm + c.zero + 4;
@@ -2813,7 +2919,12 @@ struct Step {
             for (int r = Bk + 1; r < 4; ++r) {
                 if (16 * P + 4 * r >= n) continue;
                 const int row = 16 * T + li, col = 16 * P + 4 * r + lk;
-                q_[T][r] = (row < n && col <= row) ? Phi + pk(row, col) : trash;
+                if constexpr (PHL) {
+                    const bool ok = (16 * T + 15 < n || row < n) && (T > P || col <= row);
+                    q_[T][r] = ok ? xb + coloff(16 * P + 4 * r) + 64 * T : trash;
+                } else {
+                    q_[T][r] = (row < n && col <= row) ? Phi + pk(row, col) : trash;
+                }
                 old_[T][r] = *q_[T][r];
             }
         }
@@ -2842,11 +2953,14 @@ struct Step {
         constexpr int n = DM::nZ, CB = 4, P = K0 / 16, Bk = (K0 % 16) / 4;
         const int i = w.lane;
         const bool act = i < n;
-        const int rowi = pk(act ? i : 0, 0);
+        const int rowi = rowoff(act ? i : 0);
         if constexpr (Bk == 0 && P > 0) chol_panel_update<P>();      // contribution of the finished panels
         const bool mine = act && i >= K0;
         double v[CB], lk[CB];
-        load4(mine ? Phi + rowi + K0 : sm + c.zero, v);
+        // (PHL: lane * 32 B + immediate, no select -- the lanes above the block read rows of the finished blocks in front of
+        //  it, the lanes >= n row 0's: finite values inside Phi that are never stored and that no other lane uses)
+        if constexpr (PHL) load4(Phi + rowi + coloff(K0), v);
+        else load4(mine ? Phi + rowi + K0 : sm + c.zero, v);
         constexpr int NCL = (n - K0 < CB) ? n - K0 : CB;             // columns of this block that exist
         MPCQP_UNROLL
         for (int cc = 0; cc < CB; ++cc) {
@@ -2869,7 +2983,7 @@ struct Step {
             gt[i] = myd_;
             MPCQP_UNROLL
             for (int cc = 0; cc < CB; ++cc) lk[cc] = (i > K0 + cc) ? lk[cc] : 0.0;
-            store4(Phi + rowi + K0, lk);
+            store4(Phi + rowi + coloff(K0), lk);
         }
         w.sync();
         if constexpr (K0 + CB < n) {
@@ -2901,7 +3015,7 @@ struct Step {
         const int i = w.lane;
         const bool act = i < n;
         const int rowi = pk(act ? i : 0, 0);
-        const double dia = act ? Phi[rowi + i] : 1.0;
+        const double dia = act ? Phi[PHL ? ix(i, i) : rowi + i] : 1.0;
         const double thr = 1e-14 * fabs(dia);        // lanes >= n: entries 0, never above thr
         const double* zero4 = sm + c.zero;
         myinvd = 0.0;
@@ -2985,7 +3099,7 @@ struct Step {
         constexpr int n = DM::nZ, K0 = 16 * T, KT = (n - K0 < 16) ? n - K0 : 16, NC = (KT + 3) / 4;
         const int i = w.lane;
         MPCQP_UNROLL
-        for (int u = 0; u < NC; ++u) load4((act && i >= K0 + 4 * u) ? Phi + rowi + K0 + 4 * u : sm + c.zero, cf[u]);
+        for (int u = 0; u < NC; ++u) load4((act && i >= K0 + 4 * u) ? Phi + rowi + coloff(K0 + 4 * u) : sm + c.zero, cf[u]);
     }
     // ... for the backward sweep: L[k][i] of the rows k of tile T (0 on and right of the diagonal: zero diagonal slot and
     // pads; lanes i >= k0 + 4 are beyond the stored row: they read column 0, which solve_bwd_tile scales by zero)
@@ -2996,6 +3110,16 @@ struct Step {
         MPCQP_UNROLL
         for (int u = 0; u < NC; ++u) {
             const int k0 = K0 + 4 * u;
+            if constexpr (PHL) {
+                // L[k0 + e][i] = Phi[cbase + 4 (k0 + e)]: the lane's column base (formed once per solve, the compiler keeps it)
+                // plus an immediate; the lanes beyond the chunk's rows read zeros at the offsets 4 e, or column 0
+                const int cbase = phi_col(n, (i < n) ? i : 0);
+                const double* p = solve_zero_region() ? ((i < k0 + 4 && i < n) ? Phi + cbase + 4 * k0 : sm + c.S)
+                                                      : Phi + (i < k0 + 4 ? cbase : 0) + 4 * k0;
+                MPCQP_UNROLL
+                for (int e = 0; e < 4; ++e) cb[u][e] = (k0 + e < n) ? p[4 * e] : 0.0;
+                continue;
+            }
             // (M D M' form with enough zero blocks in front of the Sigma table: entries used as stored, the lanes beyond the
             //  chunk's rows read zeros there -- at every offset e (k0 + 4) of the strided reads)
             const double* p = solve_zero_region() ? ((i < k0 + 4 && i < n) ? Phi + pk(k0, 0) + i : sm + c.S)
@@ -3073,7 +3197,8 @@ struct Step {
     }
     // the lanes beyond a chunk's rows of the backward sweep read zeros from the zero blocks in front of the Sigma table
     // (enough of them for the strided offsets e (k0 + 4)); otherwise their entries are multiplied by zero
-    static constexpr bool solve_zero_region() { return DM::zpad * DM::sp >= 3 * (DM::nZ + 3) + 4; }
+    // (PHL: the offsets are 4 e)
+    static constexpr bool solve_zero_region() { return DM::zpad * DM::sp >= (PHL ? 13 : 3 * (DM::nZ + 3) + 4); }
     __device__ __forceinline__ void solve_static() {
         const int i = w.lane;
         solve_static_reg(i < DM::nZ ? gt[i] : 0.0);
@@ -3083,7 +3208,7 @@ struct Step {
         constexpr int n = DM::nZ;
         const int i = w.lane;
         const bool act = i < n;
-        const int rowi = pk(act ? i : 0, 0);
+        const int rowi = rowoff(act ? i : 0);
         double cf[4][4];
         solve_fwd_load<0>(cf, rowi, act);
         solve_fwd_tile<0>(r, cf, rowi, act);                // (runs on into the backward sweep)
@@ -3595,7 +3720,16 @@ struct Step {
             // the rest of the (symmetric) row comes from column k of the rows below
             // (Hp_ == nullptr: rd holds H̃ z already, Hz_structured)
             double h0 = 0.0, h1 = 0.0;
-            if (Hp_) {
+            if (PHL && Hp_ == Phi) {
+                // H̃ staged in LDS in the column-block layout (load_H): the same terms in the same order
+                int j = 0;
+                MPCQP_PRAGMA(unroll MPCQP_HZ_UNROLL)
+                for (; j + 1 <= k; j += 2) { h0 += Phi[ix(k, j)] * z[j]; h1 += Phi[ix(k, j + 1)] * z[j + 1]; }
+                if (j <= k) h0 += Phi[ix(k, j)] * z[j];
+                const double* const Hc = Phi + coloff(k);
+                MPCQP_PRAGMA(unroll MPCQP_HZ_UNROLL)
+                for (int jj = k + 1; jj < n; ++jj) h1 += Hc[4 * jj] * z[jj];
+            } else if (Hp_) {
                 const double* Hk = Hp_ + pk(k, 0);
                 int j = 0;
                 MPCQP_PRAGMA(unroll MPCQP_HZ_UNROLL)

@@ -42,7 +42,7 @@
 
 // Revision of the kernel sources / device structs: part of the name of cached on-demand
 // specialisations, so that objects built from older sources are never loaded.
-#define MPCQP_KERNEL_REV 15       // 15: StepIO::kf_late (predictor-form placement of the fused correction), NaN rule of the estimator corrections; 14: one row per lane: a lane's own vector entries handed over in registers across the Newton solve (Step::lane_regs); 13: Model::stepc (per-handle step constants), one load phase for the set-up; 12: matrix-core operands of E'DE in registers (EtDE_add_mfma, register-operand form); 11: on-demand objects compiled with the pragma-unroll threshold lifted (no scratch arrays / flat accesses from eight tile rows on); 10: the row eps >= 0 rides in a Ŷ group (eps_host_group); 9: a blocked step (alpha < 1/2) no longer passes the last-step test; 8: MPCQP_FLAG_KEEP_ITERATE
+#define MPCQP_KERNEL_REV 16       // 16: Phi of the one-row-per-lane kernels column-block-major in LDS (phi(), phi_layout()); 15: StepIO::kf_late (predictor-form placement of the fused correction), NaN rule of the estimator corrections; 14: one row per lane: a lane's own vector entries handed over in registers across the Newton solve (Step::lane_regs); 13: Model::stepc (per-handle step constants), one load phase for the set-up; 12: matrix-core operands of E'DE in registers (EtDE_add_mfma, register-operand form); 11: on-demand objects compiled with the pragma-unroll threshold lifted (no scratch arrays / flat accesses from eight tile rows on); 10: the row eps >= 0 rides in a Ŷ group (eps_host_group); 9: a blocked step (alpha < 1/2) no longer passes the last-step test; 8: MPCQP_FLAG_KEEP_ITERATE
 
 namespace mpcqp {
 
@@ -176,5 +176,46 @@ struct StepIO {
 // Row i starts at 4(g+1)(2g + i%4); n rows take pk(n, 0) doubles.
 MPCQP_HD constexpr int pk(int i, int j) { return 4 * ((i >> 2) + 1) * (2 * (i >> 2) + (i & 3)) + j; }   // i >= j
 MPCQP_HD constexpr int pk_size(int n) { return pk(n, 0); }
+
+// Second layout of the same entries, used in LDS by the one-row-per-lane step kernels (compile-time dims, n = nZ~ <= 64, one
+// wavefront per problem: phi_layout(), mpcqp_bodies.h): column-block-major.  With G = ceil(n/4), block c holds the columns
+// 4c .. 4c+3 of the rows 4c .. n-1, four consecutive doubles per row, the rows consecutive:
+//     phi(n, i, j) = B(c) + 4 (i - 4c) + (j & 3),   c = j >> 2,   B(c) = 4 c n - 8 c (c - 1),   i >= 4c
+// The point: phi(n, i, j) = [B(c) - 16 c + (j & 3)] + 4 i -- with the column block a compile-time constant the bracket is an
+// immediate of the LDS instruction (non-negative, below pk_size(n)) and the row enters linearly, where the row start of pk()
+// is quadratic in the row.  A lane's four own entries of a block are one aligned 32-byte chunk at lane * 32 B + immediate, and
+// the 64 matrix-core operands of a row tile are one contiguous 2 KB.  Like the row padding of pk() the layout contains the
+// strictly-upper entries of every 4 x 4 diagonal block and the columns n .. 4G-1 of the last block; they hold what the pads
+// of pk() hold (zeros after the factorisation).  Same size: 4 G n - 8 G (G - 1) = pk_size(n), proved below for n <= 64.
+MPCQP_HD constexpr int phi_blk(int n, int c) { return 4 * c * n - 8 * c * (c - 1); }                     // B(c)
+MPCQP_HD constexpr int phi_col(int n, int j) { return 4 * (j >> 2) * (n - 2 * (j >> 2) - 2) + (j & 3); }   // B(c) - 16 c + (j & 3)
+MPCQP_HD constexpr int phi(int n, int i, int j) { return phi_col(n, j) + 4 * i; }                        // i >= 4 (j >> 2)
+// phi(n, ., .) maps its domain one-to-one onto [0, pk_size(n)), and the column offsets are non-negative
+constexpr bool phi_bijective(int n) {
+    const int G = (n + 3) / 4, size = pk_size(n);
+    if (phi_blk(n, G) != size) return false;
+    bool seen[pk_size(64)] = {};
+    int cnt = 0;
+    for (int c = 0; c < G; ++c) {
+        if (phi_col(n, 4 * c) < 0 || phi_col(n, 4 * c) != phi_blk(n, c) - 16 * c) return false;
+        for (int i = 4 * c; i < n; ++i)
+            for (int j = 4 * c; j < 4 * c + 4; ++j) {
+                const int s = phi(n, i, j);
+                if (s < 0 || s >= size || seen[s]) return false;
+                if (s != phi_blk(n, c) + 4 * (i - 4 * c) + (j & 3)) return false;
+                seen[s] = true;
+                ++cnt;
+            }
+    }
+    return cnt == size;
+}
+template <int N>
+struct PhiProof {
+    static_assert(phi_bijective(N), "phi(n, i, j) is not a bijection onto [0, pk_size(n))");
+    static constexpr bool ok = PhiProof<N - 1>::ok;
+};
+template <>
+struct PhiProof<0> { static constexpr bool ok = true; };
+static_assert(PhiProof<64>::ok, "column-block-major layout of Phi, n = 1 .. 64");
 
 }  // namespace mpcqp
