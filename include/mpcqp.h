@@ -372,8 +372,13 @@ int mpcqp_kf_lanes_per_estimator(mpcqp_handle h);
  * form,  P = Â P Â' - Â P Ĉm' (Ĉm P Ĉm' + R̂)⁻¹ Ĉm P Â' + Q̂,  on the model that is resident, by the structure-preserving
  * doubling iteration (csrc/kf_dare_bodies.h; at most 40 iterations, stopped when P moves by less than 1e-13 of
  * max(1, max|P|)), and K̂ = P̂∞ Ĉm' (Ĉm P̂∞ Ĉm' + R̂)⁻¹, the filter-form gain of mpcqp_kf_set, lands in the gain buffer of
- * the handle.  The iteration inverts H(k) (H(0) = Q̂) without pivoting: Q̂ has to be positive DEFINITE (R̂ too).  A
- * semidefinite Q̂ gets status 2; compute its gain on the host and hand it to mpcqp_kf_set.
+ * the handle.  R̂ has to be positive definite; Q̂ may be positive SEMIdefinite (noise through fewer channels than states,
+ * delay states, a σQ with zeros).  The solve makes two passes over the batch: the first inverts H(k) (H(0) = Q̂) without
+ * pivoting, which serves a definite Q̂; an estimator it leaves broken down, or whose Q̂ is numerically singular (smallest
+ * pivot <= 1e-10 max diag Q̂), is solved again by the square-root form of
+ * the same iteration (csrc/kf_dare_psd_bodies.h: H(k) = L L' without pivoting, columns of pivots <= 0 dropped,
+ * S = L (I + L'GL)⁻¹ L').  There a pivot of H(k) below -1e-8 max(1, max diag H(k)) is no rounding: an indefinite Q̂ keeps
+ * status 2.  A build without the second pass (the kernel is missing) gives a semidefinite Q̂ status 2, as before.
  *
  * mpcqp_kf_set_steady: Qhat (nx̂,nx̂,B), Rhat (nym,nym,B), i_ym [nym]: layouts, symmetry check (MPCQP_ERR_ARG) and i_ym
  * validation of mpcqp_kf_set_covariances.  Needs the model (MPCQP_ERR_ORDER).  Stores Q̂ and R̂, fills K̂, P̂∞ and the
@@ -384,21 +389,27 @@ int mpcqp_kf_lanes_per_estimator(mpcqp_handle h);
  * mpcqp_kf_solve_steady / _solve_steady_device: solve again on the model resident now (host-synchronous / enqueued on
  * `stream`, ordered like every other *_device call).  mpcqp_set_model does NOT do this by itself: until the caller
  * re-solves, the gain of the previous model stays in use.
- * mpcqp_kf_steady_iters: out [B], doubling iterations of the last solve.
+ * mpcqp_kf_steady_iters: out [B], doubling iterations of the last solve (of the pass that produced the estimator's result).
+ * mpcqp_kf_steady_path: out [B], which pass that was: 0 solved by, or left with, the definite form; 1 the square-root form
+ * ran for this estimator (whatever its status).  MPCQP_ERR_ORDER outside the mode, like mpcqp_kf_steady_iters.
  * On such a handle
  *       mpcqp_kf_status   answers, per estimator, 0 solved; 1 not converged within the cap (the batch form of the
  *                         reference's "Cannot compute the optimal Kalman gain": an undetectable pair); 2 broke down: a
- *                         pivot of R̂, H(k) or H(k)⁻¹ + G(k) was outside (0, inf), or a value was not finite.  With 1 or 2
- *                         the estimator's K̂ and P̂∞ keep their previous contents (zeros after mpcqp_kf_set_steady); the
- *                         rest of the batch is unaffected, bit for bit;
+ *                         pivot of R̂ or of I + L'GL was outside (0, inf), H(k) had a negative pivot beyond rounding (see
+ *                         above), or a value was not finite.  With 1 or 2
+ *                         the estimator's K̂ and P̂∞ keep their previous contents (zeros after mpcqp_kf_set_steady) -- or
+ *                         are set to zero, where the first pass had written a result for a numerically singular Q̂ and
+ *                         the second pass refuses the estimator: a non-zero status never comes with a gain of that
+ *                         solve; the rest of the batch is unaffected, bit for bit;
  *       MPCQP_GET_KF_COV  returns P̂∞;
  *       mpcqp_kf_lanes_per_estimator answers 16 or 64.
- * A later mpcqp_kf_set or mpcqp_kf_set_covariances leaves the mode: mpcqp_kf_solve_steady[_device] and
- * mpcqp_kf_steady_iters then answer MPCQP_ERR_ORDER. */
+ * A later mpcqp_kf_set or mpcqp_kf_set_covariances leaves the mode: mpcqp_kf_solve_steady[_device],
+ * mpcqp_kf_steady_iters and mpcqp_kf_steady_path then answer MPCQP_ERR_ORDER. */
 int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, const int32_t* i_ym, int32_t nym);
 int mpcqp_kf_solve_steady(mpcqp_handle h);
 int mpcqp_kf_solve_steady_device(mpcqp_handle h, void* stream);
 int mpcqp_kf_steady_iters(mpcqp_handle h, int32_t* out);
+int mpcqp_kf_steady_path(mpcqp_handle h, int32_t* out);
 
 
 /* ---- which kernel runs a step; building specialised kernels ahead of the control loop -----------

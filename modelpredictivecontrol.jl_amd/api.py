@@ -43,6 +43,7 @@ EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_cre
            "mpcqp_kf_set_covariances", "mpcqp_kf_set_state_covariance", "mpcqp_kf_status", "mpcqp_kf_lanes_per_estimator",
            "mpcqp_kf_set_direct", "mpcqp_kf_update", "mpcqp_kf_update_device",
            "mpcqp_kf_set_steady", "mpcqp_kf_solve_steady", "mpcqp_kf_solve_steady_device", "mpcqp_kf_steady_iters",
+           "mpcqp_kf_steady_path",
            "mpcqp_set_output_weight_blocks", "mpcqp_set_dense_weights", "mpcqp_set_custom_constraints", "mpcqp_set_custom_bounds",
            "mpcqp_set_flags", "mpcqp_set_iteration_limit", "mpcqp_set_transcription", "mpcqp_transcription_supported", "mpcqp_set_current_setpoint", "mpcqp_prepare", "mpcqp_kernel_kind", "mpcqp_lds_bytes", "mpcqp_row_groups", "mpcqp_step_consts_builds", "mpcqp_prebuild",
            "mpcqp_last_build_error", "mpcqp_multi_create", "mpcqp_multi_destroy", "mpcqp_multi_ndev",
@@ -184,6 +185,8 @@ def load_library(path: str | None = None):
         lib.mpcqp_kf_solve_steady.argtypes = [C.c_void_p]
         lib.mpcqp_kf_solve_steady_device.argtypes = [C.c_void_p, C.c_void_p]
         lib.mpcqp_kf_steady_iters.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "mpcqp_kf_steady_path"):       # (a build without the square-root pass: Handle then has no kf_steady_path)
+        lib.mpcqp_kf_steady_path.argtypes = [C.c_void_p, C.c_void_p]
     lib.mpcqp_set_current_setpoint.argtypes = [C.c_void_p, C.c_void_p]
     lib.mpcqp_prepare.argtypes = [C.c_void_p]
     lib.mpcqp_kernel_kind.argtypes = [C.c_void_p]
@@ -233,7 +236,7 @@ def colmajor(M):
 # -- SteadyKalmanFilter from Q̂ and R̂: the gain solved for on the device (csrc/kf_dare_bodies.h).  Methods of Handle, bound
 # only when the library exports the entry points
 def _kf_set_steady(self, Qhat, Rhat, i_ym):
-    """Qhat (B,nx̂,nx̂), Rhat (B,nym,nym), symmetric positive definite.  Solves the Riccati equation of every member on the
+    """Qhat (B,nx̂,nx̂) symmetric positive semidefinite, Rhat (B,nym,nym) symmetric positive definite.  Solves the Riccati equation of every member on the
     resident model; kf_gain() / kf_covariance() / kf_status() / kf_steady_iters() read the result back."""
     iy = np.ascontiguousarray(i_ym, dtype=np.int32)
     _chk(self.lib, self.lib.mpcqp_kf_set_steady(self.h, _ptr(colmajor(Qhat)), _ptr(colmajor(Rhat)), _ptr(iy), int(iy.size)))
@@ -253,6 +256,14 @@ def _kf_steady_iters(self):
     """(B,) int32 doubling iterations of the last solve."""
     out = np.empty(self.B, np.int32)
     _chk(self.lib, self.lib.mpcqp_kf_steady_iters(self.h, _ptr(out)))
+    return out
+
+
+def _kf_steady_path(self):
+    """(B,) int32: 0 the estimator was solved by (or left with) the definite form of the iteration, 1 the square-root form ran
+    for it (a semidefinite Q̂)."""
+    out = np.empty(self.B, np.int32)
+    _chk(self.lib, self.lib.mpcqp_kf_steady_path(self.h, _ptr(out)))
     return out
 
 
@@ -285,6 +296,8 @@ class Handle:
         f = _STEADY_METHODS.get(name)
         if f is not None and hasattr(self.__dict__.get("lib"), "mpcqp_kf_set_steady"):
             return types.MethodType(f, self)
+        if name == "kf_steady_path" and hasattr(self.__dict__.get("lib"), "mpcqp_kf_steady_path"):
+            return types.MethodType(_kf_steady_path, self)
         raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     def close(self):
@@ -968,8 +981,9 @@ class BatchLinMPC:
         device and follow `preparestate` / `updatestate` (and `setmodel`: the recursion reads the current model).
 
         `steady=dict(Qhat=…, Rhat=…)` is the SteadyKalmanFilter as the reference constructs it, from Q̂ and R̂ (kalman.jl:205-222):
-        the steady-state gain of every member is solved for on the device (Q̂ and R̂ positive definite, max(nx̂, nym) <= 32;
-        `steady_kalman_gain` on the host is the path for a semidefinite Q̂), and `setmodel` solves again on the new model --
+        the steady-state gain of every member is solved for on the device (R̂ positive definite, Q̂ positive semidefinite,
+        max(nx̂, nym) <= 32; `getinfo()["kf_steady_path"]` tells which form of the iteration served a member), and `setmodel`
+        solves again on the new model --
         which the reference's SteadyKalmanFilter refuses.  Members whose equation has no solution (an undetectable pair) or
         whose solve broke down keep a zero gain and are counted in one RuntimeWarning; `getinfo` shows `kf_status`.
 
@@ -1048,7 +1062,7 @@ class BatchLinMPC:
         n = int(np.count_nonzero(self.hd.kf_status()))
         if n:
             warnings.warn("Cannot compute the optimal Kalman gain K̂ for the SteadyKalmanFilter: the pair is not detectable or "
-                          f"the solve broke down, the previous gain stays ({n} of {self.B} estimators)", RuntimeWarning)
+                          f"the solve broke down, the previous gain (or zero) stays ({n} of {self.B} estimators)", RuntimeWarning)
 
     def setcovariances(self, Qhat, Rhat):
         """The Q̂, R̂ keywords of `setmodel!`: new noise covariances.  KalmanFilter: P̂ and x̂0 stay.  SteadyKalmanFilter from Q̂
@@ -1235,6 +1249,8 @@ class BatchLinMPC:
         if getattr(self, "kf_timevarying", False) or getattr(self, "kf_steady", False):
             # the estimator's covariance (P̂∞ of a steady solve), gain and per-estimator status
             info["P̂"], info["K̂"], info["kf_status"] = self.hd.kf_covariance(), self.hd.kf_gain(), self.hd.kf_status()
+            if getattr(self, "kf_steady", False) and hasattr(self.hd, "kf_steady_path"):
+                info["kf_steady_path"] = self.hd.kf_steady_path()      # 1: solved by the square-root form (semidefinite Q̂)
         # decision vector in the transcription's layout: [ΔU; ϵ] or [ΔU; X̂0(k+1..k+Hp); ϵ] (get_nZ_mpc, transcription.jl:2-7)
         parts = [DU] + ([X0.reshape(self.B, -1)] if self.transcription == "MultipleShooting" else []) + ([eps[:, None]] if self.neps else [])
         info["Z̃"] = np.concatenate(parts, axis=1)

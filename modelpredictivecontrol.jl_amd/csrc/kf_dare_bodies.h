@@ -15,7 +15,7 @@
 // until max|H(k+1) - H(k)| <= DARE_TOL max(1, max|H(k+1)|);  P̂∞ = H,  K̂ = P̂∞ Ĉm' (Ĉm P̂∞ Ĉm' + R̂)⁻¹ (the filter-form gain,
 // in the order of operations of kf_cov_body's correction).  Iteration k holds the covariance after 2^k periods of the
 // recursion, which is why a dozen of them do what the fixed-point iteration needs hundreds for.  H(0)⁻¹ needs Q̂ positive
-// definite: a semidefinite Q̂ breaks down here (status 2) and stays with the host's steady_kalman_gain.
+// definite: a semidefinite Q̂ breaks down here (status 2) and goes to the second pass (kf_dare_psd_bodies.h).
 //
 // Symmetry: S, G(k+1) and H(k+1) are stored as ½ (M + M').  A transpose is the product I M' (Ops::mmt_acc with the identity:
 // every term is a value times 0 or 1, so it is exact), which keeps the body on the existing Ops: eight products, four

@@ -11,6 +11,7 @@
 #include "kf_cov_launch.h"
 #include "kf_dare_bodies.h"
 #include "kf_dare_launch.h"
+#include "kf_dare_psd_bodies.h"
 #include "mhe_devwave.h"
 #include "mhe_wide_devwave.h"
 #include "mpcqp_launch.h"
@@ -93,6 +94,37 @@ hipError_t launch_kf_dare(const DareArgs& a, hipStream_t st) {
 
 // the grid of the covariance kernels: what is not resident at once queues behind what is
 int kf_dare_waves_for(int device, int B, int NX) { return kf_cov_waves_for(device, B, NX); }
+
+// ---- the second pass: the square-root form of the same iteration for the estimators the first pass left broken down (a
+// semidefinite Q̂) or whose Q̂ is numerically singular.  The same grid and the same seven rows; every wavefront reads and
+// factors the Q̂ of its estimators and their status words, and one without a candidate votes once and moves on.  (Spills:
+// lib/isa_resources.txt -- accepted as above.)
+template <int NX>
+__global__ __launch_bounds__(64) void k_kf_dare_psd(DareArgs a) {
+    MheDevWave w{(int)threadIdx.x};
+    kf_dare_psd_body<MheDevWave, NX>(w, a, (int)blockIdx.x);
+}
+template <int NX>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_kf_dare_psd_wide(DareArgs a) {
+    WideWave w;
+    w.lane = (int)threadIdx.x;
+    w.stage = mpcqp_smem;
+    kf_dare_psd_body<WideWave, NX>(w, a, (int)blockIdx.x);
+}
+
+hipError_t launch_kf_dare_psd(const DareArgs& a, hipStream_t st) {
+    if (!kf_dare_args_ok(a) || !a.path) return hipErrorInvalidValue;
+    switch (a.NX) {
+        case 4: hipLaunchKernelGGL(k_kf_dare_psd<4>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
+        case 8: hipLaunchKernelGGL(k_kf_dare_psd<8>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
+        case 12: hipLaunchKernelGGL(k_kf_dare_psd<12>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
+        case 16: hipLaunchKernelGGL(k_kf_dare_psd<16>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
+        case 24: hipLaunchKernelGGL(k_kf_dare_psd_wide<24>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a); break;
+        case 32: hipLaunchKernelGGL(k_kf_dare_psd_wide<32>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
 
 }  // namespace kf
 }  // namespace mpcqp

@@ -236,6 +236,38 @@ struct Ops {
         sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; a[c] *= mypinv; });
         return ok;
     }
+    // Cholesky factor of a symmetric positive SEMIdefinite matrix, without pivoting: a = L L' with L lower triangular, row-lane
+    // like a (which is used up: it holds the Schur complements).  A pivot d <= 0 drops its column -- L[:, k] = 0 and nothing
+    // is eliminated with it -- which is exact for a semidefinite a (the column under a zero pivot is zero) and leaves
+    // rounding-sized pivots of either sign out of the factor.  The elimination is gj's step (gjacc4: one in-place
+    // multiply-add per entry, rows up to the pivot with factor 0); only compile-time lane indices.  Returns the most
+    // negative pivot relative to max(1, max diag a) (0: none; -1e300: a pivot that is not a number), the same on every lane
+    // of the group: the caller decides what "semidefinite up to rounding" means.  `smallest`: the smallest pivot as it
+    // is (not scaled), whatever its sign -- how close to singular a is.
+    MPCQP_HD double chol_psd(Row& a, Row& L, int r, double& smallest) const {
+        double dg = 0.0;
+        sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; dg = (r == c) ? a[c] : dg; });
+        const double scale = fmax(1.0, w.rmax(dg));
+        double neg = 0.0, dmin = 1e300;
+        sfor<NX>([&](auto ik) {
+            constexpr int k = decltype(ik)::v;
+            const double dk = w.template rowbc<k>(a[k]);
+            const bool keep = dk > 0.0;
+            dmin = fmin(dmin, dk);
+            neg = keep ? neg : (dk <= 0.0 ? fmin(neg, dk) : -1e300);
+            const double ds = keep ? dk : 1.0;
+            const double si = recip(sqrt(ds));
+            const double below = (r > k) ? a[k] : 0.0;        // column k of the Schur complement under its pivot
+            const double g = keep ? -below * recip(ds) : 0.0;
+            L[k] = (keep && r >= k) ? a[k] * si : 0.0;        // (the pivot lane: d / sqrt(d))
+            sfor<NX / 4>([&](auto ij) {
+                constexpr int c = 4 * decltype(ij)::v;
+                w.template gjacc4<k>(a[c], a[c + 1], a[c + 2], a[c + 3], g);
+            });
+        });
+        smallest = dmin;
+        return neg > -1e300 ? neg * recip(scale) : -1e300;
+    }
     MPCQP_HD static void ld(const double* p, int stride, Row& M) {
         sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; M[c] = p[(size_t)c * stride]; });
     }

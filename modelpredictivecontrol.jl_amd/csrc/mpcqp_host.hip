@@ -74,6 +74,7 @@ struct mpcqp_handle_s {
     // for, kf_P its P̂∞, kf_st / kf_it the status and iteration count of the last solve; kf_tv stays false
     bool kf_steady = false;
     DBuf kf_it;
+    DBuf kf_path;     // which body produced each estimator's result (kf_dare_launch.h: DareArgs::path)
     int kf_dare_waves = 0;
     // mpcqp_kf_set_direct: 1 filter form (mpcqp_loop_device: correction, step, prediction), 0 predictor form (step, correction,
     // prediction).  A property of the handle: the setters of the gain and of the covariances leave it alone
@@ -1020,7 +1021,9 @@ int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* R
     return MPCQP_OK;
 }
 
-// One Riccati solve of a handle in steady mode (kf_kernels.hip: k_kf_dare*) on the model that is resident now.
+// One Riccati solve of a handle in steady mode (kf_kernels.hip: k_kf_dare*) on the model that is resident now: the definite
+// body for the whole batch, then (a library that has it) the square-root body, which reads and factors every Q̂ and solves
+// again the estimators that the definite body left broken down or whose Q̂ is numerically singular (kf_dare_launch.h).
 static int kf_dare_launch(mpcqp_handle h, hipStream_t st) {
     if (!kf::kf_dare_available()) return MPCQP_ERR_UNSUPPORTED;
     ON_DEVICE(h);
@@ -1032,7 +1035,10 @@ static int kf_dare_launch(mpcqp_handle h, hipStream_t st) {
     a.status = (int32_t*)h->kf_st.p; a.iters = (int32_t*)h->kf_it.p;
     a.B = d.B; a.nx = d.nxh; a.ny = d.ny; a.nym = h->kf.nym;
     a.NX = h->kf_NX; a.nwaves = h->kf_dare_waves;
+    a.path = (int32_t*)h->kf_path.p;
+    HIPCHK(hipMemsetAsync(h->kf_path.p, 0, (size_t)d.B * sizeof(int32_t), st));
     HIPCHK(kf::launch_kf_dare(a, st));
+    if (kf::kf_dare_psd_available()) HIPCHK(kf::launch_kf_dare_psd(a, st));
     return MPCQP_OK;
 }
 
@@ -1057,6 +1063,7 @@ int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, 
     if (!rc) rc = dev_alloc(h, h->kf_K, B * nk * sz);
     if (!rc) rc = dev_alloc(h, h->kf_st, B * sizeof(int32_t));
     if (!rc) rc = dev_alloc(h, h->kf_it, B * sizeof(int32_t));
+    if (!rc) rc = dev_alloc(h, h->kf_path, B * sizeof(int32_t));
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(h->kf_P.p, 0, B * nn * sz, h->stream));
     HIPCHK(hipMemsetAsync(h->kf_K.p, 0, B * nk * sz, h->stream));
@@ -1094,6 +1101,16 @@ int mpcqp_kf_steady_iters(mpcqp_handle h, int32_t* out) {
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, h->kf_it.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MPCQP_OK;
+}
+
+int mpcqp_kf_steady_path(mpcqp_handle h, int32_t* out) {
+    if (!h || !out) return MPCQP_ERR_NULL;
+    if (!h->kf_steady) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, h->kf_path.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
     return MPCQP_OK;
 }
 
