@@ -281,7 +281,59 @@ int mpcqp_recondense_device(mpcqp_handle h, void* stream);
 #define MPCQP_GET_MS_DEFECT 9   /* (B): max |E_S Z + F_S| (defect of the model equations, transcription.jl:303-327) of it */
 #define MPCQP_GET_KF_COV    10  /* (nx̂,nx̂,B): P̂ of the time-varying KalmanFilter, P̂∞ after mpcqp_kf_set_steady (MPCQP_ERR_ORDER on a gain from mpcqp_kf_set) */
 #define MPCQP_GET_KF_GAIN   11  /* (nx̂,nym,B): K̂ the estimator steps use -- the steady gain or K̂(k) of the last correction */
+#define MPCQP_GET_EXPLICIT_LAW 12 /* (nZ, 1+nx̂+nu+ny+nd, B): the law [g0 Gx Gu Gr Gd] of mpcqp_explicit_prepare(h, MPCQP_EXPLICIT_LAW) */
 int mpcqp_get(mpcqp_handle h, int which, double* out);
+
+/* ---- ExplicitMPC (src/controller/explicitmpc.jl): the unconstrained LinMPC, H̃ factored once, Z̃ = -H̃⁻¹ q̃ every period ------
+ * Two per-period paths on the handle of a controller WITHOUT constraints, beside mpcqp_step (which goes on working):
+ *   mpcqp_explicit_step[_device]  inputs, layouts, MPCQP_FLAG_RY_CONSTANT / _KEEP_QP and Yhat0 of mpcqp_step[_device]; Ztilde
+ *                                 is output only (ExplicitMPC has no warm start), there is no iteration count.  Per period
+ *                                 F, q̃ and a product with the stored H̃⁻¹: no factorisation, no interior-point code.
+ *   mpcqp_explicit_law[_device]   with set point, disturbance and R̂u = Uop held over the horizon -- the reference's default call
+ *                                 moveinput!(mpc, ry, d), execute.jl:59-70 -- the period is the affine map
+ *                                     Z̃ = g0 + Gx x̂0 + Gu lastu0 + Gr ry + Gd d0,    u0 = Z̃[1:nu] + lastu0
+ *                                 ry (ny,B), d0 (nd,B) or NULL; Ztilde == NULL: u0 alone, from a table of nu rows per
+ *                                 controller.  By definition the result of mpcqp_explicit_step with MPCQP_FLAG_RY_CONSTANT,
+ *                                 Ru = NULL and Dhat0 = repeat(d0).  Several controllers per wavefront; bandwidth-bound.
+ * mpcqp_explicit_prepare(h, with_law): with_law = 0 or MPCQP_EXPLICIT_LAW (the law tables are built too, by superposition:
+ *   the explicit step on the 1+nx̂+nu+ny+nd unit inputs, on device buffers).  A kernel of its own factors every controller's
+ *   H̃ on the device and keeps H̃⁻¹ (two substitutions with the factor were measured slower); nothing is computed
+ *   on the host.
+ *     MPCQP_ERR_ORDER        no model or no weights yet
+ *     MPCQP_ERR_ARG          neps = 1, a bound or custom-row group on the handle (any array given to mpcqp_set_bounds /
+ *                            mpcqp_set_custom_bounds counts, whatever it holds), or the MultipleShooting transcription --
+ *                            "ExplicitMPC does not support constraints", and it has no Cwt / transcription keyword
+ *     MPCQP_ERR_UNSUPPORTED  nZ̃ = nu Hc > 64 (one row of H̃ per lane; 65 is refused, not served), a handle without a
+ *                            condensed Hessian (nZ̃ > 256, or a problem beyond the LDS of the condensed step kernels: the
+ *                            handles mpcqp_get(MPCQP_GET_HESSIAN) refuses), or a library built without the kernels.  Every
+ *                            other handle with nZ̃ <= 64 is served, whatever Hp: the period keeps 2 ny Hp + ny nu Hp +
+ *                            nZ̃ (nZ̃ + 1) / 2 doubles in LDS, less than mpcqp_step does for the same handle
+ *   A prepared handle refreshes the factor (and the law) inside mpcqp_set_model, mpcqp_set_weights,
+ *   mpcqp_set_output_weight_blocks, mpcqp_set_dense_weights and mpcqp_recondense_device (there on the caller's stream): an
+ *   explicit call never sees a stale factor.  A handle that receives a bound group, neps or MultipleShooting afterwards
+ *   answers MPCQP_ERR_ORDER to the explicit calls (mpcqp_explicit_status included) until the rows are gone; its setters go on
+ *   working and do not factor, and the first explicit call after the rows are gone factors again, on that call's stream.
+ *   MPCQP_ERR_ORDER is also the answer of a handle that was never prepared, and of mpcqp_explicit_law without
+ *   MPCQP_EXPLICIT_LAW.  mpcqp_explicit_prepare may be repeated (to add or drop the law); tables a running law call reads
+ *   are rebuilt behind it.
+ * The law kernel runs a persistent grid of 16 wavefronts per compute unit.  The environment variable MPCQP_EXPLICIT_WAVES = n
+ *   (n >= 1) caps that grid at n wavefronts; it is read by mpcqp_explicit_prepare -- not by the per-period calls -- and the
+ *   handle keeps the grid it was prepared with.  Results do not depend on it.
+ * mpcqp_explicit_status: out [B], 0 factored, 2 H̃ not positive definite or not finite (where the reference's cholesky
+ *   throws).  Such a controller gets status 2, Z̃ = 0 and u0 = lastu0 from every explicit call (Ŷ0 = F); the rest of the
+ *   batch is unaffected, bit for bit -- the policy of the Kalman kernels.  status [B] of the per-period calls: 0 or 2. */
+#define MPCQP_EXPLICIT_LAW           1
+int mpcqp_explicit_prepare(mpcqp_handle h, int32_t with_law);
+int mpcqp_explicit_status(mpcqp_handle h, int32_t* out);
+int mpcqp_explicit_step(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* Ry, const double* Ru,
+                        const double* d0, const double* Dhat0, double* Ztilde, double* u0, int32_t* status, double* Yhat0);
+int mpcqp_explicit_step_device(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* Ry,
+                               const double* Ru, const double* d0, const double* Dhat0, double* Ztilde, double* u0,
+                               int32_t* status, double* Yhat0, void* stream);
+int mpcqp_explicit_law(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* ry, const double* d0,
+                       double* Ztilde, double* u0, int32_t* status);
+int mpcqp_explicit_law_device(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* ry,
+                              const double* d0, double* Ztilde, double* u0, int32_t* status, void* stream);
 
 /* ---- next row: the Kalman filter steps on both sides of moveinput! ----------------
  * correction, correct_estimate_obsv! (src/estimator/kalman.jl:284-295):

@@ -33,6 +33,8 @@ SINGLE_SHOOTING, MULTIPLE_SHOOTING = 0, 1
 STATUS_OPTIMAL, STATUS_ITERATION_LIMIT, STATUS_ERROR = 0, 1, 2
 GET_HESSIAN, GET_STEPRESP, GET_KMAT, GET_BVEC, GET_QTILDE, GET_FVEC, GET_AUDIT, GET_XHAT_MS, GET_MS_DEFECT = 1, 2, 3, 4, 5, 6, 7, 8, 9
 GET_KF_COV, GET_KF_GAIN = 10, 11
+GET_EXPLICIT_LAW = 12
+EXPLICIT_LAW = 1       # bit of mpcqp_explicit_prepare's with_law
 KF_STATUS_OK, KF_STATUS_DROPPED = 0, 2
 KF_STEADY_OK, KF_STEADY_NOT_CONVERGED, KF_STEADY_BROKE_DOWN = 0, 1, 2      # mpcqp_kf_status after mpcqp_kf_set_steady
 EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_create",
@@ -44,6 +46,8 @@ EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_cre
            "mpcqp_kf_set_direct", "mpcqp_kf_update", "mpcqp_kf_update_device",
            "mpcqp_kf_set_steady", "mpcqp_kf_solve_steady", "mpcqp_kf_solve_steady_device", "mpcqp_kf_steady_iters",
            "mpcqp_kf_steady_path",
+           "mpcqp_explicit_prepare", "mpcqp_explicit_status", "mpcqp_explicit_step", "mpcqp_explicit_step_device",
+           "mpcqp_explicit_law", "mpcqp_explicit_law_device",
            "mpcqp_set_output_weight_blocks", "mpcqp_set_dense_weights", "mpcqp_set_custom_constraints", "mpcqp_set_custom_bounds",
            "mpcqp_set_flags", "mpcqp_set_iteration_limit", "mpcqp_set_transcription", "mpcqp_transcription_supported", "mpcqp_set_current_setpoint", "mpcqp_prepare", "mpcqp_kernel_kind", "mpcqp_lds_bytes", "mpcqp_row_groups", "mpcqp_step_consts_builds", "mpcqp_prebuild",
            "mpcqp_last_build_error", "mpcqp_multi_create", "mpcqp_multi_destroy", "mpcqp_multi_ndev",
@@ -188,6 +192,13 @@ def load_library(path: str | None = None):
     if hasattr(lib, "mpcqp_kf_steady_path"):       # (a build without the square-root pass: Handle then has no kf_steady_path)
         lib.mpcqp_kf_steady_path.argtypes = [C.c_void_p, C.c_void_p]
     lib.mpcqp_set_current_setpoint.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "mpcqp_explicit_prepare"):
+        lib.mpcqp_explicit_prepare.argtypes = [C.c_void_p, C.c_int32]
+        lib.mpcqp_explicit_status.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mpcqp_explicit_step.argtypes = [C.c_void_p] * 11
+        lib.mpcqp_explicit_step_device.argtypes = [C.c_void_p] * 12
+        lib.mpcqp_explicit_law.argtypes = [C.c_void_p] * 8
+        lib.mpcqp_explicit_law_device.argtypes = [C.c_void_p] * 9
     lib.mpcqp_prepare.argtypes = [C.c_void_p]
     lib.mpcqp_kernel_kind.argtypes = [C.c_void_p]
     lib.mpcqp_lds_bytes.argtypes = [C.c_void_p]
@@ -430,6 +441,55 @@ class Handle:
         _chk(self.lib, self.lib.mpcqp_loop_device(self.h, v(xhat0), v(y0m), v(lastu0), v(Ry), v(Ru), v(d0), v(Dhat0),
                                                   v(Z), v(u0), v(status), v(iters), v(Yhat0), v(stream)))
 
+    # -- ExplicitMPC: H̃ factored once (explicit_prepare), then a solve (explicit_step) or a gain (explicit_law) per period
+    def explicit_prepare(self, law=False):
+        """mpcqp_explicit_prepare: factor every controller's H̃ on the device; `law=True` builds the law tables too."""
+        _chk(self.lib, self.lib.mpcqp_explicit_prepare(self.h, EXPLICIT_LAW if law else 0))
+
+    def explicit_status(self):
+        """(B,) int32: 0 factored, 2 H̃ not positive definite / not finite."""
+        out = np.empty(self.B, np.int32)
+        _chk(self.lib, self.lib.mpcqp_explicit_status(self.h, _ptr(out)))
+        return out
+
+    def explicit_step(self, xhat0, lastu0, Ry, Ru=None, d0=None, Dhat0=None, want_Yhat=False):
+        """Host-pointer explicit step.  Returns Z (B,nZ), u0, status[, Yhat0]."""
+        B = self.B
+        x, lu, ry = _f64(xhat0), _f64(lastu0), _f64(Ry)
+        ru, dd0, dh = (None if a is None else _f64(a) for a in (Ru, d0, Dhat0))
+        nry = self.ny if (self.flags & FLAG_RY_CONSTANT) else self.nY
+        if (x.size != B * self.nxhat or lu.size != B * self.nu or ry.size != B * nry or (ru is not None and ru.size != B * self.nU)
+                or (dd0 is not None and dd0.size != B * self.nd) or (dh is not None and dh.size != B * self.nD)):
+            raise ValueError("DimensionMismatch in step arguments")
+        Z, u0, status = np.empty((B, self.nZ)), np.empty((B, self.nu)), np.empty(B, np.int32)
+        yh = np.empty((B, self.nY)) if want_Yhat else None
+        _chk(self.lib, self.lib.mpcqp_explicit_step(self.h, _ptr(x), _ptr(lu), _ptr(ry), _ptr(ru), _ptr(dd0), _ptr(dh),
+                                                    _ptr(Z), _ptr(u0), _ptr(status), _ptr(yh)))
+        return (Z, u0, status, yh) if want_Yhat else (Z, u0, status)
+
+    def explicit_step_device(self, xhat0, lastu0, Ry, Z, u0, status, Ru=0, d0=0, Dhat0=0, Yhat0=0, stream=0):
+        """All arguments are integer device addresses (0 = NULL); asynchronous on `stream`."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _chk(self.lib, self.lib.mpcqp_explicit_step_device(self.h, v(xhat0), v(lastu0), v(Ry), v(Ru), v(d0), v(Dhat0),
+                                                           v(Z), v(u0), v(status), v(Yhat0), v(stream)))
+
+    def explicit_law(self, xhat0, lastu0, ry, d0=None, want_Z=True):
+        """Host-pointer law call: Z̃ = g0 + Gx x̂0 + Gu lastu0 + Gr ry + Gd d0.  Returns Z (or None with want_Z=False), u0, status."""
+        B = self.B
+        x, lu, r = _f64(xhat0), _f64(lastu0), _f64(ry)
+        dd0 = None if d0 is None else _f64(d0)
+        if x.size != B * self.nxhat or lu.size != B * self.nu or r.size != B * self.ny or (dd0 is not None and dd0.size != B * self.nd):
+            raise ValueError("DimensionMismatch in law arguments")
+        Z = np.empty((B, self.nZ)) if want_Z else None
+        u0, status = np.empty((B, self.nu)), np.empty(B, np.int32)
+        _chk(self.lib, self.lib.mpcqp_explicit_law(self.h, _ptr(x), _ptr(lu), _ptr(r), _ptr(dd0), _ptr(Z), _ptr(u0), _ptr(status)))
+        return Z, u0, status
+
+    def explicit_law_device(self, xhat0, lastu0, ry, u0, status, Z=0, d0=0, stream=0):
+        """Integer device addresses (Z = 0: u0 alone); asynchronous on `stream`."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _chk(self.lib, self.lib.mpcqp_explicit_law_device(self.h, v(xhat0), v(lastu0), v(ry), v(d0), v(Z), v(u0), v(status), v(stream)))
+
     def recondense_device(self, stream=0):
         _chk(self.lib, self.lib.mpcqp_recondense_device(self.h, C.c_void_p(int(stream)) if stream else None))
 
@@ -438,6 +498,7 @@ class Handle:
                  GET_KMAT: (self.B, self.nxhat, self.nY), GET_BVEC: (self.B, self.nY),
                  GET_QTILDE: (self.B, self.nZ), GET_FVEC: (self.B, self.nY), GET_AUDIT: (self.B, 4),
                  GET_XHAT_MS: (self.B, self.Hp, self.nxhat), GET_MS_DEFECT: (self.B,),
+                 GET_EXPLICIT_LAW: (self.B, 1 + self.nxhat + self.nu + self.ny + self.nd, self.nZ),
                  GET_KF_COV: (self.B, self.nxhat, self.nxhat), GET_KF_GAIN: (self.B, getattr(self, "nym", 0), self.nxhat)}[which]
         out = np.empty(shape)
         _chk(self.lib, self.lib.mpcqp_get(self.h, which, _ptr(out)))
@@ -1132,28 +1193,8 @@ class BatchLinMPC:
         xhat0 (B,nx̂) is `estim.x̂0` (deviation); ry (B,ny)/(ny,), d (B,nd), `lastu`, `Rhaty`
         (B,ny*Hp), `Rhatu` (B,nu*Hp), `Dhat` (B,nd*Hp) are engineering values like the reference.
         Returns u (B,nu)."""
-        B, Hp = self.B, self.Hp
-        if xhat0 is None:
-            xhat0 = self.xhat0                      # the attached estimator's state (setestimator)
-        xhat0 = np.asarray(xhat0, float)
-        if xhat0.shape != (B, self.nxh):
-            raise ValueError(f"xhat0 size must be ({B},{self.nxh})")
-        bc = lambda v, n, name: self._bc(v, n, name)
-        ry = self.yop if ry is None else bc(ry, self.ny, "ry")
-        held = Rhaty is None                      # R̂y = repeat(ry, Hp): send ry once (MPCQP_FLAG_RY_CONSTANT)
-        Rhaty = None if held else bc(Rhaty, self.nY, "R̂y")
-        want = (self.hd.flags | FLAG_RY_CONSTANT) if held else (self.hd.flags & ~FLAG_RY_CONSTANT)
-        if want != self.hd.flags:
-            self.hd.set_flags(want)
-        Rhatu = None if Rhatu is None else bc(Rhatu, self.nU, "R̂u")
-        lastu0 = self.lastu0 if lastu is None else bc(lastu, self.nu, "lastu") - self.uop
-        d0 = Dh0 = None
-        if self.nd > 0:
-            d = bc(d, self.nd, "d")
-            Dhat = np.tile(d, Hp) if Dhat is None else bc(Dhat, self.nd * Hp, "D̂")
-            d0, Dh0 = d - self.dop, Dhat - self.Dop
-        elif d is not None and np.size(d) != 0:
-            raise ValueError("d size must be (0,)")
+        B = self.B
+        xhat0, ry, held, Rhaty, Rhatu, lastu0, d0, Dh0 = self._period_args(xhat0, ry, d, lastu, Dhat, Rhaty, Rhatu)
         if self.nw > 0 and not held:               # r̂e(k) = ry(k) for the Wr term (execute.jl:351)
             self.hd.set_current_setpoint(ry - self.yop)
         if not self._prepared:                     # like JuMP's model build: before the loop, not in mpcqp_step
@@ -1182,11 +1223,7 @@ class BatchLinMPC:
                            want_Yhat=want_info)
         u0, self.status, self.iters = out[0], out[1], out[2]
         self._Yhat0 = out[3] if want_info else None
-        self._lastu0_prev = lastu0
-        self._winfo = (xhat0, np.tile(ry, Hp) if (held and self.nw > 0) else Rhaty, d0, Dh0)
-        self._ry_now = ry.copy()
-        self._ginfo = (xhat0.copy(), np.tile(ry, Hp) if held else Rhaty, self.Uop.copy() if Rhatu is None else Rhatu)
-        self.solved_once = True
+        self._period_record(xhat0, ry, held, Rhaty, Rhatu, lastu0, d0, Dh0)
         nerr = int(np.sum(self.status == STATUS_ERROR))
         nwarn = int(np.sum(self.status == STATUS_ITERATION_LIMIT))
         if nerr:      # @error branch, src/controller/execute.jl:484-489
@@ -1199,6 +1236,43 @@ class BatchLinMPC:
         return u0 + self.uop
 
     __call__ = moveinput
+
+    def _period_args(self, xhat0, ry, d, lastu, Dhat, Rhaty, Rhatu):
+        """The arguments of `moveinput` checked, broadcast over the batch and turned into what a step takes: x̂0, ry
+        (engineering), whether R̂y is ry held over the horizon (MPCQP_FLAG_RY_CONSTANT is set accordingly), R̂y, R̂u
+        (engineering, or None), and the deviations lastu0, d0, D̂0."""
+        B, Hp = self.B, self.Hp
+        if xhat0 is None:
+            xhat0 = self.xhat0                      # the attached estimator's state (setestimator)
+        xhat0 = np.asarray(xhat0, float)
+        if xhat0.shape != (B, self.nxh):
+            raise ValueError(f"xhat0 size must be ({B},{self.nxh})")
+        bc = lambda v, n, name: self._bc(v, n, name)
+        ry = self.yop if ry is None else bc(ry, self.ny, "ry")
+        held = Rhaty is None                      # R̂y = repeat(ry, Hp): send ry once (MPCQP_FLAG_RY_CONSTANT)
+        Rhaty = None if held else bc(Rhaty, self.nY, "R̂y")
+        want = (self.hd.flags | FLAG_RY_CONSTANT) if held else (self.hd.flags & ~FLAG_RY_CONSTANT)
+        if want != self.hd.flags:
+            self.hd.set_flags(want)
+        Rhatu = None if Rhatu is None else bc(Rhatu, self.nU, "R̂u")
+        lastu0 = self.lastu0 if lastu is None else bc(lastu, self.nu, "lastu") - self.uop
+        d0 = Dh0 = None
+        if self.nd > 0:
+            d = bc(d, self.nd, "d")
+            Dhat = np.tile(d, Hp) if Dhat is None else bc(Dhat, self.nd * Hp, "D̂")
+            d0, Dh0 = d - self.dop, Dhat - self.Dop
+        elif d is not None and np.size(d) != 0:
+            raise ValueError("d size must be (0,)")
+        return xhat0, ry, held, Rhaty, Rhatu, lastu0, d0, Dh0
+
+    def _period_record(self, xhat0, ry, held, Rhaty, Rhatu, lastu0, d0, Dh0):
+        """What `getinfo` and the next period need of the period that has just been solved."""
+        Hp = self.Hp
+        self._lastu0_prev = lastu0
+        self._winfo = (xhat0, np.tile(ry, Hp) if (held and self.nw > 0) else Rhaty, d0, Dh0)
+        self._ry_now = ry.copy()
+        self._ginfo = (xhat0.copy(), np.tile(ry, Hp) if held else Rhaty, self.Uop.copy() if Rhatu is None else Rhatu)
+        self.solved_once = True
 
     def _bc(self, v, n, name):
         a = np.asarray(v, float)
@@ -1291,4 +1365,88 @@ class BatchLinMPC:
                      ("xhatend", "x̂end"), ("Yhats", "Ŷs"), ("Rhaty", "R̂y"), ("Rhatu", "R̂u"), ("Ztilde", "Z̃"), ("Xhat0", "X̂0"), ("Phat", "P̂"), ("Khat", "K̂")):
             if k in info:
                 info[a] = info[k]
+        return info
+
+
+class BatchExplicitMPC(BatchLinMPC):
+    """B independent `ExplicitMPC` controllers (src/controller/explicitmpc.jl:135-179): the LinMPC without constraints, H̃
+    factored once on the device and Z̃ = -H̃⁻¹ q̃ applied every period.  Like the reference's constructor it has no `Cwt`,
+    `Wy` ... `Wr` and `transcription` keywords.  `law=True` also builds the affine law of the default call
+    `moveinput(x̂0, ry, d)`; a period without a horizon-long argument (R̂y, R̂u, D̂) is then one table product.
+
+    Estimator, `setmodel` / `setweights` (factor and law follow), `initstate` and `moveinput` are those of `BatchLinMPC`."""
+
+    def __init__(self, Ahat, Bhu, Chat, Bhd=None, Dhd=None, *, Hp, Hc=2, Mwt=None, Nwt=None, Lwt=None, M_Hp=None, N_Hc=None,
+                 L_Hp=None, law=False, uop=None, yop=None, dop=None, xhop=None, fhop=None, device=0, keep_qp=False, lib=None):
+        self.law = bool(law)
+        self._explicit_ready = False
+        super().__init__(Ahat, Bhu, Chat, Bhd, Dhd, Hp=Hp, Hc=Hc, Mwt=Mwt, Nwt=Nwt, Lwt=Lwt, M_Hp=M_Hp, N_Hc=N_Hc, L_Hp=L_Hp,
+                         Cwt=np.inf, uop=uop, yop=yop, dop=dop, xhop=xhop, fhop=fhop, device=device, keep_qp=keep_qp, lib=lib)
+        self.hd.explicit_prepare(law=self.law)
+        self._explicit_ready = True
+        self._warn_factor()
+
+    def _warn_factor(self):
+        n = int(np.count_nonzero(self.hd.explicit_status()))
+        if n:
+            warnings.warn(f"ExplicitMPC: H̃ is not positive definite, Z̃ = 0 is returned ({n} of {self.B} controllers)", RuntimeWarning)
+
+    def setmodel(self, Ahat, Bhu, Chat, Bhd=None, Dhd=None, *, uop=None, yop=None, dop=None, xhop=None, fhop=None):
+        """`setmodel!` (execute.jl:684-790): new model matrices and, optionally, new operating points -- lastu0 then moves
+        with uop like the reference's (`mpc.lastu0 .+= uop_old .- uop_new`, execute.jl:726), and the state of an attached
+        estimator with x̂op (`estim.x̂0 .+= x̂op_old .- x̂op_new`)."""
+        B, Hp = self.B, self.Hp
+        vec = lambda v, n, old: old if v is None else np.broadcast_to(np.asarray(v, float), (B, n)).copy()
+        if uop is not None:
+            new = vec(uop, self.nu, None)
+            self.lastu0 = self.lastu0 + self.uop - new
+            self.uop = new
+        self.yop, self.dop = vec(yop, self.ny, self.yop), vec(dop, self.nd, self.dop)
+        if xhop is not None:                   # the attached estimator's state keeps its engineering value (x̂0 += x̂op_old - x̂op_new)
+            new = vec(xhop, self.nxh, None)
+            if getattr(self, "xhat0", None) is not None:
+                self.xhat0 = self.xhat0 + self.xhop - new
+            self.xhop = new
+        self.fhop = vec(fhop, self.nxh, self.fhop)
+        self.Uop, self.Yop, self.Dop = np.tile(self.uop, Hp), np.tile(self.yop, Hp), np.tile(self.dop, Hp)
+        super().setmodel(Ahat, Bhu, Chat, Bhd, Dhd)
+        if self._explicit_ready:               # (the handle has refreshed factor and law inside mpcqp_set_model)
+            self._warn_factor()
+
+    def setweights(self, Mwt=None, Nwt=None, Lwt=None, M_Hp=None, N_Hc=None, L_Hp=None):
+        super().setweights(Mwt, Nwt, Lwt, M_Hp=M_Hp, N_Hc=N_Hc, L_Hp=L_Hp)
+        if self._explicit_ready:
+            self._warn_factor()
+
+    def setconstraint(self, **kw):
+        raise MpcqpError("ExplicitMPC does not support constraints.")       # explicitmpc.jl:182-184
+
+    def moveinput(self, xhat0, ry=None, d=None, *, lastu=None, Dhat=None, Rhaty=None, Rhatu=None, want_info=False, want_Z=True):
+        """`moveinput!` (execute.jl:59-80) on the explicit paths: the law when it was built and no horizon-long argument is
+        given (and Ŷ is not asked for), else the explicit step.  The law computes all of Z̃ (the table of nZ̃ rows per
+        controller); `want_Z=False` asks it for u alone, from the table of nu rows -- `self.Z` is NaN after such a period and
+        `getinfo` has nothing to report.  The explicit step always returns Z̃."""
+        default_D = Dhat is None
+        xhat0, ry, held, Rhaty, Rhatu, lastu0, d0, Dh0 = self._period_args(xhat0, ry, d, lastu, Dhat, Rhaty, Rhatu)
+        if self.law and held and Rhatu is None and default_D and not want_info:
+            Z, u0, self.status = self.hd.explicit_law(xhat0, lastu0, ry - self.yop, d0, want_Z=want_Z)
+            self.Z = np.full((self.B, self.nZ), np.nan) if Z is None else Z
+            self._Yhat0 = None
+        else:
+            out = self.hd.explicit_step(xhat0, lastu0, (ry - self.yop) if held else (Rhaty - self.Yop),
+                                        Ru=None if Rhatu is None else Rhatu - self.Uop, d0=d0, Dhat0=Dh0, want_Yhat=want_info)
+            self.Z, u0, self.status = out[0], out[1], out[2]
+            self._Yhat0 = out[3] if want_info else None
+        self.iters = np.zeros(self.B, np.int32)
+        self._period_record(xhat0, ry, held, Rhaty, Rhatu, lastu0, d0, Dh0)
+        self.lastu0 = u0.copy()
+        return u0 + self.uop
+
+    __call__ = moveinput
+
+    def getinfo(self):
+        """`getinfo` of the ExplicitMPC (explicitmpc.jl:200-220): as BatchLinMPC, with x̂end filled with NaN (:217)."""
+        info = super().getinfo()
+        info["x̂end"] = np.full((self.B, self.nxh), np.nan)
+        info["xhatend"] = info["x̂end"]
         return info

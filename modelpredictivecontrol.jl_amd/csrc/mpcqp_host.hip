@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mpcqp.h"
+#include "explicit_launch.h"
 #include "kf_cov_launch.h"
 #include "kf_dare_launch.h"
 #include "mpcqp_hostutil.h"
@@ -86,6 +87,14 @@ struct mpcqp_handle_s {
                                      // stage-structured kernel (one U row per step) takes the handle
     bool dual_reg_given = false;     // mpcqp_dims.dual_reg > 0 (else each kernel's own default)
     DBuf ms_X, ms_defect, ms_scratch, ms_next;
+    // ExplicitMPC (mpcqp_explicit_prepare): ex_Hinv / ex_st are what k_explicit_factor left for the CURRENT H~ -- every
+    // setter that changes H~ runs explicit_refresh on a prepared handle -- and ex_law_z / ex_law_u the law tables (ex_law).
+    // ex_stale: H~ changed while the handle had finite rows (the explicit calls answer MPCQP_ERR_ORDER then, the setters do
+    // not factor); the first explicit call after the rows are gone factors again (explicit_current)
+    bool ex_prepared = false, ex_law = false, ex_stale = false;
+    DBuf ex_Hinv, ex_Lsum, ex_st, ex_law_z, ex_law_u;
+    DBuf ex_bx, ex_blu, ex_bry, ex_bd0, ex_bdh, ex_bZ0, ex_bZk, ex_bu0, ex_bst;     // device buffers of the law build
+    int ex_waves_z = 0, ex_waves_u = 0;
 };
 
 static int dev_alloc(mpcqp_handle h, DBuf& b, size_t bytes) {
@@ -296,6 +305,8 @@ int mpcqp_get_sizes(mpcqp_handle h, mpcqp_sizes* out) {
     return MPCQP_OK;
 }
 
+static int explicit_refresh(mpcqp_handle h, hipStream_t st);
+
 static bool terminal_on(const Dims& d) { return (d.gmask >> (2 * P_X)) & 3u; }
 
 // the condensed kernels keep one problem's tables in the LDS of a CU: a handle whose problem does not fit (nZ~ beyond ~165 at
@@ -380,6 +391,8 @@ int mpcqp_set_model(mpcqp_handle h, const double* Ahat, const double* Bu, const 
     invalidate_stepc(h);
     rc = condense(h, h->stream, true);
     if (rc) return rc;
+    rc = explicit_refresh(h, h->stream);
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
 }
@@ -402,6 +415,7 @@ int mpcqp_set_weights(mpcqp_handle h, const double* Mdiag, const double* Ndiag,
     h->have_weights = true;
     invalidate_stepc(h);
     { int rc = refresh_hessian(h, h->stream); if (rc) return rc; }
+    { int rc = explicit_refresh(h, h->stream); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
 }
@@ -420,6 +434,7 @@ int mpcqp_set_output_weight_blocks(mpcqp_handle h, const double* Mblk) {
     }
     invalidate_stepc(h);
     { int rc = refresh_hessian(h, h->stream); if (rc) return rc; }
+    { int rc = explicit_refresh(h, h->stream); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
 }
@@ -473,6 +488,7 @@ int mpcqp_set_dense_weights(mpcqp_handle h, const double* M_Hp, const double* N_
     d.dense_w = (h->m.Mfull || h->m.Ldense) ? 1 : 0;     // (a dense N_Hc only changes H̃: any step kernel serves it)
     invalidate_stepc(h);
     { int rc = refresh_hessian(h, h->stream); if (rc) return rc; }
+    { int rc = explicit_refresh(h, h->stream); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
 }
@@ -848,7 +864,8 @@ int mpcqp_recondense_device(mpcqp_handle h, void* stream) {
     if (!h) return MPCQP_ERR_NULL;
     if (!h->have_model || !h->have_weights) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
-    return condense(h, (hipStream_t)stream, true);
+    int rc = condense(h, (hipStream_t)stream, true);
+    return rc ? rc : explicit_refresh(h, (hipStream_t)stream);
 }
 
 int mpcqp_get(mpcqp_handle h, int which, double* out) {
@@ -933,6 +950,16 @@ int mpcqp_get(mpcqp_handle h, int which, double* out) {
             if (!h->have_kf) return MPCQP_ERR_ORDER;
             HIPCHK(hipMemcpy(out, h->kf_K.p, B * d.nxh * h->kf.nym * sizeof(double), hipMemcpyDeviceToHost));
             return MPCQP_OK;
+        case MPCQP_GET_EXPLICIT_LAW: {
+            if (!h->ex_prepared || !h->ex_law) return MPCQP_ERR_ORDER;
+            const int n = d.nZ, ncol = ex::law_ncol(d), kp = ex::law_kp(d);
+            int rc = fetch(h->ex_law_z.p, ex::law_doubles(d, n), tmp);
+            if (rc) return rc;
+            for (size_t R = 0; R < B * n; ++R)
+                for (int k = 0; k < ncol; ++k)
+                    out[(R / n) * (size_t)n * ncol + (size_t)k * n + R % n] = tmp[ex::law_index(R, k, kp)];
+            return MPCQP_OK;
+        }
 #ifdef MPCQP_PROFILE
         case 99:     /* per-phase cycle counters of profiling builds (-DMPCQP_PROFILE): (16,B) */
             if (!h->prof.p) return MPCQP_ERR_ORDER;
@@ -942,6 +969,243 @@ int mpcqp_get(mpcqp_handle h, int which, double* out) {
         default:
             return MPCQP_ERR_ARG;
     }
+}
+
+// ---- ExplicitMPC (src/controller/explicitmpc.jl): H~ factored once per model, a solve or a gain per period ----------------
+
+// what mpcqp_explicit_prepare refuses with MPCQP_ERR_ARG, and what turns a prepared handle away from the explicit calls later
+static bool explicit_constrained(mpcqp_handle h) {
+    return h->d.neps != 0 || h->d.gmask != 0 || h->transcription != MPCQP_SINGLE_SHOOTING;
+}
+
+static void explicit_step_args(mpcqp_handle h, ex::StepArgs& a, uint32_t flags) {
+    a.d = h->d;
+    a.d.flags = flags;
+    a.m = h->m;
+    a.Hinv = (const double*)h->ex_Hinv.p;
+    a.Lsum = (const double*)h->ex_Lsum.p;
+    a.fstatus = (const int32_t*)h->ex_st.p;
+}
+
+// Factor (and law) of a prepared handle for the H~ that is resident now, enqueued on `st` behind K2.  Nothing on the host.
+// A handle that has become constrained since (its explicit calls answer MPCQP_ERR_ORDER, and with the row groups its problem
+// may have outgrown the condensed kernels) is only marked: the setter that called goes on serving the other kernels.
+static int explicit_refresh(mpcqp_handle h, hipStream_t st) {
+    if (!h->ex_prepared) return MPCQP_OK;
+    if (!h->have_model || !h->have_weights) return MPCQP_OK;
+    if (explicit_constrained(h)) { h->ex_stale = true; return MPCQP_OK; }
+    const Dims& d = h->d;
+    const size_t B = d.B, sz = sizeof(double);
+    { int rc = ensure_hessian(h, st); if (rc) return rc; }
+    if (!h->hessian_valid) return MPCQP_ERR_UNSUPPORTED;
+    h->ex_stale = false;
+    if (h->step_timed) HIPCHK(hipStreamWaitEvent(st, h->ev_s1, 0));     // (an explicit call on another stream may still read the tables)
+    ex::FactorArgs f{};
+    f.Hpk = h->m.Hpk; f.Ldiag = h->m.Ldiag; f.jl = h->m.jl;
+    f.Hinv = (double*)h->ex_Hinv.p; f.Lsum = (double*)h->ex_Lsum.p;
+    f.status = (int32_t*)h->ex_st.p; f.B = d.B; f.n = d.nZ; f.npk = d.npk; f.nu = d.nu; f.Hp = d.Hp;
+    HIPCHK(ex::launch_explicit_factor(f, st));
+    if (!h->ex_law) return MPCQP_OK;
+    // the law by superposition: the explicit step itself on the 1 + nx + nu + ny + nd unit inputs, held over the horizon
+    ex::LawBuildArgs lb{};
+    lb.xhat0 = (double*)h->ex_bx.p; lb.lastu0 = (double*)h->ex_blu.p; lb.ry = (double*)h->ex_bry.p;
+    lb.d0 = d.nd > 0 ? (double*)h->ex_bd0.p : nullptr; lb.Dhat0 = d.nd > 0 ? (double*)h->ex_bdh.p : nullptr;
+    lb.Z0 = (const double*)h->ex_bZ0.p; lb.Zk = (const double*)h->ex_bZk.p;
+    lb.table_z = (double*)h->ex_law_z.p; lb.table_u = (double*)h->ex_law_u.p;
+    lb.B = d.B; lb.n = d.nZ; lb.nx = d.nxh; lb.nu = d.nu; lb.ny = d.ny; lb.nd = d.nd; lb.Hp = d.Hp; lb.kp = ex::law_kp(d);
+    ex::StepArgs a{};
+    explicit_step_args(h, a, MPCQP_FLAG_RY_CONSTANT);
+    a.xhat0 = lb.xhat0; a.lastu0 = lb.lastu0; a.Ry = lb.ry; a.Ru = nullptr; a.d0 = lb.d0; a.Dhat0 = lb.Dhat0;
+    a.u0 = (double*)h->ex_bu0.p; a.status = (int32_t*)h->ex_bst.p;
+    const int ncol = ex::law_ncol(d);
+    for (int k = 0; k < ncol; ++k) {
+        HIPCHK(hipMemsetAsync(lb.xhat0, 0, B * d.nxh * sz, st));
+        HIPCHK(hipMemsetAsync(lb.lastu0, 0, B * d.nu * sz, st));
+        HIPCHK(hipMemsetAsync(lb.ry, 0, B * d.ny * sz, st));
+        if (d.nd > 0) {
+            HIPCHK(hipMemsetAsync(lb.d0, 0, B * d.nd * sz, st));
+            HIPCHK(hipMemsetAsync(lb.Dhat0, 0, B * d.nD * sz, st));
+        }
+        lb.k = k;
+        if (k > 0) HIPCHK(ex::launch_explicit_law_unit(lb, st));
+        a.Z = k == 0 ? (double*)h->ex_bZ0.p : (double*)h->ex_bZk.p;
+        HIPCHK(ex::launch_explicit_step(a, st));
+        HIPCHK(ex::launch_explicit_law_pack(lb, st));
+    }
+    return MPCQP_OK;
+}
+
+// what every explicit call does first: the factor of a handle whose H~ changed while it was constrained
+static int explicit_current(mpcqp_handle h, hipStream_t st) { return h->ex_stale ? explicit_refresh(h, st) : MPCQP_OK; }
+
+int mpcqp_explicit_prepare(mpcqp_handle h, int32_t with_law) {
+    if (!h) return MPCQP_ERR_NULL;
+    if (with_law & ~MPCQP_EXPLICIT_LAW) return MPCQP_ERR_ARG;
+    if (!h->have_model || !h->have_weights) return MPCQP_ERR_ORDER;
+    if (explicit_constrained(h)) return MPCQP_ERR_ARG;          // "ExplicitMPC does not support constraints"
+    const Dims& d = h->d;
+    if (h->stage_only || !condensed_fits(d) || !ex::explicit_available()) return MPCQP_ERR_UNSUPPORTED;
+    if (d.nZ > ex::EX_NMAX) return MPCQP_ERR_UNSUPPORTED;
+    // (cannot happen: the step's LDS is below the condensed kernels' carve-up, explicit_launch.h)
+    if (ex::step_lds_doubles(d) * sizeof(double) > ex::EX_LDS_MAX) return MPCQP_ERR_UNSUPPORTED;
+    ON_DEVICE(h);
+    const size_t B = d.B, n = d.nZ, sz = sizeof(double);
+    const bool law = with_law & MPCQP_EXPLICIT_LAW;
+    int rc = dev_alloc(h, h->ex_Hinv, B * ex::tri((int)n) * sz);
+    if (!rc) rc = dev_alloc(h, h->ex_Lsum, B * n * sz);
+    if (!rc) rc = dev_alloc(h, h->ex_st, B * sizeof(int32_t));
+    if (!rc && law) {
+        const size_t nz = ex::law_doubles(d, d.nZ) * sz, nu_ = ex::law_doubles(d, d.nu) * sz;
+        const bool fresh = !h->ex_law_z.p;
+        rc = dev_alloc(h, h->ex_law_z, nz);
+        if (!rc) rc = dev_alloc(h, h->ex_law_u, nu_);
+        if (!rc) rc = dev_alloc(h, h->ex_bx, B * d.nxh * sz);
+        if (!rc) rc = dev_alloc(h, h->ex_blu, B * d.nu * sz);
+        if (!rc) rc = dev_alloc(h, h->ex_bry, B * d.ny * sz);
+        if (!rc && d.nd > 0) rc = dev_alloc(h, h->ex_bd0, B * d.nd * sz);
+        if (!rc && d.nd > 0) rc = dev_alloc(h, h->ex_bdh, B * d.nD * sz);
+        if (!rc) rc = dev_alloc(h, h->ex_bZ0, B * n * sz);
+        if (!rc) rc = dev_alloc(h, h->ex_bZk, B * n * sz);
+        if (!rc) rc = dev_alloc(h, h->ex_bu0, B * d.nu * sz);
+        if (!rc) rc = dev_alloc(h, h->ex_bst, B * sizeof(int32_t));
+        if (rc) return rc;
+        // the padding of the tables -- the column of an odd count, the rows behind the batch -- is read and has to be finite: zeroed
+        // where the tables are allocated and never written.  (Not again by a repeated prepare: a law call of the caller's may
+        // be reading the tables; the build of explicit_refresh waits for it.)
+        if (fresh) {
+            HIPCHK(hipMemsetAsync(h->ex_law_z.p, 0, nz, h->stream));
+            HIPCHK(hipMemsetAsync(h->ex_law_u.p, 0, nu_, h->stream));
+        }
+        h->ex_waves_z = ex::explicit_law_waves_for(h->device, (long)((B * n + WAVE - 1) / WAVE));
+        h->ex_waves_u = ex::explicit_law_waves_for(h->device, (long)((B * d.nu + WAVE - 1) / WAVE));
+    }
+    if (rc) return rc;
+    h->ex_prepared = true; h->ex_law = law;
+    rc = explicit_refresh(h, h->stream);
+    if (rc) { h->ex_prepared = false; return rc; }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
+int mpcqp_explicit_status(mpcqp_handle h, int32_t* out) {
+    if (!h || !out) return MPCQP_ERR_NULL;
+    if (!h->ex_prepared || explicit_constrained(h)) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    { int rc = explicit_current(h, h->stream); if (rc) return rc; }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, h->ex_st.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MPCQP_OK;
+}
+
+int mpcqp_explicit_step_device(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* Ry,
+                               const double* Ru, const double* d0, const double* Dhat0, double* Ztilde, double* u0,
+                               int32_t* status, double* Yhat0, void* stream) {
+    if (!h || !xhat0 || !lastu0 || !Ry || !Ztilde || !u0 || !status) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    if (d.nd > 0 && (!d0 || !Dhat0)) return MPCQP_ERR_NULL;
+    if (!h->ex_prepared || explicit_constrained(h)) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    { int rc = explicit_current(h, st); if (rc) return rc; }
+    ex::StepArgs a{};
+    explicit_step_args(h, a, d.flags);
+    a.xhat0 = xhat0; a.lastu0 = lastu0; a.Ry = Ry; a.Ru = Ru; a.d0 = d0; a.Dhat0 = Dhat0;
+    a.Z = Ztilde; a.u0 = u0; a.status = status; a.Yhat0 = Yhat0;
+    if (d.flags & MPCQP_FLAG_KEEP_QP) {
+        int rc = dev_alloc(h, h->keep_q, (size_t)d.B * d.nZ * sizeof(double));
+        if (!rc) rc = dev_alloc(h, h->keep_F, (size_t)d.B * d.nY * sizeof(double));
+        if (rc) return rc;
+        a.q_keep = (double*)h->keep_q.p;
+        a.F_keep = (double*)h->keep_F.p;
+    }
+    HIPCHK(hipEventRecord(h->ev_s0, st));
+    HIPCHK(ex::launch_explicit_step(a, st));
+    HIPCHK(hipEventRecord(h->ev_s1, st));
+    h->step_timed = true;
+    return MPCQP_OK;
+}
+
+int mpcqp_explicit_law_device(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* ry,
+                              const double* d0, double* Ztilde, double* u0, int32_t* status, void* stream) {
+    if (!h || !xhat0 || !lastu0 || !ry || !u0 || !status) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    if (!h->ex_prepared || !h->ex_law || explicit_constrained(h)) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    { int rc = explicit_current(h, st); if (rc) return rc; }
+    ex::LawArgs a{};
+    a.table = (const double*)(Ztilde ? h->ex_law_z.p : h->ex_law_u.p);
+    a.xhat0 = xhat0; a.lastu0 = lastu0; a.ry = ry; a.d0 = d0;
+    a.Z = Ztilde; a.u0 = u0; a.status = status; a.fstatus = (const int32_t*)h->ex_st.p;
+    a.B = d.B; a.rows = Ztilde ? d.nZ : d.nu; a.nx = d.nxh; a.nu = d.nu; a.ny = d.ny; a.nd = d.nd; a.kp = ex::law_kp(d);
+    a.nwaves = Ztilde ? h->ex_waves_z : h->ex_waves_u;
+    HIPCHK(hipEventRecord(h->ev_s0, st));
+    HIPCHK(ex::launch_explicit_law(a, st));
+    HIPCHK(hipEventRecord(h->ev_s1, st));
+    h->step_timed = true;
+    return MPCQP_OK;
+}
+
+int mpcqp_explicit_step(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* Ry, const double* Ru,
+                        const double* d0, const double* Dhat0, double* Ztilde, double* u0, int32_t* status, double* Yhat0) {
+    if (!h || !xhat0 || !lastu0 || !Ry || !Ztilde || !u0 || !status) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    if (d.nd > 0 && (!d0 || !Dhat0)) return MPCQP_ERR_NULL;
+    if (!h->ex_prepared || explicit_constrained(h)) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    const size_t B = d.B, sz = sizeof(double);
+    const size_t nry = (d.flags & MPCQP_FLAG_RY_CONSTANT) ? d.ny : d.nY;
+    int rc = upload(h, h->s_x, xhat0, B * d.nxh * sz);
+    if (!rc) rc = upload(h, h->s_lu, lastu0, B * d.nu * sz);
+    if (!rc) rc = upload(h, h->s_ry, Ry, B * nry * sz);
+    if (!rc && Ru) rc = upload(h, h->s_ru, Ru, B * d.nU * sz);
+    if (!rc && d.nd > 0) rc = upload(h, h->s_d0, d0, B * d.nd * sz);
+    if (!rc && d.nd > 0) rc = upload(h, h->s_dh, Dhat0, B * d.nD * sz);
+    if (!rc) rc = dev_alloc(h, h->s_Z, B * d.nZ * sz);
+    if (!rc) rc = dev_alloc(h, h->s_u0, B * d.nu * sz);
+    if (!rc) rc = dev_alloc(h, h->s_st, B * sizeof(int32_t));
+    if (!rc && Yhat0) rc = dev_alloc(h, h->s_yh, B * d.nY * sz);
+    if (rc) return rc;
+    rc = mpcqp_explicit_step_device(h, (const double*)h->s_x.p, (const double*)h->s_lu.p, (const double*)h->s_ry.p,
+                                    Ru ? (const double*)h->s_ru.p : nullptr, d.nd > 0 ? (const double*)h->s_d0.p : nullptr,
+                                    d.nd > 0 ? (const double*)h->s_dh.p : nullptr, (double*)h->s_Z.p, (double*)h->s_u0.p,
+                                    (int32_t*)h->s_st.p, Yhat0 ? (double*)h->s_yh.p : nullptr, h->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(Ztilde, h->s_Z.p, B * d.nZ * sz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(u0, h->s_u0.p, B * d.nu * sz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(status, h->s_st.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (Yhat0) HIPCHK(hipMemcpyAsync(Yhat0, h->s_yh.p, B * d.nY * sz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
+int mpcqp_explicit_law(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* ry, const double* d0,
+                       double* Ztilde, double* u0, int32_t* status) {
+    if (!h || !xhat0 || !lastu0 || !ry || !u0 || !status) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    if (!h->ex_prepared || !h->ex_law || explicit_constrained(h)) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    const size_t B = d.B, sz = sizeof(double);
+    int rc = upload(h, h->s_x, xhat0, B * d.nxh * sz);
+    if (!rc) rc = upload(h, h->s_lu, lastu0, B * d.nu * sz);
+    if (!rc) rc = upload(h, h->s_ry, ry, B * d.ny * sz);
+    if (!rc && d.nd > 0) rc = upload(h, h->s_d0, d0, B * d.nd * sz);
+    if (!rc && Ztilde) rc = dev_alloc(h, h->s_Z, B * d.nZ * sz);
+    if (!rc) rc = dev_alloc(h, h->s_u0, B * d.nu * sz);
+    if (!rc) rc = dev_alloc(h, h->s_st, B * sizeof(int32_t));
+    if (rc) return rc;
+    rc = mpcqp_explicit_law_device(h, (const double*)h->s_x.p, (const double*)h->s_lu.p, (const double*)h->s_ry.p,
+                                   d.nd > 0 ? (const double*)h->s_d0.p : nullptr, Ztilde ? (double*)h->s_Z.p : nullptr,
+                                   (double*)h->s_u0.p, (int32_t*)h->s_st.p, h->stream);
+    if (rc) return rc;
+    if (Ztilde) HIPCHK(hipMemcpyAsync(Ztilde, h->s_Z.p, B * d.nZ * sz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(u0, h->s_u0.p, B * d.nu * sz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(status, h->s_st.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
 }
 
 int mpcqp_kf_set(mpcqp_handle h, const double* Khat, const int32_t* i_ym, int32_t nym) {
