@@ -463,6 +463,76 @@ int mpcqp_kf_solve_steady_device(mpcqp_handle h, void* stream);
 int mpcqp_kf_steady_iters(mpcqp_handle h, int32_t* out);
 int mpcqp_kf_steady_path(mpcqp_handle h, int32_t* out);
 
+/* ---- sim!: closed loops of the whole batch with the plant on the device (src/plot_sim.jl:241-319) ----------------
+ * mpcqp_sim_set_plant attaches one LinModel per controller, the `plant` keyword of sim!: A (nxp,nxp,B), Bu (nxp,nu,B),
+ * C (ny,nxp,B), Bd (nxp,nd,B), Dd (ny,nd,B), fx = fop - xop (nxp,B); Bd, Dd and fx may be NULL (zero).  Layouts of
+ * mpcqp_set_model, deviation variables.  The plant has the handle's nu, ny and nd; nxp is its own (a mismatched plant of
+ * another order is legal).  The arrays are copied; the call may be repeated.  nxp < 1: MPCQP_ERR_ARG; nxp > 64, a handle with
+ * max(nu, ny, nd) > 64 or a library built without the kernel: MPCQP_ERR_UNSUPPORTED.
+ *
+ * mpcqp_sim (host pointers, synchronous) / mpcqp_sim_device (device pointers, asynchronous on `stream`) run io->N periods of
+ * sim_closedloop! for every controller, without a host synchronisation between the periods.  Period i = 0..N-1:
+ *     1. d0  = d + d_step + σd∘w_d[i]
+ *     2. y0  = C x0 + Dd d0 + y_step + σy∘w_y[i],  y0m = y0[i_ym]
+ *     3. preparestate!: the correction (direct = 1; nothing with direct = 0)
+ *     4. records Y, X, D, X̂ -- the estimate after the correction -- and Ŷ = Ĉ x̂0 + D̂d d0
+ *     5. moveinput!: mpcqp_explicit_law on a handle prepared with MPCQP_EXPLICIT_LAW (io->Ru == NULL), mpcqp_explicit_step on
+ *        another prepared explicit handle, else mpcqp_step; set point and disturbance held over the horizon
+ *     6. ud0 = u0 + u_step + σu∘w_u[i]; records U, Ud
+ *     7. x0 <- A x0 + Bu ud0 + Bd d0 + fx + σx∘w_x[i]
+ *     8. updatestate!: the prediction (direct = 1), or the correction with y0m and then the prediction (direct = 0)
+ * The launches of a period are the existing device entry points (mpcqp_kf_correct_device, the controller's,
+ * mpcqp_kf_predict_device / _update_device) and the kernel k_sim_plant between them: one launch of it does items 6-7 of period i
+ * and items 1-2 of period i+1, a second one writes X̂ and Ŷ when either is asked for.  Every estimator (steady, time-varying,
+ * both forms, the NaN rule: a NaN in y0m -- a NaN draw in w_y with its σ -- skips that member's correction) and every
+ * controller kernel is served as those entry points serve it.
+ *   ry       (ny,B), held over the run; (ny,N,B) with MPCQP_SIM_FLAG_RY_PER_PERIOD
+ *   Ru       (nU,B) or NULL, as in mpcqp_step (the `ru` of sim!, repeated over Hp)
+ *   d        (nd,B) (NULL iff nd == 0)
+ *   *_step, sigma_*   (n,B) or NULL: u, y, d (nu, ny, nd) and, the σ only, x (nxp)
+ *   w_*      (n,N,B) standard-normal draws, inputs so that a run is reproducible and the host can check it exactly: read
+ *            only with their σ, which they are scaled by; a σ without its draws: MPCQP_ERR_NULL
+ *   x0 (nxp,B), xhat0 (nx̂,B), lastu0 (nu,B)   in/out: the state of period N on return
+ *   Ztilde   (nZ,B) in/out, the warm start of mpcqp_step and Z̃ of the last period; may be NULL on the law path (u0 alone, from
+ *            the table of nu rows), MPCQP_ERR_NULL elsewhere.  A handle with MPCQP_FLAG_WARM_DUAL keeps its multipliers: two
+ *            calls of N/2 periods equal one of N
+ *   Y (ny) X (nxp) D (nd) Xhat (nx̂) Yhat (ny) U (nu) Ud (nu)   records (n,N,B), each may be NULL (not written)
+ *   status   (N,B) int32 or NULL: the status of the controller's call per period
+ * MPCQP_ERR_ARG for N <= 0 or an unknown flag; MPCQP_ERR_ORDER without a plant, an estimator or a controller that can step
+ * (model and weights; an explicit handle that has become constrained).
+ * Two execution paths serve the call; mpcqp_sim_path tells which one the handle gets (for a call with ry held, Ru == NULL and
+ * without MPCQP_SIM_FLAG_NO_FUSE; any other call takes the per-period path):
+ *   MPCQP_SIM_PATH_PERIOD  the launches above; every handle.
+ *   MPCQP_SIM_PATH_FUSED   kernel k_sim_explicit runs the whole N-period loop in ONE launch: a handle prepared with
+ *                          MPCQP_EXPLICIT_LAW whose gain is steady (mpcqp_kf_set or mpcqp_kf_set_steady) and whose
+ *                          max(nx̂, nxp, nu, ny, nd, nym) <= 16.  One controller per 16-lane row, its tables loaded once; both
+ *                          values of `direct`; the NaN rule and the status-2 policy (u0 = lastu0 every period) per member.  It
+ *                          computes u0 alone: Ztilde is neither read nor written.  Results agree with the per-period path to
+ *                          rounding (the sums run in another order), not bit for bit.
+ * While mpcqp_sim_device enqueues the per-period path it sets MPCQP_FLAG_RY_CONSTANT and clears the set point of
+ * mpcqp_set_current_setpoint on the handle, and puts both back before it returns: like every call on a handle, it must not
+ * run beside another call on the same handle (a handle is not thread-safe, see the top of this file). */
+#define MPCQP_SIM_FLAG_RY_PER_PERIOD (1u << 0)
+#define MPCQP_SIM_FLAG_NO_FUSE       (1u << 1)
+#define MPCQP_SIM_PATH_PERIOD        0
+#define MPCQP_SIM_PATH_FUSED         1
+typedef struct {
+    int32_t  N;
+    uint32_t flags;       /* MPCQP_SIM_FLAG_* */
+    const double *ry, *Ru, *d;
+    const double *u_step, *y_step, *d_step;
+    const double *sigma_u, *sigma_y, *sigma_d, *sigma_x;
+    const double *w_u, *w_y, *w_d, *w_x;
+    double *x0, *xhat0, *lastu0, *Ztilde;
+    double *Y, *X, *D, *Xhat, *Yhat, *U, *Ud;
+    int32_t* status;
+} mpcqp_sim_io;
+int mpcqp_sim_set_plant(mpcqp_handle h, int32_t nxp, const double* A, const double* Bu, const double* C, const double* Bd,
+                        const double* Dd, const double* fx);
+int mpcqp_sim(mpcqp_handle h, const mpcqp_sim_io* io);
+int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io, void* stream);
+int mpcqp_sim_path(mpcqp_handle h);
+
 
 /* ---- which kernel runs a step; building specialised kernels ahead of the control loop -----------
  * A step runs on (MPCQP_KERNEL_AOT) a kernel specialised on the handle's dimensions that is compiled

@@ -4,7 +4,7 @@ JuliaControl/ModelPredictiveControl.jl behind a C-ABI (include/mpcqp.h).
 The directory name carries a dot, so it is imported through the `mpcqp` alias package at the
 repository root (`import mpcqp`), which points its `__path__` here.
 """
-from .api import (BatchLinMPC, BatchExplicitMPC, Handle, MultiHandle, MpcqpError, load_library, move_blocking, colmajor,  # noqa: F401
+from .api import (BatchLinMPC, BatchExplicitMPC, SimResult, Handle, MultiHandle, MpcqpError, load_library, move_blocking, colmajor,  # noqa: F401
                   steady_kalman_gain,
                   STATUS_OPTIMAL, STATUS_ITERATION_LIMIT, STATUS_ERROR, EXPORTS,
                   FLAG_RY_CONSTANT, FLAG_COLD_START, FLAG_KEEP_QP, FLAG_WARM_DUAL,

@@ -17,6 +17,7 @@ There is no CPU fallback: the shared library is the HIP build and every compute 
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 import types
 import warnings
@@ -35,6 +36,8 @@ GET_HESSIAN, GET_STEPRESP, GET_KMAT, GET_BVEC, GET_QTILDE, GET_FVEC, GET_AUDIT, 
 GET_KF_COV, GET_KF_GAIN = 10, 11
 GET_EXPLICIT_LAW = 12
 EXPLICIT_LAW = 1       # bit of mpcqp_explicit_prepare's with_law
+SIM_FLAG_RY_PER_PERIOD, SIM_FLAG_NO_FUSE = 1, 2     # mpcqp_sim_io.flags
+SIM_PATH_PERIOD, SIM_PATH_FUSED = 0, 1    # mpcqp_sim_path
 KF_STATUS_OK, KF_STATUS_DROPPED = 0, 2
 KF_STEADY_OK, KF_STEADY_NOT_CONVERGED, KF_STEADY_BROKE_DOWN = 0, 1, 2      # mpcqp_kf_status after mpcqp_kf_set_steady
 EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_create",
@@ -48,6 +51,7 @@ EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_cre
            "mpcqp_kf_steady_path",
            "mpcqp_explicit_prepare", "mpcqp_explicit_status", "mpcqp_explicit_step", "mpcqp_explicit_step_device",
            "mpcqp_explicit_law", "mpcqp_explicit_law_device",
+           "mpcqp_sim_set_plant", "mpcqp_sim", "mpcqp_sim_device", "mpcqp_sim_path",
            "mpcqp_set_output_weight_blocks", "mpcqp_set_dense_weights", "mpcqp_set_custom_constraints", "mpcqp_set_custom_bounds",
            "mpcqp_set_flags", "mpcqp_set_iteration_limit", "mpcqp_set_transcription", "mpcqp_transcription_supported", "mpcqp_set_current_setpoint", "mpcqp_prepare", "mpcqp_kernel_kind", "mpcqp_lds_bytes", "mpcqp_row_groups", "mpcqp_step_consts_builds", "mpcqp_prebuild",
            "mpcqp_last_build_error", "mpcqp_multi_create", "mpcqp_multi_destroy", "mpcqp_multi_ndev",
@@ -77,6 +81,17 @@ BOUND_FIELDS = ("U0min", "U0max", "DUmin", "DUmax", "Y0min", "Y0max", "x0min", "
 
 class Bounds(C.Structure):
     _fields_ = [(k, _dp) for k in BOUND_FIELDS]
+
+
+SIM_IO_IN = ("ry", "Ru", "d", "u_step", "y_step", "d_step", "sigma_u", "sigma_y", "sigma_d", "sigma_x", "w_u", "w_y", "w_d", "w_x")
+SIM_IO_STATE = ("x0", "xhat0", "lastu0", "Ztilde")
+SIM_IO_RECORDS = ("Y", "X", "D", "Xhat", "Yhat", "U", "Ud")
+
+
+class SimIO(C.Structure):
+    """mpcqp_sim_io of include/mpcqp.h"""
+    _fields_ = ([("N", C.c_int32), ("flags", C.c_uint32)] + [(k, C.c_void_p) for k in SIM_IO_IN + SIM_IO_STATE + SIM_IO_RECORDS]
+                + [("status", C.c_void_p)])
 
 
 class MpcqpError(RuntimeError):
@@ -199,6 +214,11 @@ def load_library(path: str | None = None):
         lib.mpcqp_explicit_step_device.argtypes = [C.c_void_p] * 12
         lib.mpcqp_explicit_law.argtypes = [C.c_void_p] * 8
         lib.mpcqp_explicit_law_device.argtypes = [C.c_void_p] * 9
+    if hasattr(lib, "mpcqp_sim"):
+        lib.mpcqp_sim_set_plant.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
+        lib.mpcqp_sim.argtypes = [C.c_void_p, C.POINTER(SimIO)]
+        lib.mpcqp_sim_device.argtypes = [C.c_void_p, C.POINTER(SimIO), C.c_void_p]
+        lib.mpcqp_sim_path.argtypes = [C.c_void_p]
     lib.mpcqp_prepare.argtypes = [C.c_void_p]
     lib.mpcqp_kernel_kind.argtypes = [C.c_void_p]
     lib.mpcqp_lds_bytes.argtypes = [C.c_void_p]
@@ -490,6 +510,48 @@ class Handle:
         v = lambda p: C.c_void_p(int(p)) if p else None
         _chk(self.lib, self.lib.mpcqp_explicit_law_device(self.h, v(xhat0), v(lastu0), v(ry), v(d0), v(Z), v(u0), v(status), v(stream)))
 
+    # -- sim!: closed loops of the whole batch, the plant on the device
+    def sim_set_plant(self, A, Bu, Cm, Bd=None, Dd=None, fx=None):
+        """mpcqp_sim_set_plant: A (B,nxp,nxp), Bu, Cm, Bd, Dd in ABI layout (see `colmajor`), fx = fop - xop (B,nxp)."""
+        args = [None if a is None else _f64(a) for a in (A, Bu, Cm, Bd, Dd, fx)]
+        nxp = int(round(np.sqrt(args[0].size // self.B)))
+        _chk(self.lib, self.lib.mpcqp_sim_set_plant(self.h, nxp, *[_ptr(a) for a in args]))
+        self.nxp = nxp
+
+    def sim_path(self):
+        return self.lib.mpcqp_sim_path(self.h)
+
+    def sim(self, N, flags=0, **arrays):
+        """Host-pointer mpcqp_sim.  `arrays`: the fields of mpcqp_sim_io by name, NumPy arrays in ABI layout ([B][n] or
+        [B][N][n]) or None; float64 and C-contiguous ones among x0, xhat0, lastu0, Ztilde and the records are written in place."""
+        io = SimIO(N=int(N), flags=int(flags))
+        keep = []
+        for k, v in arrays.items():
+            if v is None:
+                continue
+            if k in SIM_IO_IN:
+                v = _f64(v)
+            elif k == "status":
+                if v.dtype != np.int32 or not v.flags.c_contiguous:
+                    raise ValueError("status must be a C-contiguous int32 array")
+            elif k in SIM_IO_STATE + SIM_IO_RECORDS:
+                if v.dtype != np.float64 or not v.flags.c_contiguous:
+                    raise ValueError(f"{k} must be a C-contiguous float64 array (it is written in place)")
+            else:
+                raise TypeError(f"mpcqp_sim_io has no field {k!r}")
+            keep.append(v)
+            setattr(io, k, v.ctypes.data)
+        _chk(self.lib, self.lib.mpcqp_sim(self.h, C.byref(io)))
+
+    def sim_device(self, N, flags=0, stream=0, **addresses):
+        """mpcqp_sim_device: the fields of mpcqp_sim_io as integer device addresses (0 = NULL); asynchronous on `stream`."""
+        io = SimIO(N=int(N), flags=int(flags))
+        for k, v in addresses.items():
+            if k not in SIM_IO_IN + SIM_IO_STATE + SIM_IO_RECORDS + ("status",):
+                raise TypeError(f"mpcqp_sim_io has no field {k!r}")
+            setattr(io, k, int(v) if v else None)
+        _chk(self.lib, self.lib.mpcqp_sim_device(self.h, C.byref(io), C.c_void_p(int(stream)) if stream else None))
+
     def recondense_device(self, stream=0):
         _chk(self.lib, self.lib.mpcqp_recondense_device(self.h, C.c_void_p(int(stream)) if stream else None))
 
@@ -739,6 +801,28 @@ def move_blocking(Hp, Hc):
         if sum(nb) > Hp:
             nb[-1] = Hp - sum(nb[:-1])
     return nb
+
+
+@dataclasses.dataclass
+class SimResult:
+    """What `BatchLinMPC.sim` returns: the fields of the reference's `SimResult` (src/plot_sim.jl:1-60) with a leading batch
+    axis, each (B,n,N) in engineering units -- X̂_data is the estimate after the correction of its period -- plus `status`
+    (B,N), the controller's status per period, and `path`, the execution path of the run (api.SIM_PATH_PERIOD)."""
+    N: int
+    Y_data: np.ndarray
+    Ry_data: np.ndarray
+    Ŷ_data: np.ndarray
+    U_data: np.ndarray
+    Ud_data: np.ndarray
+    Ru_data: np.ndarray
+    D_data: np.ndarray
+    X_data: np.ndarray
+    X̂_data: np.ndarray
+    status: np.ndarray
+    path: int
+
+    Yhat_data = property(lambda self: self.Ŷ_data)         # the reference's ASCII aliases
+    Xhat_data = property(lambda self: self.X̂_data)
 
 
 class BatchLinMPC:
@@ -1186,6 +1270,29 @@ class BatchLinMPC:
         self.Z[:] = 0.0
         self.lastu0 = np.broadcast_to(np.asarray(u, float), (self.B, self.nu)) - self.uop
 
+    def _prepare_kernel(self):
+        """The kernel the steps of this controller run on, built or loaded once per constraint pattern."""
+        self._ms_kernel = False
+        if self.transcription == "MultipleShooting":
+            self.hd.set_transcription(MULTIPLE_SHOOTING)
+            why = self.hd.transcription_supported()
+            if why:
+                self.hd.set_transcription(SINGLE_SHOOTING)
+                warnings.warn("mpcqp: MultipleShooting kernel not available for this controller (reason mask "
+                              f"{why}: 1 weights that couple stages, 4 LDS): the SingleShooting "
+                              "kernels solve the same problem", RuntimeWarning)
+            else:
+                self._ms_kernel = True
+        self.kernel = KERNEL_MS if self._ms_kernel else self.hd.prepare()
+        if self.kernel == KERNEL_MS and not self._ms_kernel and self.nZ <= 256 and self.hd.lds_bytes() > 160 * 1024:
+            # (ADVICE r5: the reroute used to be silent -- the condensed problem does not fit the LDS of a CU in the
+            #  carve-up of the runtime-dimension kernel; same QP, solved in stage form, an order of magnitude slower)
+            warnings.warn(f"mpcqp: the condensed problem (nZ̃ = {self.nZ}, {self.hd.lds_bytes()} B of LDS) does not fit one "
+                          "compute unit: the SingleShooting controller's steps run on the stage-structured "
+                          "(MultipleShooting) kernel", RuntimeWarning)
+        self._ms_kernel = self.kernel == KERNEL_MS       # (also: nZ̃ > 256, which only the stage-structured kernel takes)
+        self._prepared = True
+
     def moveinput(self, xhat0, ry=None, d=None, *, lastu=None, Dhat=None, Rhaty=None, Rhatu=None,
                   want_info=False):
         """`moveinput!` for the whole batch (src/controller/execute.jl:59-80).
@@ -1198,26 +1305,7 @@ class BatchLinMPC:
         if self.nw > 0 and not held:               # r̂e(k) = ry(k) for the Wr term (execute.jl:351)
             self.hd.set_current_setpoint(ry - self.yop)
         if not self._prepared:                     # like JuMP's model build: before the loop, not in mpcqp_step
-            self._ms_kernel = False
-            if self.transcription == "MultipleShooting":
-                self.hd.set_transcription(MULTIPLE_SHOOTING)
-                why = self.hd.transcription_supported()
-                if why:
-                    self.hd.set_transcription(SINGLE_SHOOTING)
-                    warnings.warn("mpcqp: MultipleShooting kernel not available for this controller (reason mask "
-                                  f"{why}: 1 weights that couple stages, 4 LDS): the SingleShooting "
-                                  "kernels solve the same problem", RuntimeWarning)
-                else:
-                    self._ms_kernel = True
-            self.kernel = KERNEL_MS if self._ms_kernel else self.hd.prepare()
-            if self.kernel == KERNEL_MS and not self._ms_kernel and self.nZ <= 256 and self.hd.lds_bytes() > 160 * 1024:
-                # (the reroute used to be silent -- the condensed problem does not fit the LDS of a CU in the
-                #  carve-up of the runtime-dimension kernel; same QP, solved in stage form, an order of magnitude slower)
-                warnings.warn(f"mpcqp: the condensed problem (nZ̃ = {self.nZ}, {self.hd.lds_bytes()} B of LDS) does not fit one "
-                              "compute unit: the SingleShooting controller's steps run on the stage-structured "
-                              "(MultipleShooting) kernel", RuntimeWarning)
-            self._ms_kernel = self.kernel == KERNEL_MS       # (also: nZ̃ > 256, which only the stage-structured kernel takes)
-            self._prepared = True
+            self._prepare_kernel()
         out = self.hd.step(xhat0, lastu0, (ry - self.yop) if held else (Rhaty - self.Yop), self.Z,
                            Ru=None if Rhatu is None else Rhatu - self.Uop, d0=d0, Dhat0=Dh0,
                            want_Yhat=want_info)
@@ -1236,6 +1324,154 @@ class BatchLinMPC:
         return u0 + self.uop
 
     __call__ = moveinput
+
+    # -- sim!: N closed-loop periods of the whole batch, the plant on the device -------------------------------------------
+    def _sim_prepare(self):
+        if not self._prepared:
+            self._prepare_kernel()
+
+    def _sim_plant(self, plant):
+        """`plant` of `sim`: (A, Bu, C[, Bd, Dd]) or a dict of them with optional uop / yop / dop (which have to be the
+        controller's) and xop / fop (the plant's own).  Sends the plant to the handle; returns nxp and the plant's xop (B,nxp)."""
+        B, nu, ny, nd = self.B, self.nu, self.ny, self.nd
+        if plant is None:
+            raise ValueError("sim needs plant=(A, Bu, C[, Bd, Dd]): the controller holds the augmented model only")
+        if isinstance(plant, dict):
+            p = dict(plant)
+        else:
+            p = dict(zip(("A", "Bu", "C", "Bd", "Dd"), plant))
+        unknown = set(p) - {"A", "Bu", "C", "Bd", "Dd", "uop", "yop", "dop", "xop", "fop"}
+        if unknown or any(k not in p for k in ("A", "Bu", "C")):
+            raise ValueError(f"plant needs A, Bu, C and takes Bd, Dd, uop, yop, dop, xop, fop (got {sorted(p)})")
+
+        def mat(k, rows, cols):
+            a = p.get(k)
+            if a is None:
+                return None
+            a = np.asarray(a, float)
+            if a.ndim == 2:
+                a = np.broadcast_to(a, (B,) + a.shape)
+            if a.shape != (B, rows, cols):
+                raise ValueError(f"plant {k} size must be ({rows}, {cols})")       # DimensionMismatch
+            return a
+        A0 = np.asarray(p["A"], float)
+        if A0.ndim not in (2, 3) or A0.shape[-1] != A0.shape[-2]:
+            raise ValueError("plant A must be square")
+        nxp = A0.shape[-1]
+        A, Bu, Cm = mat("A", nxp, nxp), mat("Bu", nxp, nu), mat("C", ny, nxp)
+        Bd, Dd = mat("Bd", nxp, nd), mat("Dd", ny, nd)
+        if nd == 0:
+            Bd = Dd = None
+        for k, mine in (("uop", self.uop), ("yop", self.yop), ("dop", self.dop)):
+            if p.get(k) is not None and not np.array_equal(np.broadcast_to(np.asarray(p[k], float), mine.shape), mine):
+                raise ValueError(f"the plant's {k} must be the controller's")
+        vec = lambda k: np.zeros((B, nxp)) if p.get(k) is None else np.broadcast_to(np.asarray(p[k], float), (B, nxp)).copy()
+        xop, fop = vec("xop"), vec("fop")
+        fx = fop - xop
+        self.hd.sim_set_plant(colmajor(A), colmajor(Bu), colmajor(Cm), None if Bd is None else colmajor(Bd),
+                              None if Dd is None else colmajor(Dd), fx if np.any(fx != 0) else None)
+        return nxp, xop
+
+    def sim(self, N, ry=None, d=None, ru=None, *, plant=None, u_step=None, u_noise=None, y_step=None, y_noise=None,
+            d_step=None, d_noise=None, x_noise=None, x_0=None, xhat_0=None, lastu=None, seed=None, draws=None, fuse=True):
+        """`sim!(mpc, N, ry, d, ru; plant, u_step, u_noise, y_step, y_noise, d_step, d_noise, x_noise, x_0, x̂_0, lastu)`
+        (src/plot_sim.jl:241-319) for every controller of the batch: N periods of preparestate / moveinput / updatestate
+        around a plant that runs on the device, without a host synchronisation between the periods.  Returns a `SimResult`.
+
+        Arguments are engineering values.  ry (ny,) / (B,ny) is held over the run, (B,ny,N) gives one per period (default
+        yop + 1); d (nd,) / (B,nd) (default dop); ru (nu,) / (B,nu) the input set point, held (default uop).  Steps and noise
+        standard deviations are (n,) / (B,n).  `plant`: see `_sim_plant`; it shares the controller's uop, yop and dop.
+        x_0 (nxp,) / (B,nxp): the plant state; None continues from the end of the previous `sim` (the plant's xop at first).
+        xhat_0: the estimate; None continues from the attached estimator's state (the estimator half of `initstate!` is not
+        run).  lastu: None continues from `self.lastu0`.  Afterwards `self.xhat0`, `self.lastu0`, `self.Z` and `self.status` are
+        those of the last period, so `preparestate` / `moveinput` / `updatestate` can go on from there.
+
+        The noise of period i is σ∘w[:, :, i] with standard-normal draws w: `draws=dict(w_d=…, w_y=…, w_u=…, w_x=…)`, each
+        (B,n,N) with n = nd, ny, nu, nxp, or -- for the channels not given -- `numpy.random.default_rng(seed)` drawing
+        standard_normal((B,n,N)) in the order w_d, w_y, w_u, w_x (all four are drawn, whatever noise is asked for).
+        `fuse=False` keeps the run on the per-period launches; otherwise an explicit-law controller with a steady gain and
+        dimensions up to 16, `ry` held and no `ru`, runs the whole loop in one launch (`SimResult.path`: api.SIM_PATH_FUSED)."""
+        B, nu, ny, nd = self.B, self.nu, self.ny, self.nd
+        N = int(N)
+        if N < 1:
+            raise ValueError("N should be ≥ 1")
+        if not hasattr(self, "i_ym"):
+            raise ValueError("no estimator attached (setestimator)")
+        if not hasattr(self.hd.lib, "mpcqp_sim"):
+            raise NotImplementedError("sim: this library has no mpcqp_sim")
+        nxp, xop = self._sim_plant(plant)
+        flags = 0 if fuse else SIM_FLAG_NO_FUSE
+        ry = self.yop + 1.0 if ry is None else np.asarray(ry, float)
+        if ry.shape == (B, ny, N):
+            flags |= SIM_FLAG_RY_PER_PERIOD
+            Ry_data = ry.copy()
+            ry0 = _f64((ry - self.yop[:, :, None]).transpose(0, 2, 1))
+        else:
+            ry = self._bc(ry, ny, "ry")
+            Ry_data = np.repeat(ry[:, :, None], N, axis=2)
+            ry0 = ry - self.yop
+        d0 = None
+        if nd > 0:
+            d0 = self._bc(self.dop if d is None else d, nd, "d") - self.dop
+        elif d is not None and np.size(d) != 0:
+            raise ValueError("d size must be (0,)")
+        Ru0 = None
+        Ru_data = np.repeat(self.uop[:, :, None], N, axis=2)
+        if ru is not None:
+            ru = self._bc(ru, nu, "ru")
+            Ru_data = np.repeat(ru[:, :, None], N, axis=2)
+            Ru0 = np.tile(ru - self.uop, self.Hp)
+        opt = lambda v, n, name: None if v is None or n == 0 else _f64(self._bc(v, n, name))
+        steps = dict(u_step=opt(u_step, nu, "u_step"), y_step=opt(y_step, ny, "y_step"), d_step=opt(d_step, nd, "d_step"))
+        sig = dict(sigma_u=opt(u_noise, nu, "u_noise"), sigma_y=opt(y_noise, ny, "y_noise"), sigma_d=opt(d_noise, nd, "d_noise"),
+                   sigma_x=opt(x_noise, nxp, "x_noise"))
+        rng = np.random.default_rng(seed)
+        given = dict(draws or {})
+        if set(given) - {"w_d", "w_y", "w_u", "w_x"}:
+            raise ValueError("draws takes w_d, w_y, w_u, w_x")
+        w = {}
+        for k, n in (("w_d", nd), ("w_y", ny), ("w_u", nu), ("w_x", nxp)):
+            drawn = rng.standard_normal((B, n, N))
+            a = drawn if given.get(k) is None else np.asarray(given[k], float)
+            if a.shape != (B, n, N):
+                raise ValueError(f"draws[{k!r}] size must be ({B}, {n}, {N})")
+            w[k] = _f64(a.transpose(0, 2, 1)) if sig["sigma_" + k[2]] is not None else None
+        if x_0 is not None:
+            x0 = _f64(self._bc(x_0, nxp, "x_0") - xop).copy()
+        elif getattr(self, "sim_x0", None) is not None and self.sim_x0.shape == (B, nxp):
+            x0 = self.sim_x0.copy()
+        else:
+            x0 = np.zeros((B, nxp))
+        xh = self.xhat0.copy() if xhat_0 is None else _f64(self._bc(xhat_0, self.nxh, "x̂_0") - self.xhop).copy()
+        lu = _f64(self.lastu0).copy() if lastu is None else _f64(self._bc(lastu, nu, "lastu") - self.uop).copy()
+        self._sim_prepare()
+        # the single-launch path (include/mpcqp.h: MPCQP_SIM_PATH_FUSED) computes u alone: self.Z is NaN after such a run, as
+        # after moveinput(..., want_Z=False)
+        fused = fuse and Ru0 is None and not (flags & SIM_FLAG_RY_PER_PERIOD) and self.hd.sim_path() == SIM_PATH_FUSED
+        Z = None if fused else _f64(self.Z).copy()
+        rec = {k: np.empty((B, N, n)) for k, n in (("Y", ny), ("X", nxp), ("D", nd), ("Xhat", self.nxh), ("Yhat", ny), ("U", nu), ("Ud", nu))}
+        status = np.empty((B, N), np.int32)
+        self.hd.sim(N, flags, ry=ry0, Ru=Ru0, d=d0, **steps, **sig, **w, x0=x0, xhat0=xh, lastu0=lu, Ztilde=Z, status=status,
+                    **{k: (v if v.size else None) for k, v in rec.items()})
+        self.sim_x0, self.xhat0, self.lastu0 = x0, xh, lu
+        self.Z = np.full((B, self.nZ), np.nan) if fused else Z
+        self.status = status[:, -1].copy()
+        self.iters = np.zeros(B, np.int32)
+        nerr, nwarn = int(np.sum(status == STATUS_ERROR)), int(np.sum(status == STATUS_ITERATION_LIMIT))
+        if nerr:      # @error branch, src/controller/execute.jl:484-489: once per run
+            warnings.warn(f"MPC terminated without solution: returning last solution shifted "
+                          f"({nerr} of {B * N} controller periods)", RuntimeWarning)
+        if nwarn:     # @warn branch, :491-496
+            warnings.warn(f"MPC termination status not OPTIMAL: keeping solution anyway "
+                          f"({nwarn} of {B * N} controller periods)", RuntimeWarning)
+        nmiss = int(np.isnan(rec["Y"][:, :, self.i_ym]).any(axis=2).sum())
+        if nmiss:     # kalman.jl:245-251
+            warnings.warn("NaN values in the Kalman filter measurements ym: skipping correction step "
+                          f"({nmiss} of {B * N} estimator periods)", RuntimeWarning)
+        t = lambda k, op: rec[k].transpose(0, 2, 1) + op[:, :, None]
+        return SimResult(N=N, Y_data=t("Y", self.yop), Ry_data=Ry_data, Ŷ_data=t("Yhat", self.yop), U_data=t("U", self.uop),
+                         Ud_data=t("Ud", self.uop), Ru_data=Ru_data, D_data=t("D", self.dop), X_data=t("X", xop),
+                         X̂_data=t("Xhat", self.xhop), status=status, path=SIM_PATH_FUSED if fused else SIM_PATH_PERIOD)
 
     def _period_args(self, xhat0, ry, d, lastu, Dhat, Rhaty, Rhatu):
         """The arguments of `moveinput` checked, broadcast over the batch and turned into what a step takes: x̂0, ry
@@ -1420,6 +1656,9 @@ class BatchExplicitMPC(BatchLinMPC):
 
     def setconstraint(self, **kw):
         raise MpcqpError("ExplicitMPC does not support constraints.")       # explicitmpc.jl:182-184
+
+    def _sim_prepare(self):
+        """`sim` runs the law when it was built and `ru` is None, else the explicit step: no interior-point kernel to prepare."""
 
     def moveinput(self, xhat0, ry=None, d=None, *, lastu=None, Dhat=None, Rhaty=None, Rhatu=None, want_info=False, want_Z=True):
         """`moveinput!` (execute.jl:59-80) on the explicit paths: the law when it was built and no horizon-long argument is

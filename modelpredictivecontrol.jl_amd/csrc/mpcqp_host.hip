@@ -18,6 +18,7 @@
 #include "mpcqp_launch.h"
 #include "ms_bodies.h"
 #include "ms_launch.h"
+#include "sim_launch.h"
 
 using namespace mpcqp;
 
@@ -95,6 +96,15 @@ struct mpcqp_handle_s {
     DBuf ex_Hinv, ex_Lsum, ex_st, ex_law_z, ex_law_u;
     DBuf ex_bx, ex_blu, ex_bry, ex_bd0, ex_bdh, ex_bZ0, ex_bZk, ex_bu0, ex_bst;     // device buffers of the law build
     int ex_waves_z = 0, ex_waves_u = 0;
+    // the plant of the closed-loop simulation (mpcqp_sim_set_plant) and the per-period buffers of mpcqp_sim_device: what the
+    // controller leaves (u0, status, iterations) and what k_sim_plant hands the estimator and the controller (d0, y0m, the set
+    // point of the period, repeat(d0, Hp)); sim_s: staging of the host-pointer call, in the order of mpcqp_sim_io
+    bool have_plant = false;
+    int sim_nxp = 0;
+    DBuf sp_A, sp_Bu, sp_C, sp_Bd, sp_Dd, sp_fx;
+    bool sp_has_Bd = false, sp_has_Dd = false, sp_has_fx = false;
+    DBuf sim_u0, sim_st, sim_it, sim_d0, sim_y0m, sim_ry, sim_dh;
+    DBuf sim_s[26];
 };
 
 static int dev_alloc(mpcqp_handle h, DBuf& b, size_t bytes) {
@@ -1500,6 +1510,224 @@ int mpcqp_kf_correct(mpcqp_handle h, double* xhat0, const double* y0m, const dou
 
 int mpcqp_kf_predict(mpcqp_handle h, double* xhat0, const double* u0, const double* d0) {
     return kf_host(h, xhat0, u0, h ? (size_t)h->d.nu : 0, d0, false);
+}
+
+// ---- sim!: the closed loop of the whole batch, plant included (include/mpcqp.h; kernel: sim_bodies.h) ----------------------
+
+int mpcqp_sim_set_plant(mpcqp_handle h, int32_t nxp, const double* A, const double* Bu, const double* C, const double* Bd,
+                        const double* Dd, const double* fx) {
+    if (!h || !A || !Bu || !C) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    if (nxp < 1) return MPCQP_ERR_ARG;
+    if (nxp > sim::SIM_NMAX || d.nu > sim::SIM_NMAX || d.ny > sim::SIM_NMAX || d.nd > sim::SIM_NMAX || !sim::sim_available())
+        return MPCQP_ERR_UNSUPPORTED;
+    ON_DEVICE(h);
+    const size_t B = d.B, n = nxp, sz = sizeof(double);
+    int rc = upload(h, h->sp_A, A, B * n * n * sz);
+    if (!rc) rc = upload(h, h->sp_Bu, Bu, B * n * d.nu * sz);
+    if (!rc) rc = upload(h, h->sp_C, C, B * d.ny * n * sz);
+    if (!rc && Bd && d.nd > 0) rc = upload(h, h->sp_Bd, Bd, B * n * d.nd * sz);
+    if (!rc && Dd && d.nd > 0) rc = upload(h, h->sp_Dd, Dd, B * d.ny * d.nd * sz);
+    if (!rc && fx) rc = upload(h, h->sp_fx, fx, B * n * sz);
+    if (rc) { h->have_plant = false; return rc; }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->sim_nxp = nxp;
+    h->sp_has_Bd = Bd && d.nd > 0; h->sp_has_Dd = Dd && d.nd > 0; h->sp_has_fx = fx != nullptr;
+    h->have_plant = true;
+    return MPCQP_OK;
+}
+
+static bool explicit_constrained(mpcqp_handle h);
+
+// the handle's side of the fused path's eligibility (include/mpcqp.h); the call's side is sim_fused below
+static bool sim_fused_handle(mpcqp_handle h) {
+    if (!sim::sim_fused_available() || !h->have_plant || !h->have_kf || h->kf_tv) return false;
+    if (!h->have_model || !h->have_weights || !h->ex_prepared || !h->ex_law || explicit_constrained(h)) return false;
+    const Dims& d = h->d;
+    sim::PlantArgs p{};
+    p.nxh = d.nxh; p.nxp = h->sim_nxp; p.nu = d.nu; p.ny = d.ny; p.nd = d.nd; p.nym = h->kf.nym;
+    return sim::fused_dims_ok(p) && sim::fused_lds_doubles(p, ex::law_ncol(d)) * sizeof(double) <= 160 * 1024;
+}
+static bool sim_fused(mpcqp_handle h, const mpcqp_sim_io* io) {
+    return sim_fused_handle(h) && !io->Ru && !(io->flags & (MPCQP_SIM_FLAG_RY_PER_PERIOD | MPCQP_SIM_FLAG_NO_FUSE));
+}
+
+int mpcqp_sim_path(mpcqp_handle h) {
+    if (!h) return MPCQP_ERR_NULL;
+    return sim_fused_handle(h) ? MPCQP_SIM_PATH_FUSED : MPCQP_SIM_PATH_PERIOD;
+}
+
+// which controller call a period of the simulation makes
+enum { SIM_CTRL_NONE = 0, SIM_CTRL_STEP, SIM_CTRL_EXPLICIT_STEP, SIM_CTRL_EXPLICIT_LAW };
+static int sim_controller(mpcqp_handle h, const mpcqp_sim_io* io) {
+    if (!h->have_model || !h->have_weights) return SIM_CTRL_NONE;
+    if (h->ex_prepared) {
+        if (explicit_constrained(h)) return SIM_CTRL_NONE;
+        return (h->ex_law && !io->Ru) ? SIM_CTRL_EXPLICIT_LAW : SIM_CTRL_EXPLICIT_STEP;
+    }
+    return SIM_CTRL_STEP;
+}
+
+// the checks of both entry points, nothing enqueued
+static int sim_check(mpcqp_handle h, const mpcqp_sim_io* io) {
+    if (!h || !io) return MPCQP_ERR_NULL;
+    if (io->N <= 0 || (io->flags & ~(MPCQP_SIM_FLAG_RY_PER_PERIOD | MPCQP_SIM_FLAG_NO_FUSE))) return MPCQP_ERR_ARG;
+    const int ctrl = sim_controller(h, io);
+    if (!h->have_plant || !h->have_kf || ctrl == SIM_CTRL_NONE) return MPCQP_ERR_ORDER;
+    if (!io->ry || !io->x0 || !io->xhat0 || !io->lastu0 || (h->d.nd > 0 && !io->d)) return MPCQP_ERR_NULL;
+    if (!io->Ztilde && ctrl != SIM_CTRL_EXPLICIT_LAW) return MPCQP_ERR_NULL;
+    if ((io->sigma_u && !io->w_u) || (io->sigma_y && !io->w_y) || (io->sigma_x && !io->w_x) ||
+        (h->d.nd > 0 && io->sigma_d && !io->w_d))
+        return MPCQP_ERR_NULL;
+    return MPCQP_OK;
+}
+
+int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io_in, void* stream) {
+    { int rc = sim_check(h, io_in); if (rc) return rc; }
+    const Dims& d = h->d;
+    mpcqp_sim_io io_ = *io_in;
+    if (d.nd == 0) { io_.d = io_.d_step = io_.sigma_d = io_.w_d = nullptr; io_.D = nullptr; }     // (no such channel)
+    const mpcqp_sim_io* io = &io_;
+    ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    const int ctrl = sim_controller(h, io), N = io->N;
+    const bool per_period = io->flags & MPCQP_SIM_FLAG_RY_PER_PERIOD;
+    const bool horizon = ctrl != SIM_CTRL_EXPLICIT_LAW && d.nd > 0;      // the step kernels read D̂0 = repeat(d0, Hp)
+    const size_t B = d.B, sz = sizeof(double);
+    int rc = dev_alloc(h, h->sim_u0, B * d.nu * sz);
+    if (!rc) rc = dev_alloc(h, h->sim_st, B * sizeof(int32_t));
+    if (!rc) rc = dev_alloc(h, h->sim_it, B * sizeof(int32_t));
+    if (!rc) rc = dev_alloc(h, h->sim_y0m, B * (size_t)h->kf.nym * sz);
+    if (!rc && d.nd > 0) rc = dev_alloc(h, h->sim_d0, B * d.nd * sz);
+    if (!rc && per_period) rc = dev_alloc(h, h->sim_ry, B * d.ny * sz);
+    if (!rc && horizon) rc = dev_alloc(h, h->sim_dh, B * d.nD * sz);
+    if (rc) return rc;
+    double* u0 = (double*)h->sim_u0.p;
+    int32_t *cst = (int32_t*)h->sim_st.p, *cit = (int32_t*)h->sim_it.p;
+    double* y0m = (double*)h->sim_y0m.p;
+    double* d0 = d.nd > 0 ? (double*)h->sim_d0.p : nullptr;
+    double* Dh = horizon ? (double*)h->sim_dh.p : nullptr;
+    const double* ry = per_period ? (const double*)h->sim_ry.p : io->ry;
+
+    sim::PlantArgs a{};
+    a.A = (const double*)h->sp_A.p; a.Bu = (const double*)h->sp_Bu.p; a.C = (const double*)h->sp_C.p;
+    a.Bd = h->sp_has_Bd ? (const double*)h->sp_Bd.p : nullptr; a.Dd = h->sp_has_Dd ? (const double*)h->sp_Dd.p : nullptr;
+    a.fx = h->sp_has_fx ? (const double*)h->sp_fx.p : nullptr;
+    a.Chat = h->m.C; a.Dhd = d.nd > 0 ? h->m.Dd : nullptr; a.i_ym = h->kf.i_ym;
+    a.B = d.B; a.nxp = h->sim_nxp; a.nu = d.nu; a.ny = d.ny; a.nd = d.nd; a.nym = h->kf.nym; a.nxh = d.nxh; a.Hp = d.Hp; a.N = N;
+    a.G = sim::group_lanes(a.nxp, a.nu, a.ny, a.nd, a.nym);
+    a.ry = io->ry; a.d = io->d; a.ry_per_period = per_period ? 1 : 0;
+    a.u_step = io->u_step; a.y_step = io->y_step; a.d_step = io->d_step;
+    a.su = io->sigma_u; a.sy = io->sigma_y; a.sd = io->sigma_d; a.sx = io->sigma_x;
+    a.wu = io->w_u; a.wy = io->w_y; a.wd = io->w_d; a.wx = io->w_x;
+    a.x = io->x0; a.xhat = io->xhat0; a.lastu0 = io->lastu0; a.u0 = u0; a.st = cst;
+    a.d0 = d0; a.y0m = y0m; a.ry_cur = per_period ? (double*)h->sim_ry.p : nullptr; a.Dhat0 = Dh;
+    a.Y = io->Y; a.X = io->X; a.D = io->D; a.Xhat = io->Xhat; a.Yhat = io->Yhat; a.U = io->U; a.Ud = io->Ud; a.status = io->status;
+    if (sim_fused(h, io)) {         // the whole loop in one launch (k_sim_explicit); Z̃ is not computed on this path
+        { int rc2 = explicit_current(h, st); if (rc2) return rc2; }
+        sim::FusedArgs f{};
+        f.p = a;
+        f.p.i_est = f.p.i_tail = f.p.i_head = -1;
+        f.Ahat = h->m.Ahat; f.Bhu = h->m.Bu; f.Bhd = d.nd > 0 ? h->m.Bd : nullptr; f.dop = h->m.dop;
+        f.Khat = h->kf.Khat; f.law = (const double*)h->ex_law_u.p; f.fstatus = (const int32_t*)h->ex_st.p;
+        f.kp = ex::law_kp(d); f.ncol = ex::law_ncol(d); f.direct = h->kf_direct;
+        HIPCHK(hipEventRecord(h->ev_s0, st));
+        HIPCHK(sim::launch_sim_explicit(f, st));
+        HIPCHK(hipEventRecord(h->ev_s1, st));
+        h->step_timed = true;
+        return MPCQP_OK;
+    }
+    auto plant = [&](int i_est, int i_tail, int i_head) {
+        sim::PlantArgs p = a;
+        p.i_est = i_est; p.i_tail = i_tail; p.i_head = i_head;
+        return sim::launch_sim_plant(p, st);
+    };
+
+    // the step reads the set point of the period as (ny,B), whatever the handle's flag says about the caller's own steps
+    // (and r̂e(k) of the custom rows is that set point: no mpcqp_set_current_setpoint of an earlier period)
+    struct FlagGuard {
+        mpcqp_handle h; uint32_t keep; const double* ry_now;
+        ~FlagGuard() { h->d.flags = keep; h->m.ry_now = ry_now; }
+    } flag_guard{h, d.flags, h->m.ry_now};
+    h->d.flags |= MPCQP_FLAG_RY_CONSTANT;
+    h->m.ry_now = nullptr;
+
+    HIPCHK(plant(-1, -1, 0));
+    for (int i = 0; i < N; ++i) {
+        if (h->kf_direct) { rc = mpcqp_kf_correct_device(h, io->xhat0, y0m, d0, stream); if (rc) return rc; }
+        if (io->Xhat || io->Yhat) HIPCHK(plant(i, -1, -1));
+        switch (ctrl) {
+            case SIM_CTRL_EXPLICIT_LAW:
+                rc = mpcqp_explicit_law_device(h, io->xhat0, io->lastu0, ry, d0, io->Ztilde, u0, cst, stream);
+                break;
+            case SIM_CTRL_EXPLICIT_STEP:
+                rc = mpcqp_explicit_step_device(h, io->xhat0, io->lastu0, ry, io->Ru, d0, Dh, io->Ztilde, u0, cst, nullptr, stream);
+                break;
+            default:
+                rc = mpcqp_step_device(h, io->xhat0, io->lastu0, ry, io->Ru, d0, Dh, io->Ztilde, u0, cst, cit, nullptr, stream);
+        }
+        if (rc) return rc;
+        rc = h->kf_direct ? mpcqp_kf_predict_device(h, io->xhat0, u0, d0, stream)
+                          : mpcqp_kf_update_device(h, io->xhat0, u0, y0m, d0, stream);
+        if (rc) return rc;
+        HIPCHK(plant(-1, i, i + 1 < N ? i + 1 : -1));
+    }
+    return MPCQP_OK;
+}
+
+int mpcqp_sim(mpcqp_handle h, const mpcqp_sim_io* io) {
+    { int rc = sim_check(h, io); if (rc) return rc; }
+    const Dims& d = h->d;
+    ON_DEVICE(h);
+    const size_t B = d.B, N = (size_t)io->N, sz = sizeof(double), nxp = (size_t)h->sim_nxp;
+    const size_t nry = (io->flags & MPCQP_SIM_FLAG_RY_PER_PERIOD) ? N * d.ny : (size_t)d.ny;
+    mpcqp_sim_io dv = *io;
+    int rc = MPCQP_OK, k = 0;
+    // inputs and the in/out state go up, records are allocated; every array has its own staging buffer
+    auto in = [&](const double*& p, size_t n) {
+        DBuf& b = h->sim_s[k++];
+        if (!p || rc) return;
+        rc = upload(h, b, p, B * n * sz);
+        p = (const double*)b.p;
+    };
+    auto io_ = [&](double*& p, size_t n, bool up) {
+        DBuf& b = h->sim_s[k++];
+        if (!p || rc) return;
+        rc = up ? upload(h, b, p, B * n * sz) : dev_alloc(h, b, B * n * sz);
+        p = (double*)b.p;
+    };
+    in(dv.ry, nry); in(dv.Ru, d.nU); in(dv.d, d.nd);
+    in(dv.u_step, d.nu); in(dv.y_step, d.ny); in(dv.d_step, d.nd);
+    in(dv.sigma_u, d.nu); in(dv.sigma_y, d.ny); in(dv.sigma_d, d.nd); in(dv.sigma_x, nxp);
+    in(dv.w_u, N * d.nu); in(dv.w_y, N * d.ny); in(dv.w_d, N * d.nd); in(dv.w_x, N * nxp);
+    io_(dv.x0, nxp, true); io_(dv.xhat0, d.nxh, true); io_(dv.lastu0, d.nu, true); io_(dv.Ztilde, d.nZ, true);
+    io_(dv.Y, N * d.ny, false); io_(dv.X, N * nxp, false); io_(dv.D, N * d.nd, false); io_(dv.Xhat, N * d.nxh, false);
+    io_(dv.Yhat, N * d.ny, false); io_(dv.U, N * d.nu, false); io_(dv.Ud, N * d.nu, false);
+    if (!rc && io->status) {
+        rc = dev_alloc(h, h->sim_s[k], B * N * sizeof(int32_t));
+        dv.status = (int32_t*)h->sim_s[k].p;
+    }
+    if (rc) return rc;
+    if (d.nd == 0) dv.d = dv.d_step = dv.sigma_d = dv.w_d = nullptr, dv.D = nullptr;
+    rc = mpcqp_sim_device(h, &dv, h->stream);
+    if (rc) return rc;
+    auto down = [&](void* host, const void* dev, size_t bytes) {
+        return (host && dev) ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+    };
+    HIPCHK(down(io->x0, dv.x0, B * nxp * sz));
+    HIPCHK(down(io->xhat0, dv.xhat0, B * d.nxh * sz));
+    HIPCHK(down(io->lastu0, dv.lastu0, B * d.nu * sz));
+    HIPCHK(down(io->Ztilde, dv.Ztilde, B * d.nZ * sz));
+    HIPCHK(down(io->Y, dv.Y, B * N * d.ny * sz));
+    HIPCHK(down(io->X, dv.X, B * N * nxp * sz));
+    HIPCHK(down(io->D, dv.D, B * N * d.nd * sz));
+    HIPCHK(down(io->Xhat, dv.Xhat, B * N * d.nxh * sz));
+    HIPCHK(down(io->Yhat, dv.Yhat, B * N * d.ny * sz));
+    HIPCHK(down(io->U, dv.U, B * N * d.nu * sz));
+    HIPCHK(down(io->Ud, dv.Ud, B * N * d.nu * sz));
+    HIPCHK(down(io->status, dv.status, B * N * sizeof(int32_t)));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
 }
 
 static thread_local std::string g_build_err;
