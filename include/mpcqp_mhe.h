@@ -119,6 +119,16 @@ int mpcqp_mhe_update(mpcqp_mhe h, const double* u0, const double* y0m, const dou
 int mpcqp_mhe_prepare_device(mpcqp_mhe h, const double* y0m_dev, const double* d0_dev);
 int mpcqp_mhe_update_device(mpcqp_mhe h, const double* u0_dev, const double* y0m_dev, const double* d0_dev);
 int mpcqp_mhe_sync(mpcqp_mhe h);
+/* The same two calls on a stream of the caller's (NULL: the default stream): every launch of the period -- the solve, the
+ * arrival-covariance launches, the copy lastu0 <- u0 -- goes on `stream`, behind the work queued so far on the handle's own
+ * stream (an event recorded there, waited for on `stream`); what the handle's own stream does afterwards (mpcqp_mhe_get, a
+ * setter) waits for the period in the same way.  mpcqp_mhe_prepare_device / mpcqp_mhe_update_device are these calls on the
+ * handle's own stream.  mpcqp_mhe_set_state_stream: x̂0 <- xhat0_dev (nx̂,B), a device-to-device copy on `stream`. */
+int mpcqp_mhe_prepare_stream(mpcqp_mhe h, const double* y0m_dev, const double* d0_dev, void* stream);
+int mpcqp_mhe_update_stream(mpcqp_mhe h, const double* u0_dev, const double* y0m_dev, const double* d0_dev, void* stream);
+int mpcqp_mhe_set_state_stream(mpcqp_mhe h, const double* xhat0_dev, void* stream);
+/* the dimensions the handle was created with (tolerances and limits: the values in force) */
+int mpcqp_mhe_get_dims(mpcqp_mhe h, mpcqp_mhe_dims* out);
 
 #define MPCQP_MHE_XHAT0    0   /* (nx̂,B)          current estimate x̂0                                  */
 #define MPCQP_MHE_ZTILDE   1   /* (nx̂+He nx̂,B)    [x̂0arr; Ŵ] of the last solve (zero beyond Nk)          */
@@ -136,6 +146,39 @@ double mpcqp_mhe_last_ms(mpcqp_mhe h);          /* device time of the last solve
 int mpcqp_mhe_register_columns(mpcqp_mhe h);    /* NX: register columns of the kernel that runs: max(nx̂, nym) rounded up
                                                  * to a multiple of 4 (<= 16) or, above 16, of 8 (24, 32)            */
 int mpcqp_mhe_lanes_per_estimator(mpcqp_mhe h); /* 16: one estimator per DPP row; 64: one per wavefront (NX > 16)   */
+
+/* LinMPC(MovingHorizonEstimator(...)): the estimator `e` behind the controller `h` (docs/src/manual/linmpc.md, "Moving Horizon
+ * Estimator").  `e` is BORROWED: it must outlive its use by `h` (detach with e = NULL, or attach another estimator, before
+ * destroying it).  i_ym (nym): the rows of the controller's Ĉ / D̂d that `e` measures.  MPCQP_ERR_DIMS when batch, nx̂, nu, nd,
+ * nym or the device of the two handles disagree; MPCQP_ERR_ARG for an index outside 0 .. ny-1 or a repeated one.  Replaces an
+ * attached Kalman filter; mpcqp_kf_set / mpcqp_kf_set_covariances / mpcqp_kf_set_steady afterwards detach `e`.  The form
+ * (direct or predictor) is e's own.  Afterwards
+ *   mpcqp_loop_device   runs mpcqp_mhe_prepare_stream(y0m, d0), the step on e's x̂0 read in place (same (nx̂,B) layout: no copy),
+ *                       mpcqp_mhe_update_stream(u0, y0m, d0), all on the caller's stream; the caller's xhat0 receives the
+ *                       estimate the step used;
+ *   mpcqp_sim[_device]  drive `e` in every period (per-period path only: mpcqp_sim_path answers MPCQP_SIM_PATH_PERIOD);
+ *                       io->xhat0 seeds e's x̂0 at the start (mpcqp_mhe_set_state: x̂0 and nothing else) and receives the
+ *                       last estimate; a NaN in y0m is NOT a missed measurement here (a Kalman-filter feature of the
+ *                       reference, kalman.jl:245-251): it reaches the estimator unchanged.  e's status array of every
+ *                       period is kept on the device: mpcqp_sim_est_status. */
+int mpcqp_mhe_attach(mpcqp_handle h, mpcqp_mhe e, const int32_t* i_ym, int32_t nym);
+/* (N,B) int32, period-major: e's MPCQP_MHE_STATUS after each of the first N periods of the last mpcqp_sim[_device] on `h`
+ * (MPCQP_ERR_ORDER: no such run; MPCQP_ERR_ARG: it had fewer periods).  Synchronises the device. */
+int mpcqp_sim_est_status(mpcqp_handle h, int32_t* out, int32_t N);
+
+/* The estimator half of initstate! (init_estimate!, src/estimator/execute.jl:246-259) for the estimator attached to `h` --
+ * a Kalman filter of any kind or a MovingHorizonEstimator -- on the model resident in `h`: every member solves
+ *   [I - Â; Ĉm] x̂0 = [B̂u u0 + B̂d d0 + f̂op - x̂op; y0m - D̂dm d0]
+ * in the least-squares sense (Householder QR on the device, one member per wavefront).  xhat0 (nx̂,B) in/out, u0 (nu,B),
+ * y0m (nym,B), d0 (nd,B; NULL iff nd = 0), status (B): 0 solved; 1 the matrix has no full column rank -- a diagonal entry of R
+ * below 64 eps max|R_jj|, e.g. an integrating plant with an integrator on the same channel: that member's x̂0 is left
+ * UNTOUCHED (the reference returns LAPACK's minimum-norm solution there; this library does not pivot and refuses instead),
+ * its neighbours are not affected.  The covariance half (init_estimate_cov!) is the caller's: mpcqp_kf_set_state_covariance,
+ * mpcqp_mhe_init.  MPCQP_ERR_ORDER without an estimator or a model, MPCQP_ERR_UNSUPPORTED for max(nx̂, nym) > 32.
+ * _device: device pointers, asynchronous on `stream`. */
+int mpcqp_est_initstate(mpcqp_handle h, double* xhat0, const double* u0, const double* y0m, const double* d0, int32_t* status);
+int mpcqp_est_initstate_device(mpcqp_handle h, double* xhat0, const double* u0, const double* y0m, const double* d0,
+                               int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -219,6 +219,11 @@ def load_library(path: str | None = None):
         lib.mpcqp_sim.argtypes = [C.c_void_p, C.POINTER(SimIO)]
         lib.mpcqp_sim_device.argtypes = [C.c_void_p, C.POINTER(SimIO), C.c_void_p]
         lib.mpcqp_sim_path.argtypes = [C.c_void_p]
+    if hasattr(lib, "mpcqp_mhe_attach"):           # (include/mpcqp_mhe.h: the entry points that take a controller handle)
+        lib.mpcqp_mhe_attach.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        lib.mpcqp_sim_est_status.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        lib.mpcqp_est_initstate.argtypes = [C.c_void_p] * 6
+        lib.mpcqp_est_initstate_device.argtypes = [C.c_void_p] * 7
     lib.mpcqp_prepare.argtypes = [C.c_void_p]
     lib.mpcqp_kernel_kind.argtypes = [C.c_void_p]
     lib.mpcqp_lds_bytes.argtypes = [C.c_void_p]
@@ -555,6 +560,40 @@ class Handle:
     def recondense_device(self, stream=0):
         _chk(self.lib, self.lib.mpcqp_recondense_device(self.h, C.c_void_p(int(stream)) if stream else None))
 
+    # -- LinMPC(MovingHorizonEstimator) and the estimator half of initstate! (include/mpcqp_mhe.h) ------------
+    def mhe_attach(self, est, i_ym=None):
+        """mpcqp_mhe_attach: `est` an `mhe.MheHandle` (borrowed: this object keeps a reference) or None to detach; i_ym the
+        measured rows of Ĉ."""
+        if not hasattr(self.lib, "mpcqp_mhe_attach"):
+            raise NotImplementedError("this library has no mpcqp_mhe_attach")
+        if est is None:
+            _chk(self.lib, self.lib.mpcqp_mhe_attach(self.h, None, None, 0))
+            self._mhe = None
+            return
+        iy = np.ascontiguousarray(i_ym, dtype=np.int32)
+        _chk(self.lib, self.lib.mpcqp_mhe_attach(self.h, est._h, _ptr(iy), int(iy.size)))
+        self._mhe, self.nym = est, int(iy.size)
+
+    def sim_est_status(self, N):
+        """(N,B) int32: the attached estimator's status after every period of the last `sim` / `sim_device`."""
+        out = np.empty((int(N), self.B), np.int32)
+        _chk(self.lib, self.lib.mpcqp_sim_est_status(self.h, _ptr(out), int(N)))
+        return out
+
+    def est_initstate(self, xhat0, u0, y0m, d0=None):
+        """mpcqp_est_initstate: x̂0 (B,nx̂) float64, written in place for the members that solve; returns status (B,)."""
+        assert xhat0.dtype == np.float64 and xhat0.flags.c_contiguous
+        if not hasattr(self.lib, "mpcqp_est_initstate"):
+            raise NotImplementedError("this library has no mpcqp_est_initstate")
+        u, y, dd = _f64(u0), _f64(y0m), (None if d0 is None else _f64(d0))
+        st = np.empty(self.B, np.int32)
+        _chk(self.lib, self.lib.mpcqp_est_initstate(self.h, _ptr(xhat0), _ptr(u), _ptr(y), _ptr(dd), _ptr(st)))
+        return st
+
+    def est_initstate_device(self, xhat0, u0, y0m, status, d0=0, stream=0):
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _chk(self.lib, self.lib.mpcqp_est_initstate_device(self.h, v(xhat0), v(u0), v(y0m), v(d0), v(status), v(stream)))
+
     def get(self, which):
         shape = {GET_HESSIAN: (self.B, self.nZ, self.nZ), GET_STEPRESP: (self.B, self.Hp, self.nu, self.ny),
                  GET_KMAT: (self.B, self.nxhat, self.nY), GET_BVEC: (self.B, self.nY),
@@ -807,7 +846,8 @@ def move_blocking(Hp, Hc):
 class SimResult:
     """What `BatchLinMPC.sim` returns: the fields of the reference's `SimResult` (src/plot_sim.jl:1-60) with a leading batch
     axis, each (B,n,N) in engineering units -- X̂_data is the estimate after the correction of its period -- plus `status`
-    (B,N), the controller's status per period, and `path`, the execution path of the run (api.SIM_PATH_PERIOD)."""
+    (B,N), the controller's status per period, `path`, the execution path of the run (api.SIM_PATH_PERIOD), and, with a
+    MovingHorizonEstimator attached, `est_status` (B,N), the estimator's status per period (None otherwise)."""
     N: int
     Y_data: np.ndarray
     Ry_data: np.ndarray
@@ -820,6 +860,7 @@ class SimResult:
     X̂_data: np.ndarray
     status: np.ndarray
     path: int
+    est_status: np.ndarray = None
 
     Yhat_data = property(lambda self: self.Ŷ_data)         # the reference's ASCII aliases
     Xhat_data = property(lambda self: self.X̂_data)
@@ -935,6 +976,11 @@ class BatchLinMPC:
         if getattr(self, "kf_steady", False):      # SteadyKalmanFilter from Q̂ and R̂: the gain follows the model
             self.hd.kf_solve_steady()
             self._warn_steady()
+        est = getattr(self, "mhe", None)
+        if est is not None:                        # the attached MovingHorizonEstimator: the measured rows of Ĉ and D̂d
+            ops = self.__dict__.pop("_mhe_ops", {})
+            est.setmodel(self._Ahat, self._Bhu, self._Chat[:, self.i_ym], self._Bhd,
+                         None if self.nd == 0 else self._Dhd[:, self.i_ym], **ops)
 
     def setweights(self, Mwt=None, Nwt=None, Lwt=None, M_Hp=None, N_Hc=None, L_Hp=None):
         """Defaults of src/general.jl:3-6 (Mwt=1, Nwt=0.1, Lwt=0).  `M_Hp` (nY,nY), `N_Hc` (nΔU,nΔU), `L_Hp`
@@ -1116,7 +1162,50 @@ class BatchLinMPC:
         return self
 
     # -- estimator steps on both sides of moveinput! (SteadyKalmanFilter) ---------------------
-    def setestimator(self, Khat=None, i_ym=None, xhat0=None, *, covariances=None, steady=None, direct=True):
+    @property
+    def xhat0(self):
+        """The attached estimator's x̂0 (deviation, (B,nx̂)): this object's own array behind a Kalman filter, a mirror of
+        `mhe.x̂0` behind a MovingHorizonEstimator (assigning it is `setstate!`: x̂0 and nothing else)."""
+        est = self.__dict__.get("mhe")
+        if est is not None:
+            return est.x̂0
+        if "_xhat0" not in self.__dict__:
+            raise AttributeError("xhat0")
+        return self.__dict__["_xhat0"]
+
+    @xhat0.setter
+    def xhat0(self, v):
+        est = self.__dict__.get("mhe")
+        if est is not None:
+            est.x̂0 = _f64(v).copy()
+            est.handle.set_state(est.x̂0)
+        else:
+            self.__dict__["_xhat0"] = v
+
+    def _attach_mhe(self, est, i_ym, direct):
+        from .mhe import BatchMHE
+        if not isinstance(est, BatchMHE):
+            raise ValueError("mhe must be a BatchMHE")
+        if est.handle.lib is not self.hd.lib:
+            raise ValueError("the estimator and the controller were created on different libraries")
+        i_ym = np.arange(self.ny) if i_ym is None else np.asarray(i_ym, int)
+        if (est.B, est.nx̂, est.nu, est.nd, est.nym) != (self.B, self.nxh, self.nu, self.nd, len(i_ym)):
+            raise ValueError(f"DimensionMismatch: the estimator's (B, nx̂, nu, nd, nym) = {(est.B, est.nx̂, est.nu, est.nd, est.nym)}, "
+                             f"the controller's {(self.B, self.nxh, self.nu, self.nd, len(i_ym))}")
+        if len(i_ym) < 1 or i_ym.min() < 0 or i_ym.max() >= self.ny or len(set(i_ym.tolist())) != len(i_ym):
+            raise ValueError("i_ym: unique indices of measured outputs in 0 .. ny-1")
+        if direct is not None and bool(direct) != est.direct:
+            raise ValueError(f"direct={direct} contradicts the estimator's direct={est.direct}: the form is the estimator's own")
+        for name, mine, its in (("uop", self.uop, est.uop), ("yop[i_ym]", self.yop[:, i_ym], est.yop_m), ("dop", self.dop, est.dop),
+                                ("x̂op", self.xhop, est.x̂op), ("f̂op", self.fhop, est.f̂op)):
+            if not np.array_equal(mine, its):
+                raise ValueError(f"the estimator's {name} must be the controller's")
+        self.hd.mhe_attach(est.handle, i_ym)
+        self.i_ym, self.mhe, self.direct = i_ym, est, est.direct
+        self.kf_timevarying = self.kf_steady = False
+        return self
+
+    def setestimator(self, Khat=None, i_ym=None, xhat0=None, *, covariances=None, steady=None, direct=None, mhe=None):
         """Attach a SteadyKalmanFilter: Khat (B,nx̂,nym) steady-state gain (see
         `steady_kalman_gain`), i_ym measured-output indices (default all).  The estimate x̂0
         (deviation, (B,nx̂)) is then carried by this object like `mpc.estim.x̂0`.
@@ -1137,15 +1226,28 @@ class BatchLinMPC:
         `steady_kalman_gain` returns): the library applies x̂ <- Â (x̂ + K̂ v) + ... like `update_estimate!`.
 
         In both forms a member whose `ym` row holds a NaN, or every member when `ym` is None, skips the correction of that
-        period (RuntimeWarning with the count); its prediction runs."""
-        if (Khat is not None) + (covariances is not None) + (steady is not None) > 1:
-            raise ValueError("give one of Khat (SteadyKalmanFilter), steady (SteadyKalmanFilter from Q̂ and R̂) or covariances (KalmanFilter)")
+        period (RuntimeWarning with the count); its prediction runs.
+
+        `mhe=est` puts a `BatchMHE` behind the controller, `LinMPC(MovingHorizonEstimator(...))` of the manual: same batch, nx̂,
+        nu, nd, library and operating points (uop, yop[i_ym], dop, x̂op), nym = len(i_ym); the form is `est.direct` (a `direct=`
+        that contradicts it is an error).  `est` is borrowed and shared: `preparestate`, `updatestate`, `setstate` and
+        `setmodel` (the rows i_ym of Ĉ and D̂d) forward to it, `mpc.xhat0` is `est.x̂0`, `moveinput(None, …)` reads it,
+        `getinfo()["estim"]` is `est.getinfo()`, and `sim` / `hd.loop_device` run it on the device without a copy of x̂0."""
+        if (Khat is not None) + (covariances is not None) + (steady is not None) + (mhe is not None) > 1:
+            raise ValueError("give one of Khat (SteadyKalmanFilter), steady (SteadyKalmanFilter from Q̂ and R̂), covariances (KalmanFilter) "
+                             "or mhe (MovingHorizonEstimator)")
+        if mhe is not None:
+            if xhat0 is not None:
+                raise ValueError("xhat0: the estimate is the MovingHorizonEstimator's own (est.setstate)")
+            return self._attach_mhe(mhe, i_ym, direct)
+        direct = True if direct is None else direct
         if covariances is not None:
             return self.setkalmanfilter(**covariances, i_ym=i_ym, xhat0=xhat0, direct=direct)
         if steady is not None:
             return self.setsteadykalmanfilter(**steady, i_ym=i_ym, xhat0=xhat0, direct=direct)
         if Khat is None:
-            raise ValueError("setestimator needs Khat, steady or covariances")
+            raise ValueError("setestimator needs Khat, steady, covariances or mhe")
+        self.__dict__.pop("mhe", None)              # (mpcqp_kf_set detaches a MovingHorizonEstimator)
         self.kf_timevarying = self.kf_steady = False
         self.i_ym = np.arange(self.ny) if i_ym is None else np.asarray(i_ym, int)
         Khat = np.asarray(Khat, float)
@@ -1185,6 +1287,8 @@ class BatchLinMPC:
         Qhat, Rhat, P0 = self._cov(Qhat, self.nxh, "Q̂"), self._cov(Rhat, nym, "R̂"), self._cov(P0, self.nxh, "P̂_0")
         self._set_direct(direct)
         self.hd.kf_set_covariances(Qhat, Rhat, P0, self.i_ym)
+        self.__dict__.pop("mhe", None)
+        self._P0 = P0.copy()                        # P̂_0, for initstate (init_estimate_cov!)
         self.kf_timevarying, self.kf_steady = True, False
         self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
         return self
@@ -1197,6 +1301,7 @@ class BatchLinMPC:
         Qhat, Rhat = self._cov(Qhat, self.nxh, "Q̂"), self._cov(Rhat, len(self.i_ym), "R̂")
         self._set_direct(direct)
         self.hd.kf_set_steady(Qhat, Rhat, self.i_ym)
+        self.__dict__.pop("mhe", None)
         self.kf_timevarying, self.kf_steady = False, True
         self._warn_steady()
         self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
@@ -1225,6 +1330,9 @@ class BatchLinMPC:
         time-varying KalmanFilter."""
         if not hasattr(self, "i_ym"):
             raise ValueError("no estimator attached (setestimator)")
+        if getattr(self, "mhe", None) is not None:      # (a covariance raises there, as in the reference)
+            self.mhe.setstate(self._bc(xhat, self.nxh, "x̂"), Phat)
+            return self
         if Phat is not None:
             if not getattr(self, "kf_timevarying", False):
                 raise ValueError("the SteadyKalmanFilter has no covariance estimate P̂ to set")
@@ -1245,6 +1353,8 @@ class BatchLinMPC:
         """`preparestate!` (src/estimator/execute.jl:334-345 -> correct_estimate_obsv!,
         kalman.jl:284-295): x̂0 += K̂ (y0m - Ĉm x̂0 - D̂dm d0).  Returns x̂ = x̂0 + x̂op.  Members with a NaN in `ym` (all of
         them with ym=None) keep their x̂0.  Predictor form (direct=False): nothing to do, no device call."""
+        if getattr(self, "mhe", None) is not None:      # preparestate!(estim::MovingHorizonEstimator): one solve (direct form)
+            return self._mhe_period(self.mhe.preparestate(ym, d), self.direct)
         if not getattr(self, "direct", True):
             return self.xhat0 + self.xhop
         y0m = self._y0m(ym)
@@ -1256,6 +1366,10 @@ class BatchLinMPC:
         """`updatestate!` (src/estimator/execute.jl:374-386 -> predict_estimate_obsv!,
         kalman.jl:298-309): x̂0 <- Â x̂0 + B̂u u0 + B̂d d0 + f̂op - x̂op.  Predictor form (direct=False): the correction with
         `ym` first (kalman.jl:276-281, 520-525; ym=None or NaN rows: skipped), then the prediction."""
+        if getattr(self, "mhe", None) is not None:
+            if ym is None:
+                raise ValueError("updatestate: the MovingHorizonEstimator needs ym")
+            return self._mhe_period(self.mhe.updatestate(u, ym, d), not self.direct)
         u0 = self._bc(u, self.nu, "u") - self.uop
         d0 = None if self.nd == 0 else self._bc(d, self.nd, "d") - self.dop
         if getattr(self, "direct", True):
@@ -1264,11 +1378,54 @@ class BatchLinMPC:
             self.hd.kf_update(self.xhat0, u0, self._y0m(ym), d0)
         return self.xhat0 + self.xhop
 
+    def _mhe_period(self, xhat, solved):
+        """One warning for the members whose MovingHorizonEstimator solve of this call failed (mhe/execute.jl:596-606)."""
+        if solved:
+            self._warn_mhe(self.mhe.status, self.B, "estimators")
+        return xhat
+
+    @staticmethod
+    def _warn_mhe(status, total, what):
+        nerr, nwarn = int(np.sum(status == 2)), int(np.sum(status == 1))
+        if nerr:      # @error branch, src/estimator/mhe/execute.jl:596-600
+            warnings.warn(f"MHE terminated without solution: estimation in open-loop ({nerr} of {total} {what})", RuntimeWarning)
+        if nwarn:     # @warn branch, :602-606
+            warnings.warn("MHE termination status not OPTIMAL or LOCALLY_SOLVED: keeping solution anyway "
+                          f"({nwarn} of {total} {what})", RuntimeWarning)
+
     # -- per-step ---------------------------------------------------------------------------
-    def initstate(self, u):
-        """controller part of `initstate!` (src/controller/execute.jl:9-13)."""
+    def initstate(self, u, ym=None, d=None):
+        """`initstate!(mpc, u, ym, d)` (src/controller/execute.jl:9-13).  With `ym=None` the controller part only: Z̃ = 0,
+        lastu0 = u - uop.  With `ym` (nym,) / (B,nym) also the estimator half (src/estimator/execute.jl:208-259): every member's
+        x̂0 becomes the least-squares solution of  [I - Â; Ĉm] x̂0 = [B̂u u0 + B̂d d0 + f̂op - x̂op; y0m - D̂dm d0]  -- the steady
+        state with ŷm = ym, a bumpless transfer -- solved on the device (QR, one member per wavefront), then
+        `init_estimate_cov!`: P̂ <- P̂_0 on a time-varying KalmanFilter, `est.initstate(x̂, u, d)` on a MovingHorizonEstimator
+        (windows emptied, P̄ <- P̂_0), nothing on a steady filter.  Members whose matrix has no full column rank (an integrating
+        plant with an integrator on the same channel) keep their x̂0 -- the reference returns the minimum-norm solution there --
+        and are counted in one RuntimeWarning.  Returns x̂ (B,nx̂) when `ym` is given."""
         self.Z[:] = 0.0
         self.lastu0 = np.broadcast_to(np.asarray(u, float), (self.B, self.nu)) - self.uop
+        if ym is None:
+            return None
+        if not hasattr(self, "i_ym"):
+            raise ValueError("no estimator attached (setestimator)")
+        y0m = self._bc(ym, len(self.i_ym), "ym") - self.yop[:, self.i_ym]
+        d0 = None if self.nd == 0 else self._bc(d, self.nd, "d") - self.dop
+        xh = _f64(self.xhat0).copy()
+        st = self.hd.est_initstate(xh, self.lastu0, y0m, d0)
+        est = getattr(self, "mhe", None)
+        if est is not None:
+            est.initstate(xh + self.xhop, self.lastu0 + self.uop, None if self.nd == 0 else d0 + self.dop)
+        else:
+            self.xhat0 = xh
+            if getattr(self, "kf_timevarying", False):
+                self.hd.kf_set_state_covariance(self._P0)
+        self.init_status = st
+        n = int(np.count_nonzero(st))
+        if n:
+            warnings.warn("initstate!: [I - Â; Ĉm] has no full column rank, the estimate x̂0 is left unchanged "
+                          f"({n} of {self.B} estimators)", RuntimeWarning)
+        return self.xhat0 + self.xhop
 
     def _prepare_kernel(self):
         """The kernel the steps of this controller run on, built or loaded once per constraint pattern."""
@@ -1373,7 +1530,8 @@ class BatchLinMPC:
         return nxp, xop
 
     def sim(self, N, ry=None, d=None, ru=None, *, plant=None, u_step=None, u_noise=None, y_step=None, y_noise=None,
-            d_step=None, d_noise=None, x_noise=None, x_0=None, xhat_0=None, lastu=None, seed=None, draws=None, fuse=True):
+            d_step=None, d_noise=None, x_noise=None, x_0=None, xhat_0=None, lastu=None, seed=None, draws=None, fuse=True,
+            initstate=False):
         """`sim!(mpc, N, ry, d, ru; plant, u_step, u_noise, y_step, y_noise, d_step, d_noise, x_noise, x_0, x̂_0, lastu)`
         (src/plot_sim.jl:241-319) for every controller of the batch: N periods of preparestate / moveinput / updatestate
         around a plant that runs on the device, without a host synchronisation between the periods.  Returns a `SimResult`.
@@ -1382,8 +1540,13 @@ class BatchLinMPC:
         yop + 1); d (nd,) / (B,nd) (default dop); ru (nu,) / (B,nu) the input set point, held (default uop).  Steps and noise
         standard deviations are (n,) / (B,n).  `plant`: see `_sim_plant`; it shares the controller's uop, yop and dop.
         x_0 (nxp,) / (B,nxp): the plant state; None continues from the end of the previous `sim` (the plant's xop at first).
-        xhat_0: the estimate; None continues from the attached estimator's state (the estimator half of `initstate!` is not
-        run).  lastu: None continues from `self.lastu0`.  Afterwards `self.xhat0`, `self.lastu0`, `self.Z` and `self.status` are
+        xhat_0: the estimate; None continues from the attached estimator's state.  `initstate=True` does what
+        `sim_closedloop!` does first (src/plot_sim.jl:289-290): `initstate(lastu, lasty[i_ym], lastd)` with `lasty` the plant's
+        output at x_0 and d (no step, no noise), then `setstate` when `xhat_0` is given; the default leaves the estimator as it
+        is.  With a MovingHorizonEstimator attached (`setestimator(mhe=…)`) every period runs the estimator's solve on the
+        device, `SimResult.est_status` holds its status per period, failed solves are counted in one warning per run, and a NaN
+        in a measurement is passed to the estimator unchanged (missed measurements are a Kalman-filter feature of the
+        reference, kalman.jl:245-251).  lastu: None continues from `self.lastu0`.  Afterwards `self.xhat0`, `self.lastu0`, `self.Z` and `self.status` are
         those of the last period, so `preparestate` / `moveinput` / `updatestate` can go on from there.
 
         The noise of period i is σ∘w[:, :, i] with standard-normal draws w: `draws=dict(w_d=…, w_y=…, w_u=…, w_x=…)`, each
@@ -1442,8 +1605,19 @@ class BatchLinMPC:
             x0 = self.sim_x0.copy()
         else:
             x0 = np.zeros((B, nxp))
-        xh = self.xhat0.copy() if xhat_0 is None else _f64(self._bc(xhat_0, self.nxh, "x̂_0") - self.xhop).copy()
         lu = _f64(self.lastu0).copy() if lastu is None else _f64(self._bc(lastu, nu, "lastu") - self.uop).copy()
+        if initstate:         # sim_closedloop!: initstate!(est_mpc, lastu, lasty[i_ym], lastd), then setstate! (plot_sim.jl:289-290)
+            p = plant if isinstance(plant, dict) else dict(zip(("A", "Bu", "C", "Bd", "Dd"), plant))
+            bcm = lambda a: np.broadcast_to(np.asarray(a, float), (B,) + np.shape(a)[-2:])
+            lasty0 = np.einsum("bij,bj->bi", bcm(p["C"]), x0)
+            if nd > 0 and p.get("Dd") is not None:
+                lasty0 = lasty0 + np.einsum("bij,bj->bi", bcm(p["Dd"]), d0)
+            self.initstate(lu + self.uop, (lasty0 + self.yop)[:, self.i_ym], None if nd == 0 else d0 + self.dop)
+            if xhat_0 is not None:
+                self.setstate(self._bc(xhat_0, self.nxh, "x̂_0"))
+            xh = _f64(self.xhat0).copy()
+        else:
+            xh = self.xhat0.copy() if xhat_0 is None else _f64(self._bc(xhat_0, self.nxh, "x̂_0") - self.xhop).copy()
         self._sim_prepare()
         # the single-launch path (include/mpcqp.h: MPCQP_SIM_PATH_FUSED) computes u alone: self.Z is NaN after such a run, as
         # after moveinput(..., want_Z=False)
@@ -1453,7 +1627,15 @@ class BatchLinMPC:
         status = np.empty((B, N), np.int32)
         self.hd.sim(N, flags, ry=ry0, Ru=Ru0, d=d0, **steps, **sig, **w, x0=x0, xhat0=xh, lastu0=lu, Ztilde=Z, status=status,
                     **{k: (v if v.size else None) for k, v in rec.items()})
-        self.sim_x0, self.xhat0, self.lastu0 = x0, xh, lu
+        est = getattr(self, "mhe", None)
+        est_status = None
+        if est is not None:       # the estimator's device state went on with the run; its host mirror follows
+            from .mhe import GET_STATUS
+            est.x̂0, est.status = xh, est.handle.get(GET_STATUS)
+            est_status = self.hd.sim_est_status(N).T.copy()
+            self.sim_x0, self.lastu0 = x0, lu
+        else:
+            self.sim_x0, self.xhat0, self.lastu0 = x0, xh, lu
         self.Z = np.full((B, self.nZ), np.nan) if fused else Z
         self.status = status[:, -1].copy()
         self.iters = np.zeros(B, np.int32)
@@ -1464,14 +1646,17 @@ class BatchLinMPC:
         if nwarn:     # @warn branch, :491-496
             warnings.warn(f"MPC termination status not OPTIMAL: keeping solution anyway "
                           f"({nwarn} of {B * N} controller periods)", RuntimeWarning)
-        nmiss = int(np.isnan(rec["Y"][:, :, self.i_ym]).any(axis=2).sum())
+        if est is not None:
+            self._warn_mhe(est_status, B * N, "estimator periods")
+        nmiss = 0 if est is not None else int(np.isnan(rec["Y"][:, :, self.i_ym]).any(axis=2).sum())
         if nmiss:     # kalman.jl:245-251
             warnings.warn("NaN values in the Kalman filter measurements ym: skipping correction step "
                           f"({nmiss} of {B * N} estimator periods)", RuntimeWarning)
         t = lambda k, op: rec[k].transpose(0, 2, 1) + op[:, :, None]
         return SimResult(N=N, Y_data=t("Y", self.yop), Ry_data=Ry_data, Ŷ_data=t("Yhat", self.yop), U_data=t("U", self.uop),
                          Ud_data=t("Ud", self.uop), Ru_data=Ru_data, D_data=t("D", self.dop), X_data=t("X", xop),
-                         X̂_data=t("Xhat", self.xhop), status=status, path=SIM_PATH_FUSED if fused else SIM_PATH_PERIOD)
+                         X̂_data=t("Xhat", self.xhop), status=status, path=SIM_PATH_FUSED if fused else SIM_PATH_PERIOD,
+                         est_status=est_status)
 
     def _period_args(self, xhat0, ry, d, lastu, Dhat, Rhaty, Rhatu):
         """The arguments of `moveinput` checked, broadcast over the batch and turned into what a step takes: x̂0, ry
@@ -1561,6 +1746,8 @@ class BatchLinMPC:
             info["P̂"], info["K̂"], info["kf_status"] = self.hd.kf_covariance(), self.hd.kf_gain(), self.hd.kf_status()
             if getattr(self, "kf_steady", False) and hasattr(self.hd, "kf_steady_path"):
                 info["kf_steady_path"] = self.hd.kf_steady_path()      # 1: solved by the square-root form (semidefinite Q̂)
+        if getattr(self, "mhe", None) is not None:
+            info["estim"] = self.mhe.getinfo()
         # decision vector in the transcription's layout: [ΔU; ϵ] or [ΔU; X̂0(k+1..k+Hp); ϵ] (get_nZ_mpc, transcription.jl:2-7)
         parts = [DU] + ([X0.reshape(self.B, -1)] if self.transcription == "MultipleShooting" else []) + ([eps[:, None]] if self.neps else [])
         info["Z̃"] = np.concatenate(parts, axis=1)
@@ -1640,10 +1827,12 @@ class BatchExplicitMPC(BatchLinMPC):
         self.yop, self.dop = vec(yop, self.ny, self.yop), vec(dop, self.nd, self.dop)
         if xhop is not None:                   # the attached estimator's state keeps its engineering value (x̂0 += x̂op_old - x̂op_new)
             new = vec(xhop, self.nxh, None)
-            if getattr(self, "xhat0", None) is not None:
+            if getattr(self, "mhe", None) is None and getattr(self, "xhat0", None) is not None:
                 self.xhat0 = self.xhat0 + self.xhop - new
             self.xhop = new
         self.fhop = vec(fhop, self.nxh, self.fhop)
+        if getattr(self, "mhe", None) is not None:      # the estimator moves its windows, x̂0 and bounds itself (BatchMHE.setmodel)
+            self._mhe_ops = dict(uop=self.uop, yop_m=self.yop[:, self.i_ym], dop=self.dop, x̂op=self.xhop, f̂op=self.fhop)
         self.Uop, self.Yop, self.Dop = np.tile(self.uop, Hp), np.tile(self.yop, Hp), np.tile(self.dop, Hp)
         super().setmodel(Ahat, Bhu, Chat, Bhd, Dhd)
         if self._explicit_ready:               # (the handle has refreshed factor and law inside mpcqp_set_model)

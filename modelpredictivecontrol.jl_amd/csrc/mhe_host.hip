@@ -24,6 +24,7 @@ struct mpcqp_mhe_s {
     uint32_t flags = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev_own = nullptr, ev_ext = nullptr;      // ordering between the handle's stream and a caller's (enter_stream / leave_stream)
     bool timed = false, have_model = false, have_init = false;
     int Nk = 0;
     std::vector<void*> owned;
@@ -48,11 +49,27 @@ struct mpcqp_mhe_s {
 static hipError_t do_setup(mpcqp_mhe h) {
     return h->wide ? mhe::launch_wide_setup(h->d, h->raw, h->a.cst, h->stream) : mhe::launch_setup(h->d, h->raw, h->a.cst, h->stream);
 }
-static hipError_t do_cov(mpcqp_mhe h, int mode, const double* P0, double* Pout) {
-    return h->wide ? mhe::launch_wide_cov(h->d, h->a, mode, P0, Pout, h->stream) : mhe::launch_cov(h->d, h->a, mode, P0, Pout, h->stream);
+static hipError_t do_cov(mpcqp_mhe h, int mode, const double* P0, double* Pout, hipStream_t st) {
+    return h->wide ? mhe::launch_wide_cov(h->d, h->a, mode, P0, Pout, st) : mhe::launch_cov(h->d, h->a, mode, P0, Pout, st);
 }
-static hipError_t do_step(mpcqp_mhe h, const mhe::Args& a) {
-    return h->wide ? mhe::launch_wide_step(h->d, a, h->stream) : mhe::launch_step(h->d, a, h->stream);
+static hipError_t do_step(mpcqp_mhe h, const mhe::Args& a, hipStream_t st) {
+    return h->wide ? mhe::launch_wide_step(h->d, a, st) : mhe::launch_step(h->d, a, st);
+}
+
+// A period enqueued on a caller's stream (the *_stream entry points: an estimator attached to a controller runs on the stream
+// of the controller's loop) starts behind everything queued so far on the handle's own stream, and whatever the handle's own
+// stream does next -- mpcqp_mhe_get, a setter's upload -- starts behind that period.
+static int enter_stream(mpcqp_mhe h, hipStream_t st) {
+    if (st == h->stream) return MPCQP_OK;
+    HIPCHK(hipEventRecord(h->ev_own, h->stream));
+    HIPCHK(hipStreamWaitEvent(st, h->ev_own, 0));
+    return MPCQP_OK;
+}
+static int leave_stream(mpcqp_mhe h, hipStream_t st) {
+    if (st == h->stream) return MPCQP_OK;
+    HIPCHK(hipEventRecord(h->ev_ext, st));
+    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_ext, 0));
+    return MPCQP_OK;
 }
 
 static int dalloc(mpcqp_mhe h, void** p, size_t bytes) {
@@ -88,7 +105,7 @@ static int ensure_scratch(mpcqp_mhe h) {
 
 // one estimation period on the device: window bookkeeping (add_data_windows!, execute.jl:497-548),
 // arrival covariance correction when the window moves (current form, execute.jl:727-745), solve
-static int solve_period(mpcqp_mhe h, const double* y_dev, const double* d_dev, const double* u_dev) {
+static int solve_period(mpcqp_mhe h, const double* y_dev, const double* d_dev, const double* u_dev, hipStream_t st) {
     mhe::Dims& d = h->d;
     bool moving = false;
     if (h->Nk < d.He) {
@@ -101,14 +118,14 @@ static int solve_period(mpcqp_mhe h, const double* y_dev, const double* d_dev, c
     d.N = h->Nk;
     int rc = ensure_scratch(h);
     if (rc) return rc;
-    if (d.direct && moving) HIPCHK(do_cov(h, 1, nullptr, nullptr));
+    if (d.direct && moving) HIPCHK(do_cov(h, 1, nullptr, nullptr, st));
     mhe::Args a = h->a;
     a.y0m_new = y_dev;
     a.d0_new = d_dev;
     a.u0_new = u_dev;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    HIPCHK(do_step(h, a));
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipEventRecord(h->ev0, st));
+    HIPCHK(do_step(h, a, st));
+    HIPCHK(hipEventRecord(h->ev1, st));
     h->timed = true;
     return MPCQP_OK;
 }
@@ -163,6 +180,8 @@ int mpcqp_mhe_create(const mpcqp_mhe_dims* in, mpcqp_mhe* out) {
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&h->ev0);
     if (e == hipSuccess) e = hipEventCreate(&h->ev1);
+    if (e == hipSuccess) e = hipEventCreate(&h->ev_own);
+    if (e == hipSuccess) e = hipEventCreate(&h->ev_ext);
     if (e != hipSuccess) { g_hip_err = std::string("stream/event create: ") + hipGetErrorString(e); rc = MPCQP_ERR_DEVICE; }
     const size_t B = d.B, nx = d.nx, nu = d.nu, nym = d.nym, nd = d.nd, He = d.He;
     auto mk = [&](double** p, size_t n) { if (!rc) rc = dalloc_t(h, p, n); };
@@ -189,6 +208,8 @@ int mpcqp_mhe_destroy(mpcqp_mhe h) {
     for (void* p : h->owned) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->ev_own) (void)hipEventDestroy(h->ev_own);
+    if (h->ev_ext) (void)hipEventDestroy(h->ev_ext);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return MPCQP_OK;
@@ -409,7 +430,7 @@ int mpcqp_mhe_init(mpcqp_mhe h, const double* xhat0, const double* P0, const dou
     if (rc) return rc;
     d.hy = d.hd = 0;
     h->Nk = 0;
-    HIPCHK(do_cov(h, 4, h->P0, nullptr));
+    HIPCHK(do_cov(h, 4, h->P0, nullptr, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_init = true;
     return MPCQP_OK;
@@ -459,31 +480,68 @@ int mpcqp_mhe_shift_windows(mpcqp_mhe h, const double* dy0m, const double* du0, 
     return rc;
 }
 
-int mpcqp_mhe_prepare_device(mpcqp_mhe h, const double* y0m_dev, const double* d0_dev) {
+int mpcqp_mhe_prepare_stream(mpcqp_mhe h, const double* y0m_dev, const double* d0_dev, void* stream) {
     if (!h || !y0m_dev) return MPCQP_ERR_NULL;
     if (h->d.nd > 0 && !d0_dev) return MPCQP_ERR_NULL;
     if (!h->have_init) return MPCQP_ERR_ORDER;
     if (!h->d.direct) return MPCQP_OK;
     ON_DEVICE(h);
-    return solve_period(h, y0m_dev, d0_dev, h->lastu);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = enter_stream(h, st);
+    if (!rc) rc = solve_period(h, y0m_dev, d0_dev, h->lastu, st);
+    if (!rc) rc = leave_stream(h, st);
+    return rc;
 }
 
-int mpcqp_mhe_update_device(mpcqp_mhe h, const double* u0_dev, const double* y0m_dev, const double* d0_dev) {
+int mpcqp_mhe_update_stream(mpcqp_mhe h, const double* u0_dev, const double* y0m_dev, const double* d0_dev, void* stream) {
     if (!h) return MPCQP_ERR_NULL;
     if (h->d.nu > 0 && !u0_dev) return MPCQP_ERR_NULL;
     if (!h->have_init) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     const mhe::Dims& d = h->d;
+    hipStream_t st = (hipStream_t)stream;
+    if (!d.direct && (!y0m_dev || (d.nd > 0 && !d0_dev))) return MPCQP_ERR_NULL;
+    int rc = enter_stream(h, st);
+    if (rc) return rc;
     if (!d.direct) {
-        if (!y0m_dev || (d.nd > 0 && !d0_dev)) return MPCQP_ERR_NULL;
-        int rc = solve_period(h, y0m_dev, d0_dev, u0_dev);
+        rc = solve_period(h, y0m_dev, d0_dev, u0_dev, st);
         if (rc) return rc;
     }
     // update_cov! (execute.jl:755-781): once the window is full, the arrival covariance advances by one
     // KalmanFilter period (prediction only in the current form: it was corrected in preparestate!)
-    if (h->Nk == d.He) HIPCHK(do_cov(h, d.direct ? 2 : 3, nullptr, nullptr));
+    if (h->Nk == d.He) HIPCHK(do_cov(h, d.direct ? 2 : 3, nullptr, nullptr, st));
     if (d.nu > 0)
-        HIPCHK(hipMemcpyAsync(h->lastu, u0_dev, (size_t)d.B * d.nu * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->lastu, u0_dev, (size_t)d.B * d.nu * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return leave_stream(h, st);
+}
+
+int mpcqp_mhe_prepare_device(mpcqp_mhe h, const double* y0m_dev, const double* d0_dev) {
+    return h ? mpcqp_mhe_prepare_stream(h, y0m_dev, d0_dev, h->stream) : MPCQP_ERR_NULL;
+}
+
+int mpcqp_mhe_update_device(mpcqp_mhe h, const double* u0_dev, const double* y0m_dev, const double* d0_dev) {
+    return h ? mpcqp_mhe_update_stream(h, u0_dev, y0m_dev, d0_dev, h->stream) : MPCQP_ERR_NULL;
+}
+
+int mpcqp_mhe_set_state_stream(mpcqp_mhe h, const double* xhat0_dev, void* stream) {
+    if (!h || !xhat0_dev) return MPCQP_ERR_NULL;
+    if (!h->have_init) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = enter_stream(h, st);
+    if (rc) return rc;
+    if (xhat0_dev != h->a.xhat0)
+        HIPCHK(hipMemcpyAsync(h->a.xhat0, xhat0_dev, (size_t)h->d.B * h->d.nx * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return leave_stream(h, st);
+}
+
+int mpcqp_mhe_get_dims(mpcqp_mhe h, mpcqp_mhe_dims* out) {
+    if (!h || !out) return MPCQP_ERR_NULL;
+    const mhe::Dims& d = h->d;
+    *out = mpcqp_mhe_dims{};
+    out->batch = d.B; out->nxhat = d.nx; out->nu = d.nu; out->nym = d.nym; out->nd = d.nd; out->He = d.He;
+    out->direct = d.direct; out->device = h->device; out->flags = h->flags; out->max_iter = d.max_iter;
+    out->gap_tol = d.gap_tol; out->res_tol = d.res_tol; out->dual_reg = d.dual_reg;
     return MPCQP_OK;
 }
 
@@ -555,7 +613,7 @@ int mpcqp_mhe_get(mpcqp_mhe h, int what, void* out) {
         case MPCQP_MHE_EPSILON: src = h->a.eps_out; bytes = B * 8; break;
         case MPCQP_MHE_PBAR: {
             // the row-lane array back to (nx̂,nx̂,B): a covariance launch with no update writes the ABI copy
-            HIPCHK(do_cov(h, 0, nullptr, h->Pout));
+            HIPCHK(do_cov(h, 0, nullptr, h->Pout, h->stream));
             src = h->Pout; bytes = B * nx * nx * 8; break;
         }
         default: return MPCQP_ERR_ARG;

@@ -10,7 +10,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/mpcqp.h"
+#include "../../include/mpcqp_mhe.h"
+#include "est_init_launch.h"
 #include "explicit_launch.h"
 #include "kf_cov_launch.h"
 #include "kf_dare_launch.h"
@@ -105,6 +106,13 @@ struct mpcqp_handle_s {
     bool sp_has_Bd = false, sp_has_Dd = false, sp_has_fx = false;
     DBuf sim_u0, sim_st, sim_it, sim_d0, sim_y0m, sim_ry, sim_dh;
     DBuf sim_s[26];
+    // LinMPC(MovingHorizonEstimator): the estimator behind this controller (mpcqp_mhe_attach; borrowed).  kf.i_ym / kf.nym
+    // then hold the attachment's measured rows, have_kf is false.  sim_est: its status array after every period of the last
+    // mpcqp_sim[_device], [N][B]; ei_*: staging of the host-pointer mpcqp_est_initstate
+    mpcqp_mhe mhe = nullptr;
+    DBuf sim_est;
+    int sim_est_N = 0;
+    DBuf ei_x, ei_u, ei_y, ei_d, ei_st;
 };
 
 static int dev_alloc(mpcqp_handle h, DBuf& b, size_t bytes) {
@@ -818,6 +826,22 @@ int mpcqp_loop_device(mpcqp_handle h, double* xhat0, const double* y0m, const do
                       double* Ztilde, double* u0, int32_t* status, int32_t* iters, double* Yhat0,
                       void* stream) {
     if (!h || !y0m || !xhat0) return MPCQP_ERR_NULL;
+    if (h->mhe) {
+        // a MovingHorizonEstimator behind the controller: preparestate!, the step on the estimator's own x̂0 (read in place),
+        // updatestate!, three calls on the caller's stream.  Refusals first: a step that does not run leaves the windows alone
+        if (!lastu0 || !Ry || !Ztilde || !u0 || !status || (h->d.nd > 0 && (!d0 || !Dhat0))) return MPCQP_ERR_NULL;
+        if (!h->have_model || !h->have_weights) return MPCQP_ERR_ORDER;
+        if (uses_stage_kernel(h) && ms_unsupported(h)) return MPCQP_ERR_UNSUPPORTED;
+        const double* xe = (const double*)mpcqp_mhe_device_ptr(h->mhe, MPCQP_MHE_XHAT0);
+        int rc = mpcqp_mhe_prepare_stream(h->mhe, y0m, d0, stream);
+        if (!rc) rc = step_device_impl(h, xe, lastu0, Ry, Ru, d0, Dhat0, Ztilde, u0, status, iters, Yhat0, stream, nullptr, nullptr, 0);
+        if (rc) return rc;
+        {
+            ON_DEVICE(h);
+            HIPCHK(hipMemcpyAsync(xhat0, xe, (size_t)h->d.B * h->d.nxh * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        }
+        return mpcqp_mhe_update_stream(h->mhe, u0, y0m, d0, stream);
+    }
     if (!h->have_kf) return MPCQP_ERR_ORDER;
     if (h->d.nxh > 4 * WAVE) return MPCQP_ERR_UNSUPPORTED;
     // K̂(k) and P̂(k+1|k) first, in either form: the recursion depends on which measurements are missing and on nothing else
@@ -1237,6 +1261,7 @@ int mpcqp_kf_set(mpcqp_handle h, const double* Khat, const int32_t* i_ym, int32_
     h->kf.i_ym = (const int*)h->kf_iym.p;
     h->kf.nym = nym;
     h->have_kf = true;
+    h->mhe = nullptr;           // (a Kalman handle again)
     h->kf_tv = false;           // (back to the steady gain: the covariance kernel no longer runs)
     h->kf_steady = false;       // (a gain of the caller's: nothing to re-solve)
     return MPCQP_OK;
@@ -1290,6 +1315,7 @@ int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* R
     h->kf_NX = kf::kf_cov_columns_for(std::max(d.nxh, (int)nym));
     h->kf_waves = kf::kf_cov_waves_for(h->device, d.B, h->kf_NX);
     h->have_kf = true;
+    h->mhe = nullptr;
     h->kf_tv = true;
     h->kf_steady = false;
     return MPCQP_OK;
@@ -1349,6 +1375,7 @@ int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, 
     h->kf_NX = kf::kf_cov_columns_for(std::max(d.nxh, (int)nym));
     h->kf_dare_waves = kf::kf_dare_waves_for(h->device, d.B, h->kf_NX);
     h->have_kf = true;
+    h->mhe = nullptr;
     h->kf_tv = false;
     h->kf_steady = true;
     return mpcqp_kf_solve_steady(h);
@@ -1512,6 +1539,74 @@ int mpcqp_kf_predict(mpcqp_handle h, double* xhat0, const double* u0, const doub
     return kf_host(h, xhat0, u0, h ? (size_t)h->d.nu : 0, d0, false);
 }
 
+// ---- LinMPC(MovingHorizonEstimator): attachment, and the estimator half of initstate! (include/mpcqp_mhe.h) ------------------
+
+int mpcqp_mhe_attach(mpcqp_handle h, mpcqp_mhe e, const int32_t* i_ym, int32_t nym) {
+    if (!h) return MPCQP_ERR_NULL;
+    if (!e) { h->mhe = nullptr; return MPCQP_OK; }
+    if (!i_ym) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    mpcqp_mhe_dims ed{};
+    { int rc = mpcqp_mhe_get_dims(e, &ed); if (rc) return rc; }
+    if (ed.batch != d.B || ed.nxhat != d.nxh || ed.nu != d.nu || ed.nd != d.nd || ed.nym != nym || ed.device != h->device ||
+        nym < 1 || nym > d.ny)
+        return MPCQP_ERR_DIMS;
+    for (int i = 0; i < nym; ++i) {
+        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;     // validate_ym, construct.jl:190-196
+        for (int j = 0; j < i; ++j)
+            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
+    }
+    ON_DEVICE(h);
+    int rc = upload(h, h->kf_iym, i_ym, (size_t)nym * sizeof(int32_t));
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->kf.Khat = nullptr;
+    h->kf.i_ym = (const int*)h->kf_iym.p;
+    h->kf.nym = nym;
+    h->have_kf = h->kf_tv = h->kf_steady = false;       // (the attachment replaces a Kalman filter)
+    h->mhe = e;
+    return MPCQP_OK;
+}
+
+int mpcqp_est_initstate_device(mpcqp_handle h, double* xhat0, const double* u0, const double* y0m, const double* d0,
+                               int32_t* status, void* stream) {
+    if (!h || !xhat0 || !u0 || !y0m || !status) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    if (!(h->have_kf || h->mhe) || !h->have_model) return MPCQP_ERR_ORDER;
+    if (std::max(d.nxh, h->kf.nym) > est::EST_INIT_NMAX || !est::est_init_available()) return MPCQP_ERR_UNSUPPORTED;
+    ON_DEVICE(h);
+    est::InitArgs a{};
+    a.Ahat = h->m.Ahat; a.Bu = h->m.Bu; a.C = h->m.C; a.Bd = d.nd > 0 ? h->m.Bd : nullptr; a.Dd = d.nd > 0 ? h->m.Dd : nullptr;
+    a.fx = h->m.dop; a.i_ym = h->kf.i_ym;
+    a.B = d.B; a.nx = d.nxh; a.nu = d.nu; a.ny = d.ny; a.nd = d.nd; a.nym = h->kf.nym;
+    a.u0 = u0; a.y0m = y0m; a.d0 = d.nd > 0 ? d0 : nullptr; a.xhat0 = xhat0; a.status = status;
+    HIPCHK(est::launch_est_init(a, (hipStream_t)stream));
+    return MPCQP_OK;
+}
+
+int mpcqp_est_initstate(mpcqp_handle h, double* xhat0, const double* u0, const double* y0m, const double* d0, int32_t* status) {
+    if (!h || !xhat0 || !u0 || !y0m || !status) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    if (!(h->have_kf || h->mhe) || !h->have_model) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    const size_t B = d.B, sz = sizeof(double);
+    int rc = upload(h, h->ei_x, xhat0, B * d.nxh * sz);
+    if (!rc) rc = upload(h, h->ei_u, u0, B * d.nu * sz);
+    if (!rc) rc = upload(h, h->ei_y, y0m, B * (size_t)h->kf.nym * sz);
+    if (!rc && d.nd > 0) rc = upload(h, h->ei_d, d0, B * d.nd * sz);
+    if (!rc) rc = dev_alloc(h, h->ei_st, B * sizeof(int32_t));
+    if (rc) return rc;
+    rc = mpcqp_est_initstate_device(h, (double*)h->ei_x.p, (const double*)h->ei_u.p, (const double*)h->ei_y.p,
+                                    d.nd > 0 ? (const double*)h->ei_d.p : nullptr, (int32_t*)h->ei_st.p, h->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(xhat0, h->ei_x.p, B * d.nxh * sz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(status, h->ei_st.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
 // ---- sim!: the closed loop of the whole batch, plant included (include/mpcqp.h; kernel: sim_bodies.h) ----------------------
 
 int mpcqp_sim_set_plant(mpcqp_handle h, int32_t nxp, const double* A, const double* Bu, const double* C, const double* Bd,
@@ -1573,7 +1668,7 @@ static int sim_check(mpcqp_handle h, const mpcqp_sim_io* io) {
     if (!h || !io) return MPCQP_ERR_NULL;
     if (io->N <= 0 || (io->flags & ~(MPCQP_SIM_FLAG_RY_PER_PERIOD | MPCQP_SIM_FLAG_NO_FUSE))) return MPCQP_ERR_ARG;
     const int ctrl = sim_controller(h, io);
-    if (!h->have_plant || !h->have_kf || ctrl == SIM_CTRL_NONE) return MPCQP_ERR_ORDER;
+    if (!h->have_plant || !(h->have_kf || h->mhe) || ctrl == SIM_CTRL_NONE) return MPCQP_ERR_ORDER;
     if (!io->ry || !io->x0 || !io->xhat0 || !io->lastu0 || (h->d.nd > 0 && !io->d)) return MPCQP_ERR_NULL;
     if (!io->Ztilde && ctrl != SIM_CTRL_EXPLICIT_LAW) return MPCQP_ERR_NULL;
     if ((io->sigma_u && !io->w_u) || (io->sigma_y && !io->w_y) || (io->sigma_x && !io->w_x) ||
@@ -1601,7 +1696,13 @@ int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io_in, void* stream) {
     if (!rc && d.nd > 0) rc = dev_alloc(h, h->sim_d0, B * d.nd * sz);
     if (!rc && per_period) rc = dev_alloc(h, h->sim_ry, B * d.ny * sz);
     if (!rc && horizon) rc = dev_alloc(h, h->sim_dh, B * d.nD * sz);
+    if (!rc && h->mhe) rc = dev_alloc(h, h->sim_est, B * (size_t)N * sizeof(int32_t));
     if (rc) return rc;
+    // an attached MovingHorizonEstimator: the controller, the plant kernel and the X̂ / Ŷ records read its x̂0 in place
+    mpcqp_mhe const est = h->mhe;
+    double* const xh = est ? (double*)mpcqp_mhe_device_ptr(est, MPCQP_MHE_XHAT0) : io->xhat0;
+    const int32_t* const est_st = est ? (const int32_t*)mpcqp_mhe_device_ptr(est, MPCQP_MHE_STATUS) : nullptr;
+    h->sim_est_N = 0;
     double* u0 = (double*)h->sim_u0.p;
     int32_t *cst = (int32_t*)h->sim_st.p, *cit = (int32_t*)h->sim_it.p;
     double* y0m = (double*)h->sim_y0m.p;
@@ -1620,7 +1721,7 @@ int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io_in, void* stream) {
     a.u_step = io->u_step; a.y_step = io->y_step; a.d_step = io->d_step;
     a.su = io->sigma_u; a.sy = io->sigma_y; a.sd = io->sigma_d; a.sx = io->sigma_x;
     a.wu = io->w_u; a.wy = io->w_y; a.wd = io->w_d; a.wx = io->w_x;
-    a.x = io->x0; a.xhat = io->xhat0; a.lastu0 = io->lastu0; a.u0 = u0; a.st = cst;
+    a.x = io->x0; a.xhat = xh; a.lastu0 = io->lastu0; a.u0 = u0; a.st = cst;
     a.d0 = d0; a.y0m = y0m; a.ry_cur = per_period ? (double*)h->sim_ry.p : nullptr; a.Dhat0 = Dh;
     a.Y = io->Y; a.X = io->X; a.D = io->D; a.Xhat = io->Xhat; a.Yhat = io->Yhat; a.U = io->U; a.Ud = io->Ud; a.status = io->status;
     if (sim_fused(h, io)) {         // the whole loop in one launch (k_sim_explicit); Z̃ is not computed on this path
@@ -1652,26 +1753,49 @@ int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io_in, void* stream) {
     h->d.flags |= MPCQP_FLAG_RY_CONSTANT;
     h->m.ry_now = nullptr;
 
+    if (est) { rc = mpcqp_mhe_set_state_stream(est, io->xhat0, stream); if (rc) return rc; }     // setstate!: x̂0 and nothing else
     HIPCHK(plant(-1, -1, 0));
     for (int i = 0; i < N; ++i) {
-        if (h->kf_direct) { rc = mpcqp_kf_correct_device(h, io->xhat0, y0m, d0, stream); if (rc) return rc; }
+        if (est) { rc = mpcqp_mhe_prepare_stream(est, y0m, d0, stream); if (rc) return rc; }      // (predictor form: nothing)
+        else if (h->kf_direct) { rc = mpcqp_kf_correct_device(h, io->xhat0, y0m, d0, stream); if (rc) return rc; }
         if (io->Xhat || io->Yhat) HIPCHK(plant(i, -1, -1));
         switch (ctrl) {
             case SIM_CTRL_EXPLICIT_LAW:
-                rc = mpcqp_explicit_law_device(h, io->xhat0, io->lastu0, ry, d0, io->Ztilde, u0, cst, stream);
+                rc = mpcqp_explicit_law_device(h, xh, io->lastu0, ry, d0, io->Ztilde, u0, cst, stream);
                 break;
             case SIM_CTRL_EXPLICIT_STEP:
-                rc = mpcqp_explicit_step_device(h, io->xhat0, io->lastu0, ry, io->Ru, d0, Dh, io->Ztilde, u0, cst, nullptr, stream);
+                rc = mpcqp_explicit_step_device(h, xh, io->lastu0, ry, io->Ru, d0, Dh, io->Ztilde, u0, cst, nullptr, stream);
                 break;
             default:
-                rc = mpcqp_step_device(h, io->xhat0, io->lastu0, ry, io->Ru, d0, Dh, io->Ztilde, u0, cst, cit, nullptr, stream);
+                rc = mpcqp_step_device(h, xh, io->lastu0, ry, io->Ru, d0, Dh, io->Ztilde, u0, cst, cit, nullptr, stream);
         }
         if (rc) return rc;
-        rc = h->kf_direct ? mpcqp_kf_predict_device(h, io->xhat0, u0, d0, stream)
-                          : mpcqp_kf_update_device(h, io->xhat0, u0, y0m, d0, stream);
-        if (rc) return rc;
+        if (est) {
+            rc = mpcqp_mhe_update_stream(est, u0, y0m, d0, stream);
+            if (rc) return rc;
+            // the estimator's status of this period (the solve of preparestate! or, predictor form, of updatestate!)
+            HIPCHK(hipMemcpyAsync((int32_t*)h->sim_est.p + (size_t)i * B, est_st, B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        } else {
+            rc = h->kf_direct ? mpcqp_kf_predict_device(h, io->xhat0, u0, d0, stream)
+                              : mpcqp_kf_update_device(h, io->xhat0, u0, y0m, d0, stream);
+            if (rc) return rc;
+        }
         HIPCHK(plant(-1, i, i + 1 < N ? i + 1 : -1));
     }
+    if (est) {
+        HIPCHK(hipMemcpyAsync(io->xhat0, xh, B * d.nxh * sz, hipMemcpyDeviceToDevice, st));
+        h->sim_est_N = N;
+    }
+    return MPCQP_OK;
+}
+
+int mpcqp_sim_est_status(mpcqp_handle h, int32_t* out, int32_t N) {
+    if (!h || !out) return MPCQP_ERR_NULL;
+    if (h->sim_est_N < 1 || !h->sim_est.p) return MPCQP_ERR_ORDER;
+    if (N < 1 || N > h->sim_est_N) return MPCQP_ERR_ARG;
+    ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());         // (the run may have been enqueued on a stream of the caller's)
+    HIPCHK(hipMemcpy(out, h->sim_est.p, (size_t)N * h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
     return MPCQP_OK;
 }
 

@@ -22,7 +22,8 @@ from .api import MpcqpError, _chk, _f64, _ptr, colmajor
 EXPORTS = ("mpcqp_mhe_create", "mpcqp_mhe_destroy", "mpcqp_mhe_set_model", "mpcqp_mhe_set_bounds", "mpcqp_mhe_set_bounds_window", "mpcqp_mhe_set_softness", "mpcqp_mhe_set_softness_window", "mpcqp_mhe_init", "mpcqp_mhe_set_state", "mpcqp_mhe_shift_windows",
            "mpcqp_mhe_prepare", "mpcqp_mhe_update", "mpcqp_mhe_prepare_device", "mpcqp_mhe_update_device",
            "mpcqp_mhe_sync", "mpcqp_mhe_get", "mpcqp_mhe_device_ptr", "mpcqp_mhe_nk", "mpcqp_mhe_last_ms",
-           "mpcqp_mhe_register_columns", "mpcqp_mhe_lanes_per_estimator")
+           "mpcqp_mhe_register_columns", "mpcqp_mhe_lanes_per_estimator", "mpcqp_mhe_prepare_stream", "mpcqp_mhe_update_stream",
+           "mpcqp_mhe_set_state_stream", "mpcqp_mhe_get_dims", "mpcqp_mhe_attach")
 KEEP_WINDOWS = 1
 GET_XHAT0, GET_ZTILDE, GET_STATUS, GET_ITERS, GET_PBAR, GET_VHAT, GET_XHATWIN, GET_EPSILON = range(8)
 
@@ -52,6 +53,11 @@ def _bind(lib):
     lib.mpcqp_mhe_prepare_device.argtypes = [C.c_void_p] * 3
     lib.mpcqp_mhe_update_device.argtypes = [C.c_void_p] * 4
     lib.mpcqp_mhe_sync.argtypes = [C.c_void_p]
+    if hasattr(lib, "mpcqp_mhe_prepare_stream"):
+        lib.mpcqp_mhe_prepare_stream.argtypes = [C.c_void_p] * 4
+        lib.mpcqp_mhe_update_stream.argtypes = [C.c_void_p] * 5
+        lib.mpcqp_mhe_set_state_stream.argtypes = [C.c_void_p] * 3
+        lib.mpcqp_mhe_get_dims.argtypes = [C.c_void_p, C.POINTER(MheDims)]
     lib.mpcqp_mhe_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.mpcqp_mhe_device_ptr.restype = C.c_void_p
     lib.mpcqp_mhe_device_ptr.argtypes = [C.c_void_p, C.c_int]
@@ -144,6 +150,24 @@ class MheHandle:
 
     def update_device(self, u0, y0m=0, d0=0):
         _chk(self.lib, self.lib.mpcqp_mhe_update_device(self._h, u0, y0m, d0))
+
+    def prepare_stream(self, y0m, d0=0, stream=0):
+        """mpcqp_mhe_prepare_stream: device addresses, asynchronous on `stream` (0: the default stream)."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _chk(self.lib, self.lib.mpcqp_mhe_prepare_stream(self._h, v(y0m), v(d0), v(stream)))
+
+    def update_stream(self, u0, y0m=0, d0=0, stream=0):
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _chk(self.lib, self.lib.mpcqp_mhe_update_stream(self._h, v(u0), v(y0m), v(d0), v(stream)))
+
+    def set_state_stream(self, xhat0, stream=0):
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _chk(self.lib, self.lib.mpcqp_mhe_set_state_stream(self._h, v(xhat0), v(stream)))
+
+    def dims(self):
+        out = MheDims()
+        _chk(self.lib, self.lib.mpcqp_mhe_get_dims(self._h, C.byref(out)))
+        return out
 
     def sync(self):
         _chk(self.lib, self.lib.mpcqp_mhe_sync(self._h))
