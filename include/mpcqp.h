@@ -281,6 +281,9 @@ int mpcqp_recondense_device(mpcqp_handle h, void* stream);
 #define MPCQP_GET_MS_DEFECT 9   /* (B): max |E_S Z + F_S| (defect of the model equations, transcription.jl:303-327) of it */
 #define MPCQP_GET_KF_COV    10  /* (nx̂,nx̂,B): P̂ of the time-varying KalmanFilter, P̂∞ after mpcqp_kf_set_steady (MPCQP_ERR_ORDER on a gain from mpcqp_kf_set) */
 #define MPCQP_GET_KF_GAIN   11  /* (nx̂,nym,B): K̂ the estimator steps use -- the steady gain or K̂(k) of the last correction */
+#define MPCQP_GET_IM_XS     13  /* (nxs,B): x̂s of the InternalModel estimator (mpcqp_im_set) */
+#define MPCQP_GET_IM_YS     14  /* (ny,B):  ŷs of its last correction (0 in the unmeasured rows) */
+#define MPCQP_GET_IM_YHATS  15  /* (nY,B):  Ŷs of its last correction, the term the steps add to the model's B */
 #define MPCQP_GET_EXPLICIT_LAW 12 /* (nZ, 1+nx̂+nu+ny+nd, B): the law [g0 Gx Gu Gr Gd] of mpcqp_explicit_prepare(h, MPCQP_EXPLICIT_LAW) */
 int mpcqp_get(mpcqp_handle h, int which, double* out);
 
@@ -533,6 +536,39 @@ int mpcqp_sim(mpcqp_handle h, const mpcqp_sim_io* io);
 int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io, void* stream);
 int mpcqp_sim_path(mpcqp_handle h);
 
+
+/* ---- InternalModel (src/estimator/internal_model.jl): the estimator that changes the controller's free response ----------
+ * The state is not augmented (Â = A, nx̂ = nx).  A stochastic model on the MEASURED outputs, As (nxs,nxs,B), Bs (nxs,nym,B),
+ * Cs (nym,nxs,B), Ds (nym,nym,B), column-major per member like the model -- all four NULL: the identity in all four with
+ * nxs = nym, the reference's default -- gives per period
+ *     correct   ŷs[i_ym[j]] = y0m[j] - (Ĉm x̂d + D̂dm d0)[j]   (0 for a y0m[j] that is not finite, 0 in the unmeasured rows;
+ *               x̂0 = x̂d is not touched), then block t = 1..Hp of Ŷs = Cs As^(t-1) (Âs x̂s + B̂s ŷs) -- the Ks x̂s + Ps ŷs of
+ *               init_stochpred, as a recurrence -- and B_eff = B + Ŷs
+ *     step      every mpcqp_step[_device] of the handle reads B_eff in place of the model's B: F, Ŷ, the gradient and the
+ *               output-bound rows carry Ŷs.  The step kernels are the ones of a handle without this estimator.
+ *     update    x̂d <- Â x̂d + B̂u u0 + B̂d d0 + (f̂op - x̂op),  x̂s <- Âs x̂s + B̂s ŷs
+ * with B̂s = Bs Ds⁻¹ and Âs = As - B̂s Cs from the set-up (k_im_setup: elimination with partial pivoting, per member).
+ * mpcqp_im_set replaces whatever estimator the handle had and zeroes x̂s, ŷs and Ŷs.  mpcqp_set_model keeps x̂s, ŷs, Ŷs and
+ * the stochastic model: the next step uses the new B with the Ŷs of the last correction.  mpcqp_im_status (B) int32:
+ *       0  ready
+ *       2  Ds of the member is singular (a zero or non-finite pivot): its stochastic part is off, ŷs = Ŷs = 0 always
+ * mpcqp_loop_device on such a handle enqueues correct, step, update on the caller's stream and updates xhat0 in place;
+ * mpcqp_sim[_device] takes it on the per-period path (the Ŷ record is Ĉ x̂0 + D̂d d0 + ŷs); mpcqp_est_initstate[_device] is
+ * init_estimate!: x̂d = (I - Â)⁻¹ (B̂u u0 + B̂d d0 + f̂op - x̂op), ŷs from it, x̂s = (I - Âs)⁻¹ B̂s ŷs; status 1 for a member one
+ * of whose two systems is singular, which keeps its x̂0, x̂s and ŷs.
+ * Limits (MPCQP_ERR_UNSUPPORTED): max(nx, nu, ny, nd, nxs) > 32; a handle whose steps run on the stage-structured kernel
+ * (MultipleShooting, or SingleShooting beyond the condensed kernels: it does not read B); custom linear constraints (nw > 0:
+ * their ŷ(k) term would need ŷs inside the kernel); mpcqp_explicit_* on such a handle; a shard handle of mpcqp_multi_*; a
+ * library built without the kernels.  mpcqp_kf_set_direct(h, 0) on such a handle: MPCQP_ERR_ARG (the estimator is always in
+ * the filter form).  nym < 1, nym > ny: MPCQP_ERR_DIMS; nxs < 1, i_ym out of range or repeated, some but not all of the
+ * four matrices NULL: MPCQP_ERR_ARG.  A refused call changes nothing. */
+int mpcqp_im_set(mpcqp_handle h, int32_t nxs, const double* As, const double* Bs, const double* Cs, const double* Ds,
+                 const int32_t* i_ym, int32_t nym);
+int mpcqp_im_status(mpcqp_handle h, int32_t* out);
+int mpcqp_im_correct(mpcqp_handle h, const double* xhat0, const double* y0m, const double* d0);
+int mpcqp_im_correct_device(mpcqp_handle h, const double* xhat0, const double* y0m, const double* d0, void* stream);
+int mpcqp_im_update(mpcqp_handle h, double* xhat0, const double* u0, const double* d0);
+int mpcqp_im_update_device(mpcqp_handle h, double* xhat0, const double* u0, const double* d0, void* stream);
 
 /* ---- which kernel runs a step; building specialised kernels ahead of the control loop -----------
  * A step runs on (MPCQP_KERNEL_AOT) a kernel specialised on the handle's dimensions that is compiled

@@ -281,6 +281,46 @@ function steadykalmanfilter_iters(b::BatchLinMPC)
 end
 
 # ------------------------------------------------------------------------------------------------
+# InternalModel behind the batch (include/mpcqp.h, "InternalModel"): the stochastic model on the measured outputs goes to the
+# device once, Âs and B̂s are computed there; per period correct (ŷs, Ŷs, B + Ŷs for the steps), the unchanged step, update.
+# Call sequence = BatchLinMPC.setestimator(internal=...) of api.py; these ccalls have not been run.
+import ModelPredictiveControl: InternalModel
+
+"As, Bs, Cs, Ds of the batch's InternalModels (restricted to the measured outputs) to the device."
+function push_internalmodel!(b::BatchLinMPC)
+    es = [c.estim for c in b.mpcs]
+    all(e -> e isa InternalModel && e.i_ym == es[1].i_ym && e.nxs == es[1].nxs, es) || throw(ArgumentError("InternalModels with one i_ym and nxs"))
+    iy = es[1].i_ym
+    stack3(f) = cat((Matrix{Float64}(f(e)) for e in es)...; dims=3)
+    As, Bs, Cs, Ds = stack3(e -> e.As), stack3(e -> e.Bs[:, iy]), stack3(e -> e.Cs[iy, :]), stack3(e -> e.Ds[iy, iy])
+    i_ym = Cint.(iy .- 1)                                                    # 0-based
+    GC.@preserve As Bs Cs Ds i_ym check(ccall((:mpcqp_im_set, lib), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Cint), b.h, es[1].nxs, As, Bs, Cs, Ds, i_ym, length(i_ym)))
+    return b
+end
+
+"preparestate! of the batch: ŷs and Ŷs from x̂0 = x̂d (nx, B) and y0m (nym, B); x̂0 is not changed."
+correct_internalmodel!(b::BatchLinMPC, x̂0::Matrix{Float64}, y0m::Matrix{Float64}, d0::Matrix{Float64}=zeros(0, size(x̂0, 2))) =
+    GC.@preserve x̂0 y0m d0 check(ccall((:mpcqp_im_correct, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                       b.h, x̂0, y0m, isempty(d0) ? C_NULL : pointer(d0)))
+
+"updatestate! of the batch: x̂d in place, x̂s on the device."
+update_internalmodel!(b::BatchLinMPC, x̂0::Matrix{Float64}, u0::Matrix{Float64}, d0::Matrix{Float64}=zeros(0, size(x̂0, 2))) =
+    GC.@preserve x̂0 u0 d0 check(ccall((:mpcqp_im_update, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                      b.h, x̂0, u0, isempty(d0) ? C_NULL : pointer(d0)))
+
+"The device entry points (asynchronous on `stream`) and the set-up's status (2: Ds singular)."
+correct_internalmodel_device!(b::BatchLinMPC, x̂0::Ptr{Float64}, y0m::Ptr{Float64}, d0::Ptr{Float64}, stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:mpcqp_im_correct_device, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}), b.h, x̂0, y0m, d0, stream))
+update_internalmodel_device!(b::BatchLinMPC, x̂0::Ptr{Float64}, u0::Ptr{Float64}, d0::Ptr{Float64}, stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:mpcqp_im_update_device, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}), b.h, x̂0, u0, d0, stream))
+function internalmodel_status(b::BatchLinMPC)
+    st = Vector{Cint}(undef, length(b.mpcs))
+    check(ccall((:mpcqp_im_status, lib), Cint, (Ptr{Cvoid}, Ptr{Cint}), b.h, st))
+    return st
+end
+
+# ------------------------------------------------------------------------------------------------
 # Batch of linear MovingHorizonEstimator objects (include/mpcqp_mhe.h; SURVEY 8 row f2).  The estimators keep
 # their Julia fields; preparestate! / updatestate! of the BATCH run on the device.  Call sequence = the one of
 # modelpredictivecontrol.jl_amd/mhe.py (BatchMHE), which the GPU tests drive.

@@ -35,6 +35,8 @@ STATUS_OPTIMAL, STATUS_ITERATION_LIMIT, STATUS_ERROR = 0, 1, 2
 GET_HESSIAN, GET_STEPRESP, GET_KMAT, GET_BVEC, GET_QTILDE, GET_FVEC, GET_AUDIT, GET_XHAT_MS, GET_MS_DEFECT = 1, 2, 3, 4, 5, 6, 7, 8, 9
 GET_KF_COV, GET_KF_GAIN = 10, 11
 GET_EXPLICIT_LAW = 12
+GET_IM_XS, GET_IM_YS, GET_IM_YHATS = 13, 14, 15
+IM_STATUS_OK, IM_STATUS_SINGULAR = 0, 2          # mpcqp_im_status
 EXPLICIT_LAW = 1       # bit of mpcqp_explicit_prepare's with_law
 SIM_FLAG_RY_PER_PERIOD, SIM_FLAG_NO_FUSE = 1, 2     # mpcqp_sim_io.flags
 SIM_PATH_PERIOD, SIM_PATH_FUSED = 0, 1    # mpcqp_sim_path
@@ -52,6 +54,7 @@ EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_cre
            "mpcqp_explicit_prepare", "mpcqp_explicit_status", "mpcqp_explicit_step", "mpcqp_explicit_step_device",
            "mpcqp_explicit_law", "mpcqp_explicit_law_device",
            "mpcqp_sim_set_plant", "mpcqp_sim", "mpcqp_sim_device", "mpcqp_sim_path",
+           "mpcqp_im_set", "mpcqp_im_status", "mpcqp_im_correct", "mpcqp_im_correct_device", "mpcqp_im_update", "mpcqp_im_update_device",
            "mpcqp_set_output_weight_blocks", "mpcqp_set_dense_weights", "mpcqp_set_custom_constraints", "mpcqp_set_custom_bounds",
            "mpcqp_set_flags", "mpcqp_set_iteration_limit", "mpcqp_set_transcription", "mpcqp_transcription_supported", "mpcqp_set_current_setpoint", "mpcqp_prepare", "mpcqp_kernel_kind", "mpcqp_lds_bytes", "mpcqp_row_groups", "mpcqp_step_consts_builds", "mpcqp_prebuild",
            "mpcqp_last_build_error", "mpcqp_multi_create", "mpcqp_multi_destroy", "mpcqp_multi_ndev",
@@ -224,6 +227,13 @@ def load_library(path: str | None = None):
         lib.mpcqp_sim_est_status.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         lib.mpcqp_est_initstate.argtypes = [C.c_void_p] * 6
         lib.mpcqp_est_initstate_device.argtypes = [C.c_void_p] * 7
+    if hasattr(lib, "mpcqp_im_set"):               # (InternalModel)
+        lib.mpcqp_im_set.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32]
+        lib.mpcqp_im_status.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mpcqp_im_correct.argtypes = [C.c_void_p] * 4
+        lib.mpcqp_im_correct_device.argtypes = [C.c_void_p] * 5
+        lib.mpcqp_im_update.argtypes = [C.c_void_p] * 4
+        lib.mpcqp_im_update_device.argtypes = [C.c_void_p] * 5
     lib.mpcqp_prepare.argtypes = [C.c_void_p]
     lib.mpcqp_kernel_kind.argtypes = [C.c_void_p]
     lib.mpcqp_lds_bytes.argtypes = [C.c_void_p]
@@ -600,7 +610,8 @@ class Handle:
                  GET_QTILDE: (self.B, self.nZ), GET_FVEC: (self.B, self.nY), GET_AUDIT: (self.B, 4),
                  GET_XHAT_MS: (self.B, self.Hp, self.nxhat), GET_MS_DEFECT: (self.B,),
                  GET_EXPLICIT_LAW: (self.B, 1 + self.nxhat + self.nu + self.ny + self.nd, self.nZ),
-                 GET_KF_COV: (self.B, self.nxhat, self.nxhat), GET_KF_GAIN: (self.B, getattr(self, "nym", 0), self.nxhat)}[which]
+                 GET_KF_COV: (self.B, self.nxhat, self.nxhat), GET_KF_GAIN: (self.B, getattr(self, "nym", 0), self.nxhat),
+                 GET_IM_XS: (self.B, getattr(self, "nxs", 0)), GET_IM_YS: (self.B, self.ny), GET_IM_YHATS: (self.B, self.nY)}[which]
         out = np.empty(shape)
         _chk(self.lib, self.lib.mpcqp_get(self.h, which, _ptr(out)))
         return out
@@ -613,6 +624,50 @@ class Handle:
 
     def last_step_ms(self):
         return self.lib.mpcqp_last_step_ms(self.h)
+
+    # -- InternalModel (csrc/im_bodies.h) ------------------------------------------------------
+    def im_set(self, stoch, i_ym):
+        """mpcqp_im_set: `stoch` None (the default stochastic model: the identity in all four matrices) or (As, Bs, Cs, Ds) in
+        ABI layout -- colmajor() of (B,nxs,nxs), (B,nxs,nym), (B,nym,nxs), (B,nym,nym); i_ym the measured rows of Ĉ."""
+        if not hasattr(self.lib, "mpcqp_im_set"):
+            raise NotImplementedError("this library has no mpcqp_im_set")
+        iy = np.ascontiguousarray(i_ym, dtype=np.int32)
+        if stoch is None:
+            nxs, arrs = int(iy.size), [None] * 4
+        else:
+            arrs = [None if a is None else _f64(a) for a in stoch]
+            nxs = int(arrs[0].shape[-1]) if arrs[0] is not None else 0
+        _chk(self.lib, self.lib.mpcqp_im_set(self.h, nxs, *[_ptr(a) for a in arrs], _ptr(iy), int(iy.size)))
+        self.nym, self.nxs = int(iy.size), nxs
+
+    def im_status(self):
+        """(B,) int32: 0 ready, 2 the member's Ds is singular (its stochastic part is off)."""
+        out = np.empty(self.B, np.int32)
+        _chk(self.lib, self.lib.mpcqp_im_status(self.h, _ptr(out)))
+        return out
+
+    def im_correct(self, xhat0, y0m, d0=None):
+        """ŷs, Ŷs and B + Ŷs from x̂0 = x̂d (B,nx) -- not changed -- and y0m (B,nym)."""
+        x, y, dd = _f64(xhat0), _f64(y0m), (None if d0 is None else _f64(d0))
+        _chk(self.lib, self.lib.mpcqp_im_correct(self.h, _ptr(x), _ptr(y), _ptr(dd)))
+
+    def im_update(self, xhat0, u0, d0=None):
+        """x̂d <- Â x̂d + B̂u u0 + B̂d d0 + (f̂op - x̂op) in place on the (B,nx) host array, x̂s <- Âs x̂s + B̂s ŷs on the device."""
+        assert xhat0.dtype == np.float64 and xhat0.flags.c_contiguous
+        u, dd = _f64(u0), (None if d0 is None else _f64(d0))
+        _chk(self.lib, self.lib.mpcqp_im_update(self.h, _ptr(xhat0), _ptr(u), _ptr(dd)))
+
+    def im_correct_device(self, xhat0, y0m, d0=0, stream=0):
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _chk(self.lib, self.lib.mpcqp_im_correct_device(self.h, v(xhat0), v(y0m), v(d0), v(stream)))
+
+    def im_update_device(self, xhat0, u0, d0=0, stream=0):
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _chk(self.lib, self.lib.mpcqp_im_update_device(self.h, v(xhat0), v(u0), v(d0), v(stream)))
+
+    def im_state(self):
+        """x̂s (B,nxs), ŷs (B,ny), Ŷs (B,nY) of the InternalModel."""
+        return self.get(GET_IM_XS), self.get(GET_IM_YS), self.get(GET_IM_YHATS)
 
     # -- SteadyKalmanFilter steps (SURVEY 8f-1) -----------------------------------------------
     def kf_set(self, Khat, i_ym):
@@ -962,8 +1017,18 @@ class BatchLinMPC:
         self.iters = np.zeros(B, np.int32)
 
     # -- model / weights ---------------------------------------------------------------------
-    def setmodel(self, Ahat, Bhu, Chat, Bhd=None, Dhd=None):
-        """`setmodel!` re-condensation path (src/controller/execute.jl:684-790): K1 (+K2)."""
+    def setmodel(self, Ahat, Bhu, Chat, Bhd=None, Dhd=None, *, xhop=None, fhop=None):
+        """`setmodel!` re-condensation path (src/controller/execute.jl:684-790): K1 (+K2).  `xhop` / `fhop`: new x̂op / f̂op; the
+        state of an attached Kalman filter or InternalModel keeps its engineering value (`estim.x̂0 .+= x̂op_old .- x̂op_new`).
+        An InternalModel keeps x̂s, ŷs and its stochastic model (setmodel_estimator!, internal_model.jl:241-257): the next
+        step uses the new model with the Ŷs of the last correction."""
+        if xhop is not None:
+            new = np.broadcast_to(np.asarray(xhop, float), (self.B, self.nxh)).copy()
+            if getattr(self, "mhe", None) is None and "_xhat0" in self.__dict__:
+                self.xhat0 = self.xhat0 + self.xhop - new
+            self.xhop = new
+        if fhop is not None:
+            self.fhop = np.broadcast_to(np.asarray(fhop, float), (self.B, self.nxh)).copy()
         dopv = self.fhop - self.xhop
         self._Ahat, self._Bhu = np.asarray(Ahat, float).copy(), np.asarray(Bhu, float).copy()
         self._Chat = np.asarray(Chat, float).copy()
@@ -1201,11 +1266,11 @@ class BatchLinMPC:
             if not np.array_equal(mine, its):
                 raise ValueError(f"the estimator's {name} must be the controller's")
         self.hd.mhe_attach(est.handle, i_ym)
-        self.i_ym, self.mhe, self.direct = i_ym, est, est.direct
+        self.i_ym, self.mhe, self.direct, self.internal = i_ym, est, est.direct, False
         self.kf_timevarying = self.kf_steady = False
         return self
 
-    def setestimator(self, Khat=None, i_ym=None, xhat0=None, *, covariances=None, steady=None, direct=None, mhe=None):
+    def setestimator(self, Khat=None, i_ym=None, xhat0=None, *, covariances=None, steady=None, direct=None, mhe=None, internal=None):
         """Attach a SteadyKalmanFilter: Khat (B,nx̂,nym) steady-state gain (see
         `steady_kalman_gain`), i_ym measured-output indices (default all).  The estimate x̂0
         (deviation, (B,nx̂)) is then carried by this object like `mpc.estim.x̂0`.
@@ -1232,10 +1297,17 @@ class BatchLinMPC:
         nu, nd, library and operating points (uop, yop[i_ym], dop, x̂op), nym = len(i_ym); the form is `est.direct` (a `direct=`
         that contradicts it is an error).  `est` is borrowed and shared: `preparestate`, `updatestate`, `setstate` and
         `setmodel` (the rows i_ym of Ĉ and D̂d) forward to it, `mpc.xhat0` is `est.x̂0`, `moveinput(None, …)` reads it,
-        `getinfo()["estim"]` is `est.getinfo()`, and `sim` / `hd.loop_device` run it on the device without a copy of x̂0."""
-        if (Khat is not None) + (covariances is not None) + (steady is not None) + (mhe is not None) > 1:
-            raise ValueError("give one of Khat (SteadyKalmanFilter), steady (SteadyKalmanFilter from Q̂ and R̂), covariances (KalmanFilter) "
-                             "or mhe (MovingHorizonEstimator)")
+        `getinfo()["estim"]` is `est.getinfo()`, and `sim` / `hd.loop_device` run it on the device without a copy of x̂0.
+
+        `internal=dict(stoch_ym=None | (As, Bs, Cs, Ds))` attaches the `InternalModel` (see `setinternalmodel`)."""
+        if (Khat is not None) + (covariances is not None) + (steady is not None) + (mhe is not None) + (internal is not None) > 1:
+            raise ValueError("give one of Khat (SteadyKalmanFilter), steady (SteadyKalmanFilter from Q̂ and R̂), covariances (KalmanFilter), "
+                             "mhe (MovingHorizonEstimator) or internal (InternalModel)")
+        if internal is not None:
+            if direct is not None and not direct:
+                raise ValueError("direct=False: the InternalModel is always in the filter form")
+            return self.setinternalmodel(**internal, i_ym=i_ym, xhat0=xhat0)
+        self.internal = False
         if mhe is not None:
             if xhat0 is not None:
                 raise ValueError("xhat0: the estimate is the MovingHorizonEstimator's own (est.setstate)")
@@ -1257,6 +1329,61 @@ class BatchLinMPC:
         self.hd.kf_set(colmajor(Khat), self.i_ym)
         self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
         return self
+
+    def setinternalmodel(self, stoch_ym=None, i_ym=None, xhat0=None):
+        """The `InternalModel` estimator (src/estimator/internal_model.jl): the state is the model's own (no augmentation, so
+        nx̂ = nx), and the mismatch between the measurements and the model's outputs drives a stochastic model on the
+        measured outputs, `stoch_ym=(As, Bs, Cs, Ds)` -- (nxs,nxs), (nxs,nym), (nym,nxs), (nym,nym), each shared or with a
+        leading batch axis; None: the identity in all four, one integrator-free pass-through per measured output, the
+        reference's default.  Its prediction Ŷs over the horizon is added to the controller's free response on the device:
+        `preparestate` computes ŷs and Ŷs, every `moveinput` that follows uses them in the objective and in the output bounds,
+        `updatestate` advances x̂d = x̂0 and x̂s.  `evaloutput`, `getinfo()["Ŷs"]` and `getinfo()["ŷ"]` include them.
+        Like the reference's constructor this raises ValueError for a model with an eigenvalue on or outside the unit circle,
+        for a `Ds` that is zero and for `Cs` / `Ds` whose row count is not nym.  Members whose `Ds` is singular are counted in
+        one RuntimeWarning; their stochastic part stays off (`getinfo()["im_status"]` 2).  Not available with custom linear
+        constraints, MultipleShooting or on `BatchExplicitMPC` (include/mpcqp.h)."""
+        B = self.B
+        i_ym = np.arange(self.ny) if i_ym is None else np.asarray(i_ym, int)
+        nym = len(i_ym)
+        if nym < 1 or i_ym.min() < 0 or i_ym.max() >= self.ny or len(set(i_ym.tolist())) != nym:
+            raise ValueError("i_ym: unique indices of measured outputs in 0 .. ny-1")
+        if np.any(np.abs(np.linalg.eigvals(self._Ahat)) >= 1.0):
+            raise ValueError("InternalModel does not support integrating or unstable model")
+        stoch = None
+        if stoch_ym is not None:
+            mats = [np.asarray(a, float) for a in stoch_ym]
+            if len(mats) != 4 or any(a.ndim not in (2, 3) for a in mats):
+                raise ValueError("stoch_ym: (As, Bs, Cs, Ds)")
+            mats = [np.broadcast_to(a, (B,) + a.shape[-2:]) for a in mats]
+            As, Bs, Cs, Ds = mats
+            nxs = As.shape[-1]
+            if Cs.shape[1] != nym or Ds.shape[1] != nym:
+                raise ValueError(f"Stochastic model output quantity ({Cs.shape[1]}) is different from measured output quantity ({nym})")
+            if nxs < 1 or As.shape != (B, nxs, nxs) or Bs.shape != (B, nxs, nym) or Cs.shape != (B, nym, nxs) or Ds.shape != (B, nym, nym):
+                raise ValueError("DimensionMismatch between As, Bs, Cs, Ds")
+            if np.any(np.all(Ds == 0, axis=(1, 2))):
+                raise ValueError("Stochastic model requires a nonzero direct transmission matrix D")
+            stoch = [colmajor(a) for a in mats]
+        self.hd.im_set(stoch, i_ym)
+        self.__dict__.pop("mhe", None)
+        self.i_ym, self.internal, self.direct, self._hd_direct = i_ym, True, True, True      # (mpcqp_im_set puts the handle in the filter form)
+        self.kf_timevarying = self.kf_steady = False
+        self.xhat0 = np.zeros((B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (B, self.nxh))).copy()
+        n = int(np.count_nonzero(self.hd.im_status()))
+        if n:
+            warnings.warn(f"InternalModel: Ds is singular, the stochastic part of the estimator is off ({n} of {B} estimators)", RuntimeWarning)
+        return self
+
+    def evaloutput(self, d=None):
+        """`evaloutput(estim, d)`: ŷ = Ĉ x̂0 + D̂d d0 + yop, + ŷs of the last `preparestate` behind an InternalModel."""
+        if not hasattr(self, "i_ym"):
+            raise ValueError("no estimator attached (setestimator)")
+        y = np.einsum("bij,bj->bi", self._Chat, self.xhat0) + self.yop
+        if self.nd > 0:
+            y = y + np.einsum("bij,bj->bi", self._Dhd, self._bc(d, self.nd, "d") - self.dop)
+        if getattr(self, "internal", False):
+            y = y + self.hd.get(GET_IM_YS)
+        return y
 
     def _set_direct(self, direct):
         """The form of the estimator about to be attached, settled before the estimator itself goes to the device.  The
@@ -1288,6 +1415,7 @@ class BatchLinMPC:
         self._set_direct(direct)
         self.hd.kf_set_covariances(Qhat, Rhat, P0, self.i_ym)
         self.__dict__.pop("mhe", None)
+        self.internal = False
         self._P0 = P0.copy()                        # P̂_0, for initstate (init_estimate_cov!)
         self.kf_timevarying, self.kf_steady = True, False
         self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
@@ -1302,6 +1430,7 @@ class BatchLinMPC:
         self._set_direct(direct)
         self.hd.kf_set_steady(Qhat, Rhat, self.i_ym)
         self.__dict__.pop("mhe", None)
+        self.internal = False
         self.kf_timevarying, self.kf_steady = False, True
         self._warn_steady()
         self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
@@ -1355,6 +1484,14 @@ class BatchLinMPC:
         them with ym=None) keep their x̂0.  Predictor form (direct=False): nothing to do, no device call."""
         if getattr(self, "mhe", None) is not None:      # preparestate!(estim::MovingHorizonEstimator): one solve (direct form)
             return self._mhe_period(self.mhe.preparestate(ym, d), self.direct)
+        if getattr(self, "internal", False):            # correct_estimate!(estim::InternalModel): ŷs and Ŷs, x̂0 stays
+            y0m = self._bc(ym, len(self.i_ym), "ym") - self.yop[:, self.i_ym]
+            n = int((~np.isfinite(y0m)).any(axis=1).sum())
+            if n:
+                warnings.warn(f"NaN values in the internal model measurements ym: assigning them ŷs=0 ({n} of {self.B} estimators)",
+                              RuntimeWarning)
+            self.hd.im_correct(self.xhat0, y0m, None if self.nd == 0 else self._bc(d, self.nd, "d") - self.dop)
+            return self.xhat0 + self.xhop
         if not getattr(self, "direct", True):
             return self.xhat0 + self.xhop
         y0m = self._y0m(ym)
@@ -1372,7 +1509,9 @@ class BatchLinMPC:
             return self._mhe_period(self.mhe.updatestate(u, ym, d), not self.direct)
         u0 = self._bc(u, self.nu, "u") - self.uop
         d0 = None if self.nd == 0 else self._bc(d, self.nd, "d") - self.dop
-        if getattr(self, "direct", True):
+        if getattr(self, "internal", False):
+            self.hd.im_update(self.xhat0, u0, d0)
+        elif getattr(self, "direct", True):
             self.hd.kf_predict(self.xhat0, u0, d0)
         else:
             self.hd.kf_update(self.xhat0, u0, self._y0m(ym), d0)
@@ -1423,7 +1562,9 @@ class BatchLinMPC:
         self.init_status = st
         n = int(np.count_nonzero(st))
         if n:
-            warnings.warn("initstate!: [I - Â; Ĉm] has no full column rank, the estimate x̂0 is left unchanged "
+            warnings.warn(("initstate!: I - Â or I - Âs is singular, x̂0 and x̂s are left unchanged " if getattr(self, "internal", False) else
+                           "initstate!: [I - Â; Ĉm] has no full column rank, the estimate x̂0 is left unchanged ")
+                          + 
                           f"({n} of {self.B} estimators)", RuntimeWarning)
         return self.xhat0 + self.xhop
 
@@ -1649,7 +1790,10 @@ class BatchLinMPC:
         if est is not None:
             self._warn_mhe(est_status, B * N, "estimator periods")
         nmiss = 0 if est is not None else int(np.isnan(rec["Y"][:, :, self.i_ym]).any(axis=2).sum())
-        if nmiss:     # kalman.jl:245-251
+        if nmiss and getattr(self, "internal", False):
+            warnings.warn(f"NaN values in the internal model measurements ym: assigning them ŷs=0 ({nmiss} of {B * N} estimator periods)",
+                          RuntimeWarning)
+        elif nmiss:   # kalman.jl:245-251
             warnings.warn("NaN values in the Kalman filter measurements ym: skipping correction step "
                           f"({nmiss} of {B * N} estimator periods)", RuntimeWarning)
         t = lambda k, op: rec[k].transpose(0, 2, 1) + op[:, :, None]
@@ -1725,6 +1869,10 @@ class BatchLinMPC:
         yk = np.einsum("bij,bj->bi", self._Chat, xhat0) + self.yop
         if nd > 0:
             yk = yk + np.einsum("bij,bj->bi", self._Dhd, d0)
+        if getattr(self, "internal", False):        # the Ŷs and ŷs of the last correction: what the step used (predictstoch!)
+            info["Ŷs"], info["im_status"] = self.hd.get(GET_IM_YHATS), self.hd.im_status()
+            info["x̂s"], info["ŷs"] = self.hd.get(GET_IM_XS), self.hd.get(GET_IM_YS)
+            yk = yk + info["ŷs"]
         info["ŷ"] = yk
         # x̂end = x̂0(k+Hp): the augmented model driven by the optimal inputs (predict!, transcription.jl:1136-1145)
         x = xhat0.copy()

@@ -13,6 +13,7 @@
 #include "../../include/mpcqp_mhe.h"
 #include "est_init_launch.h"
 #include "explicit_launch.h"
+#include "im_launch.h"
 #include "kf_cov_launch.h"
 #include "kf_dare_launch.h"
 #include "mpcqp_hostutil.h"
@@ -113,6 +114,13 @@ struct mpcqp_handle_s {
     DBuf sim_est;
     int sim_est_N = 0;
     DBuf ei_x, ei_u, ei_y, ei_d, ei_st;
+    // InternalModel (mpcqp_im_set): the stochastic model as given (im_As .. im_Ds), Âs and B̂s of the set-up, x̂s, ŷs, Ŷs, the
+    // B + Ŷs every step of the handle reads in place of Model::Bvec, z = Âs x̂s + B̂s ŷs of the last correction (next period's
+    // x̂s) and the set-up's status.  kf.i_ym / kf.nym hold the measured rows, have_kf is false and mhe null.
+    bool have_im = false;
+    bool in_multi = false;      // a shard of mpcqp_multi_create
+    int im_nxs = 0;
+    DBuf im_As, im_Bs, im_Cs, im_Ds, im_Ahs, im_Bhs, im_xs, im_ys, im_Yhs, im_Beff, im_z, im_st;
 };
 
 static int dev_alloc(mpcqp_handle h, DBuf& b, size_t bytes) {
@@ -324,6 +332,7 @@ int mpcqp_get_sizes(mpcqp_handle h, mpcqp_sizes* out) {
 }
 
 static int explicit_refresh(mpcqp_handle h, hipStream_t st);
+static int im_refresh(mpcqp_handle h, hipStream_t st);
 
 static bool terminal_on(const Dims& d) { return (d.gmask >> (2 * P_X)) & 3u; }
 
@@ -408,6 +417,8 @@ int mpcqp_set_model(mpcqp_handle h, const double* Ahat, const double* Bu, const 
     h->have_model = true;
     invalidate_stepc(h);
     rc = condense(h, h->stream, true);
+    if (rc) return rc;
+    rc = im_refresh(h, h->stream);              // (InternalModel: B_eff = the new B + the Ŷs of the last correction)
     if (rc) return rc;
     rc = explicit_refresh(h, h->stream);
     if (rc) return rc;
@@ -526,6 +537,7 @@ int mpcqp_set_custom_constraints(mpcqp_handle h, int nw, const double* Wy, const
     Dims& d = h->d;
     if (nw < 0) return MPCQP_ERR_ARG;
     if (nw > 0 && (!Wy || !Wu)) return MPCQP_ERR_NULL;
+    if (nw > 0 && h->have_im) return MPCQP_ERR_UNSUPPORTED;      // (the ŷ(k) term of the custom rows would need ŷs inside the kernel)
     ON_DEVICE(h);
     Model& m = h->m;
     d.nw = nw; d.nW = nw * (d.Hp + 1);
@@ -778,6 +790,7 @@ static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* l
 #endif
     // (refusals first: nothing is recorded on the stream for a step that does not run)
     if (uses_stage_kernel(h) && ms_unsupported(h)) return MPCQP_ERR_UNSUPPORTED;      // (the fused Kalman loop runs on the stage-structured kernel too since round 6)
+    if (h->have_im && (uses_stage_kernel(h) || d.nW > 0)) return MPCQP_ERR_UNSUPPORTED;  // (the stage kernel does not read B; custom rows need ŷs)
     // (the step constants are handle data like H~: built before the step's time starts)
     if (!uses_stage_kernel(h)) { int rc = ensure_stepc(h, st); if (rc) return rc; }
     HIPCHK(hipEventRecord(h->ev_s0, st));
@@ -814,7 +827,13 @@ static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* l
         HIPCHK(launch_ms_step(dm, mm, io, ms, st));
     } else {
         { int rc = ensure_hessian(h, st); if (rc) return rc; }      // (skipped while the problem did not fit the LDS: see hessian_valid)
-        HIPCHK(launch_step(d, h->m, io, st));
+        if (h->have_im) {       // InternalModel: the same kernels on B + Ŷs (k_im_correct keeps it current)
+            Model mm = h->m;
+            mm.Bvec = (double*)h->im_Beff.p;
+            HIPCHK(launch_step(d, mm, io, st));
+        } else {
+            HIPCHK(launch_step(d, h->m, io, st));
+        }
     }
     HIPCHK(hipEventRecord(h->ev_s1, st));
     h->step_timed = true;
@@ -826,6 +845,16 @@ int mpcqp_loop_device(mpcqp_handle h, double* xhat0, const double* y0m, const do
                       double* Ztilde, double* u0, int32_t* status, int32_t* iters, double* Yhat0,
                       void* stream) {
     if (!h || !y0m || !xhat0) return MPCQP_ERR_NULL;
+    if (h->have_im) {
+        // InternalModel: correct (ŷs, Ŷs, B + Ŷs), the step on x̂0 = x̂d, update (x̂d in place, x̂s), three calls on the caller's
+        // stream.  Refusals first: a step that does not run leaves the estimator alone
+        if (!lastu0 || !Ry || !Ztilde || !u0 || !status || (h->d.nd > 0 && (!d0 || !Dhat0))) return MPCQP_ERR_NULL;
+        if (!h->have_model || !h->have_weights) return MPCQP_ERR_ORDER;
+        if (uses_stage_kernel(h) || h->d.nW > 0) return MPCQP_ERR_UNSUPPORTED;
+        int rc = mpcqp_im_correct_device(h, xhat0, y0m, d0, stream);
+        if (!rc) rc = step_device_impl(h, xhat0, lastu0, Ry, Ru, d0, Dhat0, Ztilde, u0, status, iters, Yhat0, stream, nullptr, nullptr, 0);
+        return rc ? rc : mpcqp_im_update_device(h, xhat0, u0, d0, stream);
+    }
     if (h->mhe) {
         // a MovingHorizonEstimator behind the controller: preparestate!, the step on the estimator's own x̂0 (read in place),
         // updatestate!, three calls on the caller's stream.  Refusals first: a step that does not run leaves the windows alone
@@ -899,6 +928,7 @@ int mpcqp_recondense_device(mpcqp_handle h, void* stream) {
     if (!h->have_model || !h->have_weights) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     int rc = condense(h, (hipStream_t)stream, true);
+    if (!rc) rc = im_refresh(h, (hipStream_t)stream);
     return rc ? rc : explicit_refresh(h, (hipStream_t)stream);
 }
 
@@ -983,6 +1013,18 @@ int mpcqp_get(mpcqp_handle h, int which, double* out) {
         case MPCQP_GET_KF_GAIN:
             if (!h->have_kf) return MPCQP_ERR_ORDER;
             HIPCHK(hipMemcpy(out, h->kf_K.p, B * d.nxh * h->kf.nym * sizeof(double), hipMemcpyDeviceToHost));
+            return MPCQP_OK;
+        case MPCQP_GET_IM_XS:
+            if (!h->have_im) return MPCQP_ERR_ORDER;
+            HIPCHK(hipMemcpy(out, h->im_xs.p, B * h->im_nxs * sizeof(double), hipMemcpyDeviceToHost));
+            return MPCQP_OK;
+        case MPCQP_GET_IM_YS:
+            if (!h->have_im) return MPCQP_ERR_ORDER;
+            HIPCHK(hipMemcpy(out, h->im_ys.p, B * d.ny * sizeof(double), hipMemcpyDeviceToHost));
+            return MPCQP_OK;
+        case MPCQP_GET_IM_YHATS:
+            if (!h->have_im) return MPCQP_ERR_ORDER;
+            HIPCHK(hipMemcpy(out, h->im_Yhs.p, B * d.nY * sizeof(double), hipMemcpyDeviceToHost));
             return MPCQP_OK;
         case MPCQP_GET_EXPLICIT_LAW: {
             if (!h->ex_prepared || !h->ex_law) return MPCQP_ERR_ORDER;
@@ -1075,6 +1117,7 @@ static int explicit_current(mpcqp_handle h, hipStream_t st) { return h->ex_stale
 int mpcqp_explicit_prepare(mpcqp_handle h, int32_t with_law) {
     if (!h) return MPCQP_ERR_NULL;
     if (with_law & ~MPCQP_EXPLICIT_LAW) return MPCQP_ERR_ARG;
+    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;               // (the law has no Ŷs term)
     if (!h->have_model || !h->have_weights) return MPCQP_ERR_ORDER;
     if (explicit_constrained(h)) return MPCQP_ERR_ARG;          // "ExplicitMPC does not support constraints"
     const Dims& d = h->d;
@@ -1123,6 +1166,7 @@ int mpcqp_explicit_prepare(mpcqp_handle h, int32_t with_law) {
 
 int mpcqp_explicit_status(mpcqp_handle h, int32_t* out) {
     if (!h || !out) return MPCQP_ERR_NULL;
+    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;
     if (!h->ex_prepared || explicit_constrained(h)) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     { int rc = explicit_current(h, h->stream); if (rc) return rc; }
@@ -1138,6 +1182,7 @@ int mpcqp_explicit_step_device(mpcqp_handle h, const double* xhat0, const double
     if (!h || !xhat0 || !lastu0 || !Ry || !Ztilde || !u0 || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && (!d0 || !Dhat0)) return MPCQP_ERR_NULL;
+    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;
     if (!h->ex_prepared || explicit_constrained(h)) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
@@ -1165,6 +1210,7 @@ int mpcqp_explicit_law_device(mpcqp_handle h, const double* xhat0, const double*
     if (!h || !xhat0 || !lastu0 || !ry || !u0 || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;
     if (!h->ex_prepared || !h->ex_law || explicit_constrained(h)) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
@@ -1187,6 +1233,7 @@ int mpcqp_explicit_step(mpcqp_handle h, const double* xhat0, const double* lastu
     if (!h || !xhat0 || !lastu0 || !Ry || !Ztilde || !u0 || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && (!d0 || !Dhat0)) return MPCQP_ERR_NULL;
+    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;
     if (!h->ex_prepared || explicit_constrained(h)) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     const size_t B = d.B, sz = sizeof(double);
@@ -1220,6 +1267,7 @@ int mpcqp_explicit_law(mpcqp_handle h, const double* xhat0, const double* lastu0
     if (!h || !xhat0 || !lastu0 || !ry || !u0 || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;
     if (!h->ex_prepared || !h->ex_law || explicit_constrained(h)) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     const size_t B = d.B, sz = sizeof(double);
@@ -1261,6 +1309,7 @@ int mpcqp_kf_set(mpcqp_handle h, const double* Khat, const int32_t* i_ym, int32_
     h->kf.i_ym = (const int*)h->kf_iym.p;
     h->kf.nym = nym;
     h->have_kf = true;
+    h->have_im = false;
     h->mhe = nullptr;           // (a Kalman handle again)
     h->kf_tv = false;           // (back to the steady gain: the covariance kernel no longer runs)
     h->kf_steady = false;       // (a gain of the caller's: nothing to re-solve)
@@ -1315,6 +1364,7 @@ int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* R
     h->kf_NX = kf::kf_cov_columns_for(std::max(d.nxh, (int)nym));
     h->kf_waves = kf::kf_cov_waves_for(h->device, d.B, h->kf_NX);
     h->have_kf = true;
+    h->have_im = false;
     h->mhe = nullptr;
     h->kf_tv = true;
     h->kf_steady = false;
@@ -1375,6 +1425,7 @@ int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, 
     h->kf_NX = kf::kf_cov_columns_for(std::max(d.nxh, (int)nym));
     h->kf_dare_waves = kf::kf_dare_waves_for(h->device, d.B, h->kf_NX);
     h->have_kf = true;
+    h->have_im = false;
     h->mhe = nullptr;
     h->kf_tv = false;
     h->kf_steady = true;
@@ -1469,6 +1520,7 @@ int mpcqp_kf_predict_device(mpcqp_handle h, double* xhat0, const double* u0, con
 int mpcqp_kf_set_direct(mpcqp_handle h, int32_t direct) {
     if (!h) return MPCQP_ERR_NULL;
     if (direct != 0 && direct != 1) return MPCQP_ERR_ARG;
+    if (h->have_im && direct == 0) return MPCQP_ERR_ARG;        // (InternalModel: always the filter form)
     h->kf_direct = direct;
     return MPCQP_OK;
 }
@@ -1539,6 +1591,145 @@ int mpcqp_kf_predict(mpcqp_handle h, double* xhat0, const double* u0, const doub
     return kf_host(h, xhat0, u0, h ? (size_t)h->d.nu : 0, d0, false);
 }
 
+// ---- InternalModel (include/mpcqp.h; kernels: im_bodies.h) -------------------------------------------------------------------
+
+static void im_args(mpcqp_handle h, im::ImArgs& a) {
+    const Dims& d = h->d;
+    a.Ahat = h->m.Ahat; a.Bu = h->m.Bu; a.C = h->m.C; a.Bd = d.nd > 0 ? h->m.Bd : nullptr; a.Dd = d.nd > 0 ? h->m.Dd : nullptr;
+    a.dop = h->m.dop; a.Bvec = h->m.Bvec; a.i_ym = h->kf.i_ym;
+    a.B = d.B; a.nx = d.nxh; a.nu = d.nu; a.ny = d.ny; a.nd = d.nd; a.nym = h->kf.nym; a.nxs = h->im_nxs; a.Hp = d.Hp;
+    a.G = im::group_lanes(a.nx, a.nu, a.ny, a.nd, a.nxs);
+    a.As = (const double*)h->im_As.p; a.Bs = (const double*)h->im_Bs.p; a.Cs = (const double*)h->im_Cs.p; a.Ds = (const double*)h->im_Ds.p;
+    a.Ahs = (double*)h->im_Ahs.p; a.Bhs = (double*)h->im_Bhs.p;
+    a.xs = (double*)h->im_xs.p; a.ys = (double*)h->im_ys.p; a.Yhs = (double*)h->im_Yhs.p; a.Beff = (double*)h->im_Beff.p;
+    a.z = (double*)h->im_z.p; a.status = (int32_t*)h->im_st.p;
+}
+
+// B_eff = B + Ŷs after k_predmat wrote a new B (mpcqp_set_model, mpcqp_recondense_device)
+static int im_refresh(mpcqp_handle h, hipStream_t st) {
+    if (!h->have_im) return MPCQP_OK;
+    im::ImArgs a{};
+    im_args(h, a);
+    HIPCHK(im::launch_im(a, im::IM_BEFF, st));
+    return MPCQP_OK;
+}
+
+int mpcqp_im_set(mpcqp_handle h, int32_t nxs, const double* As, const double* Bs, const double* Cs, const double* Ds,
+                 const int32_t* i_ym, int32_t nym) {
+    if (!h || !i_ym) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    if (nym < 1 || nym > d.ny) return MPCQP_ERR_DIMS;
+    const int given = (As != nullptr) + (Bs != nullptr) + (Cs != nullptr) + (Ds != nullptr);
+    if (given != 0 && given != 4) return MPCQP_ERR_ARG;
+    if (given == 0) nxs = nym;      // the default: the identity in all four
+    if (nxs < 1) return MPCQP_ERR_ARG;
+    for (int i = 0; i < nym; ++i) {
+        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;     // validate_ym, construct.jl:190-196
+        for (int j = 0; j < i; ++j)
+            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
+    }
+    if (!im::im_available() || !im::dims_ok(d.nxh, d.nu, d.ny, d.nd, nym, nxs)) return MPCQP_ERR_UNSUPPORTED;
+    if (h->in_multi || h->ex_prepared || d.nW > 0 || uses_stage_kernel(h)) return MPCQP_ERR_UNSUPPORTED;
+    ON_DEVICE(h);
+    const size_t B = d.B, sz = sizeof(double), n = (size_t)nxs, m = (size_t)nym;
+    std::vector<double> eye;
+    if (given == 0) {
+        eye.assign(B * m * m, 0.0);
+        for (size_t b = 0; b < B; ++b)
+            for (size_t i = 0; i < m; ++i) eye[b * m * m + i * m + i] = 1.0;
+        As = Bs = Cs = Ds = eye.data();
+    }
+    // (a step enqueued on a caller's stream may still read x̂s, Ŷs or B_eff: upload() orders the copies behind it, and the
+    //  set-up kernel follows them on the same stream)
+    int rc = upload(h, h->im_As, As, B * n * n * sz);
+    if (!rc) rc = upload(h, h->im_Bs, Bs, B * n * m * sz);
+    if (!rc) rc = upload(h, h->im_Cs, Cs, B * m * n * sz);
+    if (!rc) rc = upload(h, h->im_Ds, Ds, B * m * m * sz);
+    if (!rc) rc = upload(h, h->kf_iym, i_ym, m * sizeof(int32_t));
+    if (!rc) rc = dev_alloc(h, h->im_Ahs, B * n * n * sz);
+    if (!rc) rc = dev_alloc(h, h->im_Bhs, B * n * m * sz);
+    if (!rc) rc = dev_alloc(h, h->im_xs, B * n * sz);
+    if (!rc) rc = dev_alloc(h, h->im_z, B * n * sz);
+    if (!rc) rc = dev_alloc(h, h->im_ys, B * d.ny * sz);
+    if (!rc) rc = dev_alloc(h, h->im_Yhs, B * d.nY * sz);
+    if (!rc) rc = dev_alloc(h, h->im_Beff, B * d.nY * sz);
+    if (!rc) rc = dev_alloc(h, h->im_st, B * sizeof(int32_t));
+    if (rc) { h->have_im = false; return rc; }
+    h->kf.Khat = nullptr;
+    h->kf.i_ym = (const int*)h->kf_iym.p;
+    h->kf.nym = nym;
+    h->im_nxs = nxs;
+    h->have_kf = h->kf_tv = h->kf_steady = false;       // (replaces a Kalman filter or an attached MovingHorizonEstimator)
+    h->mhe = nullptr;
+    h->kf_direct = 1;
+    h->have_im = true;
+    im::ImArgs a{};
+    im_args(h, a);
+    const hipError_t e = im::launch_im(a, im::IM_SETUP, h->stream);
+    if (e != hipSuccess) { h->have_im = false; HIPCHK(e); }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
+int mpcqp_im_status(mpcqp_handle h, int32_t* out) {
+    if (!h || !out) return MPCQP_ERR_NULL;
+    if (!h->have_im) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, h->im_st.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MPCQP_OK;
+}
+
+int mpcqp_im_correct_device(mpcqp_handle h, const double* xhat0, const double* y0m, const double* d0, void* stream) {
+    if (!h || !xhat0 || !y0m) return MPCQP_ERR_NULL;
+    if (h->d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    if (!h->have_model || !h->have_im) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    im::ImArgs a{};
+    im_args(h, a);
+    a.xhat0 = const_cast<double*>(xhat0); a.y0m = y0m; a.d0 = h->d.nd > 0 ? d0 : nullptr;
+    HIPCHK(im::launch_im(a, im::IM_CORRECT, (hipStream_t)stream));
+    return MPCQP_OK;
+}
+
+int mpcqp_im_update_device(mpcqp_handle h, double* xhat0, const double* u0, const double* d0, void* stream) {
+    if (!h || !xhat0 || !u0) return MPCQP_ERR_NULL;
+    if (h->d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    if (!h->have_model || !h->have_im) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    im::ImArgs a{};
+    im_args(h, a);
+    a.xhat0 = xhat0; a.u0 = u0; a.d0 = h->d.nd > 0 ? d0 : nullptr;
+    HIPCHK(im::launch_im(a, im::IM_UPDATE, (hipStream_t)stream));
+    return MPCQP_OK;
+}
+
+static int im_host(mpcqp_handle h, double* xhat0, const double* v, const double* d0, bool correct) {
+    if (!h || !xhat0 || !v) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    if (!h->have_model || !h->have_im) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    const size_t B = d.B, sz = sizeof(double);
+    int rc = upload(h, h->kf_x, xhat0, B * d.nxh * sz);
+    if (!rc) rc = upload(h, correct ? h->kf_y : h->kf_u, v, B * (size_t)(correct ? h->kf.nym : d.nu) * sz);
+    if (!rc && d.nd > 0) rc = upload(h, h->kf_d, d0, B * d.nd * sz);
+    if (rc) return rc;
+    const double* dd = d.nd > 0 ? (const double*)h->kf_d.p : nullptr;
+    rc = correct ? mpcqp_im_correct_device(h, (const double*)h->kf_x.p, (const double*)h->kf_y.p, dd, h->stream)
+                 : mpcqp_im_update_device(h, (double*)h->kf_x.p, (const double*)h->kf_u.p, dd, h->stream);
+    if (rc) return rc;
+    if (!correct) HIPCHK(hipMemcpyAsync(xhat0, h->kf_x.p, B * d.nxh * sz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
+int mpcqp_im_correct(mpcqp_handle h, const double* xhat0, const double* y0m, const double* d0) {
+    return im_host(h, const_cast<double*>(xhat0), y0m, d0, true);
+}
+
+int mpcqp_im_update(mpcqp_handle h, double* xhat0, const double* u0, const double* d0) { return im_host(h, xhat0, u0, d0, false); }
+
 // ---- LinMPC(MovingHorizonEstimator): attachment, and the estimator half of initstate! (include/mpcqp_mhe.h) ------------------
 
 int mpcqp_mhe_attach(mpcqp_handle h, mpcqp_mhe e, const int32_t* i_ym, int32_t nym) {
@@ -1564,6 +1755,7 @@ int mpcqp_mhe_attach(mpcqp_handle h, mpcqp_mhe e, const int32_t* i_ym, int32_t n
     h->kf.i_ym = (const int*)h->kf_iym.p;
     h->kf.nym = nym;
     h->have_kf = h->kf_tv = h->kf_steady = false;       // (the attachment replaces a Kalman filter)
+    h->have_im = false;
     h->mhe = e;
     return MPCQP_OK;
 }
@@ -1573,6 +1765,15 @@ int mpcqp_est_initstate_device(mpcqp_handle h, double* xhat0, const double* u0, 
     if (!h || !xhat0 || !u0 || !y0m || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
+    if (h->have_im) {           // init_estimate! of the InternalModel: x̂d, ŷs and x̂s (k_im_init)
+        if (!h->have_model) return MPCQP_ERR_ORDER;
+        ON_DEVICE(h);
+        im::ImArgs a{};
+        im_args(h, a);
+        a.u0 = u0; a.y0m = y0m; a.d0 = d.nd > 0 ? d0 : nullptr; a.xhat0 = xhat0; a.init_status = status;
+        HIPCHK(im::launch_im(a, im::IM_INIT, (hipStream_t)stream));
+        return MPCQP_OK;
+    }
     if (!(h->have_kf || h->mhe) || !h->have_model) return MPCQP_ERR_ORDER;
     if (std::max(d.nxh, h->kf.nym) > est::EST_INIT_NMAX || !est::est_init_available()) return MPCQP_ERR_UNSUPPORTED;
     ON_DEVICE(h);
@@ -1589,7 +1790,7 @@ int mpcqp_est_initstate(mpcqp_handle h, double* xhat0, const double* u0, const d
     if (!h || !xhat0 || !u0 || !y0m || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
-    if (!(h->have_kf || h->mhe) || !h->have_model) return MPCQP_ERR_ORDER;
+    if (!(h->have_kf || h->mhe || h->have_im) || !h->have_model) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     const size_t B = d.B, sz = sizeof(double);
     int rc = upload(h, h->ei_x, xhat0, B * d.nxh * sz);
@@ -1668,7 +1869,8 @@ static int sim_check(mpcqp_handle h, const mpcqp_sim_io* io) {
     if (!h || !io) return MPCQP_ERR_NULL;
     if (io->N <= 0 || (io->flags & ~(MPCQP_SIM_FLAG_RY_PER_PERIOD | MPCQP_SIM_FLAG_NO_FUSE))) return MPCQP_ERR_ARG;
     const int ctrl = sim_controller(h, io);
-    if (!h->have_plant || !(h->have_kf || h->mhe) || ctrl == SIM_CTRL_NONE) return MPCQP_ERR_ORDER;
+    if (!h->have_plant || !(h->have_kf || h->mhe || h->have_im) || ctrl == SIM_CTRL_NONE) return MPCQP_ERR_ORDER;
+    if (h->have_im && (ctrl != SIM_CTRL_STEP || uses_stage_kernel(h) || h->d.nW > 0)) return MPCQP_ERR_UNSUPPORTED;
     if (!io->ry || !io->x0 || !io->xhat0 || !io->lastu0 || (h->d.nd > 0 && !io->d)) return MPCQP_ERR_NULL;
     if (!io->Ztilde && ctrl != SIM_CTRL_EXPLICIT_LAW) return MPCQP_ERR_NULL;
     if ((io->sigma_u && !io->w_u) || (io->sigma_y && !io->w_y) || (io->sigma_x && !io->w_x) ||
@@ -1715,6 +1917,7 @@ int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io_in, void* stream) {
     a.Bd = h->sp_has_Bd ? (const double*)h->sp_Bd.p : nullptr; a.Dd = h->sp_has_Dd ? (const double*)h->sp_Dd.p : nullptr;
     a.fx = h->sp_has_fx ? (const double*)h->sp_fx.p : nullptr;
     a.Chat = h->m.C; a.Dhd = d.nd > 0 ? h->m.Dd : nullptr; a.i_ym = h->kf.i_ym;
+    a.yhs = h->have_im ? (const double*)h->im_ys.p : nullptr;       // evaloutput of the InternalModel: + ŷs
     a.B = d.B; a.nxp = h->sim_nxp; a.nu = d.nu; a.ny = d.ny; a.nd = d.nd; a.nym = h->kf.nym; a.nxh = d.nxh; a.Hp = d.Hp; a.N = N;
     a.G = sim::group_lanes(a.nxp, a.nu, a.ny, a.nd, a.nym);
     a.ry = io->ry; a.d = io->d; a.ry_per_period = per_period ? 1 : 0;
@@ -1757,6 +1960,7 @@ int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io_in, void* stream) {
     HIPCHK(plant(-1, -1, 0));
     for (int i = 0; i < N; ++i) {
         if (est) { rc = mpcqp_mhe_prepare_stream(est, y0m, d0, stream); if (rc) return rc; }      // (predictor form: nothing)
+        else if (h->have_im) { rc = mpcqp_im_correct_device(h, io->xhat0, y0m, d0, stream); if (rc) return rc; }
         else if (h->kf_direct) { rc = mpcqp_kf_correct_device(h, io->xhat0, y0m, d0, stream); if (rc) return rc; }
         if (io->Xhat || io->Yhat) HIPCHK(plant(i, -1, -1));
         switch (ctrl) {
@@ -1775,6 +1979,9 @@ int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io_in, void* stream) {
             if (rc) return rc;
             // the estimator's status of this period (the solve of preparestate! or, predictor form, of updatestate!)
             HIPCHK(hipMemcpyAsync((int32_t*)h->sim_est.p + (size_t)i * B, est_st, B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        } else if (h->have_im) {
+            rc = mpcqp_im_update_device(h, io->xhat0, u0, d0, stream);
+            if (rc) return rc;
         } else {
             rc = h->kf_direct ? mpcqp_kf_predict_device(h, io->xhat0, u0, d0, stream)
                               : mpcqp_kf_update_device(h, io->xhat0, u0, y0m, d0, stream);
@@ -2092,6 +2299,7 @@ int mpcqp_multi_create(const mpcqp_dims* in, const int32_t* device_ids, int32_t 
         mpcqp_handle hg = nullptr;
         const int rc = mpcqp_create(&dg, &hg);
         if (rc) { mpcqp_multi_destroy(mh); return rc; }
+        hg->in_multi = true;
         mh->h.push_back(hg);
         mh->off.push_back(o);
         mh->cnt.push_back(dg.batch);

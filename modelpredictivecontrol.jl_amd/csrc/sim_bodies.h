@@ -35,6 +35,7 @@ MPCQP_HD void sim_plant_body(W& w, const PlantArgs& a, int wave, double* sm) {
                 for (int j = 0; j < a.nxh; ++j) y += a.Chat[(b * a.nxh + j) * ny + r] * xh[j];
                 if (a.Dhd)
                     for (int j = 0; j < nd; ++j) y += a.Dhd[(b * nd + j) * ny + r] * a.d0[b * nd + j];
+                if (a.yhs) y += a.yhs[b * ny + r];
                 a.Yhat[(b * N + i) * ny + r] = y;
             }
         }

@@ -40,6 +40,7 @@ struct PlantArgs {
     double *d0, *y0m, *ry_cur, *Dhat0;               // per-period buffers: [B][nd], [B][nym], [B][ny] or null, [B][Hp][nd] or null
     double *Y, *X, *D, *Xhat, *Yhat, *U, *Ud;
     int32_t* status;                                 // [B][N] or null
+    const double* yhs;                               // [B][ny] or null: added to Ŷ (i_est), the ŷs of an InternalModel
 };
 
 inline int group_lanes(int nxp, int nu, int ny, int nd, int nym) {
