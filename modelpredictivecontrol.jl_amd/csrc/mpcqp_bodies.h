@@ -933,28 +933,47 @@ struct Qp {
     // ow: P is OVERWRITTEN with (Hg ? H̃ : 0) + scale * E'DE on the whole stored triangle (Hg == nullptr: the weights of H̃
     // ride in dd, Step::fold_H)
     // PH: P is Phi of a kernel with the column-block-major layout (phi_layout(); Hg stays pk())
-    template <bool PH = false>
+    // MK: the K steps whose four row factors (and ϵ-row entries) are all zero are skipped (EtDE_share_; the polish, whose row
+    //     factors are rho on the working set and exactly 0 elsewhere).  One wavefront only: a team's helpers run every K step.
+    template <bool PH = false, bool MK = false>
     __device__ __forceinline__ int EtDE_add_mfma(const double* dd, double* P, double scale, const double* tb,
                                                  const double* Hg = nullptr, bool ow = false) {
         // (a team of wavefronts splits the passes over the tile rows: W::NTEAM, mpcqp_devwave.h)
         if constexpr (W::NTEAM > 1) { static_assert(W::WV == 0, MPCQP_POST_WV0); w.post(TJ_ETDE, (int)(dd - sm), (int)(P - sm), tb ? (int)(tb - sm) : 0, (ow ? 1 : 0) | (Hg ? 2 : 0) | (tb ? 4 : 0), scale); }
-        const int e = EtDE_share<PH>(dd, P, scale, tb ? tb : dd, Hg, ow, tb != nullptr);
+        const int e = EtDE_share<PH, MK && W::NTEAM == 1>(dd, P, scale, tb ? tb : dd, Hg, ow, tb != nullptr);
         if constexpr (W::NTEAM > 1) w.join();
         return e;
     }
     // (a forwarding layer of its own: merged into EtDE_share_, the compiler schedules the E'DE assembly differently)
-    template <bool PH = false>
+    template <bool PH = false, bool MK = false>
     __device__ __forceinline__ int EtDE_share(const double* dd, double* P, double scale, const double* tb, const double* Hg, bool ow, bool has_tb) {
-        return EtDE_share_<PH>(dd, P, scale, tb, Hg, ow, has_tb);
+        return EtDE_share_<PH, MK>(dd, P, scale, tb, Hg, ow, has_tb);
     }
     // (tb: a pointer into LDS also when there is no ϵ row to ride -- has_tb says so: a select with nullptr makes the pointer generic)
-    template <bool PH>
+    template <bool PH, bool MK = false>
     __device__ __forceinline__ int EtDE_share_(const double* dd, double* P, double scale, const double* tb, const double* Hg, bool ow, bool has_tb) {
         static_assert(!PH || phi_layout<W, DM>(), "column-block-major Phi outside its kernels");
         ow = ow || Hg != nullptr;
         constexpr int NU = DM::nu, NY = DM::ny, NDU = DM::nDU, NYR = DM::nY, SP = DM::sp, RS = DM::rs;
         constexpr int NT = (NDU + 15) / 16, NK = (NYR + 3) / 4;
         const int li = w.lane & 15, lk = w.lane >> 4;
+        // MK: lane kk looks at the four rows of K step kk (rows 4 kk .. 4 kk + 3 of E): a non-zero row factor or ϵ-row entry
+        // keeps the step in (NaN != 0: so does a NaN).  A ballot makes that a wave-uniform mask in scalar registers, and every
+        // test of it is a scalar branch around a whole K step -- no row-factor load, no product, no matrix-core instruction.
+        // More than 64 K steps: no mask, every step runs.
+        // (One ballot per pass, over the K steps from the pass's first on: with ONE mask for all passes the compiler keeps the
+        //  outcome of every test of a later pass as a lane mask of its own across the earlier ones -- 22 scalar register pairs
+        //  in k_step_s<C3>, paid for with scalar spills inside the interior-point loop.  Tested 32 bits at a time: one
+        //  s_bitcmp1_b32 per K step.)
+        constexpr bool MSK = MK && NK <= WAVE;
+        bool knz = false;
+        if constexpr (MSK) {
+            MPCQP_UNROLL
+            for (int u = 0; u < 4; ++u) {
+                const int r = 4 * w.lane + u, rr = r < NYR ? r : 0;
+                knz = knz || (r < NYR && (dd[rr] != 0.0 || (has_tb && tb[rr] != 0.0)));
+            }
+        }
         // the four K rows of an aligned step in the order 0,2,1,3 (see StaticDims::rs); any order works,
         // A and B operands use the same
         const int lkp = (NY % 4 == 0) ? (((lk & 1) << 1) | (lk >> 1)) : lk;
@@ -1079,6 +1098,15 @@ struct Qp {
             };
             const int kB = (I1 > I0) ? kfirst(I1) : NK;               // second row of the pass joins here
             const int kA = kfirst(I0) < kB ? kfirst(I0) : kB;          // (an earlier start only adds zeros)
+            // (MSK) the K steps of this pass that stay in: bit kk of klo / khi (K step kk, kk - 32)
+            unsigned klo = ~0u, khi = ~0u;
+            if constexpr (MSK) {
+                const int k0 = VREG ? ((DJ * I0 < NK) ? DJ * I0 : NK) : kA;     // the pass's first K step
+                const unsigned long long km = __builtin_amdgcn_ballot_w64(knz && w.lane >= k0);
+                klo = (unsigned)km;
+                khi = (unsigned)(km >> 32);
+            }
+            auto kon = [&](int kk) { return !MSK || (((kk < 32 ? klo : khi) >> (kk & 31)) & 1u) != 0; };
             // One K step: operands straight from the Σ table.  A lane whose block column has not
             // started at step t reads the zero slot (no select on the value).  With ny a multiple
             // of 4 the step t of the four K rows is wave-uniform and every row exists.
@@ -1138,6 +1166,28 @@ struct Qp {
                         if constexpr (EP) { if (erow) tbb[buf][u] = tbl[4 * kk]; }
                     }
                 };
+                if constexpr (MSK) {
+                    // K steps of the mask only, each on its own (few are left: nothing to pipeline); H̃ is requested in front
+                    // of them -- the double buffer of row factors is not live here
+                    if (Hg) hload();
+                    MPCQP_UNROLL
+                    for (int kk = kA_; kk < NK; ++kk) {
+                        if (!kon(kk)) continue;
+                        const double dv = ddl[4 * kk];
+                        double tbv = 0.0;
+                        if constexpr (EP) { if (erow) tbv = tbl[4 * kk]; }
+                        MPCQP_UNROLL
+                        for (int I = I0; I <= I1; ++I) {
+                            if (I > I0 && kk < kB_) continue;
+                            const bool eI = erow && I == IE;
+                            double ad = V[kk - DJ * I] * dv;
+                            if constexpr (EP) { if (eI && li == LE) ad = tbv; }
+                            MPCQP_UNROLL
+                            for (int J = 0; J <= I; ++J)
+                                acc[I - I0][J] = __builtin_amdgcn_mfma_f64_16x16x4f64(ad, V[kk - DJ * J], acc[I - I0][J], 0, 0, 0);
+                        }
+                    }
+                } else {
                 ldc(kA_, 0);
                 MPCQP_UNROLL
                 for (int c0 = kA_; c0 < NK; c0 += CH) {
@@ -1161,15 +1211,18 @@ struct Qp {
                     }
                     MPCQP_SCHED_FENCE();
                 }
+                }
             } else {
             // (the request one step past the end reads whatever follows in LDS and is never used)
-            constexpr bool PIPE = (NY % 4 == 0) && DM::zpad > 0;
+            // (MSK: a K step of the mask requests its own operands -- no request ahead across skipped steps)
+            constexpr bool PIPE = (NY % 4 == 0) && DM::zpad > 0 && !MSK;
             Ops cur, nxt;
             if (PIPE) kload(kA, cur);
             // (one-row passes run kA .. NK in the first loop; with LATEH it stops three quarters of the way for the H̃ requests)
             const int kB1 = (LATEH && I1 == I0) ? kA + (3 * (kB - kA)) / 4 : kB;
             MPCQP_PRAGMA(unroll MPCQP_ETDE_UNROLL)
             for (int kk = kA; kk < kB1; ++kk) {
+                if (!kon(kk)) continue;
                 if (PIPE) { kload(kk + 1, nxt); MPCQP_SCHED_FENCE(); kcomp(cur, true, false); MPCQP_SCHED_FENCE(); cur = nxt; }
                 else { kload(kk, cur); kcomp(cur, true, false); }
             }
@@ -1178,6 +1231,7 @@ struct Qp {
                 MPCQP_SCHED_FENCE();
                 MPCQP_PRAGMA(unroll MPCQP_ETDE_UNROLL)
                 for (int kk = kB1; kk < kB; ++kk) {
+                    if (!kon(kk)) continue;
                     if (PIPE) { kload(kk + 1, nxt); MPCQP_SCHED_FENCE(); kcomp(cur, true, false); MPCQP_SCHED_FENCE(); cur = nxt; }
                     else { kload(kk, cur); kcomp(cur, true, false); }
                 }
@@ -1186,12 +1240,13 @@ struct Qp {
                 if (LATEH && Hg) hload();
                 MPCQP_PRAGMA(unroll MPCQP_ETDE_UNROLL)
                 for (int kk = kB; kk < NK; ++kk) {
+                    if (!kon(kk)) continue;
                     if (PIPE) { kload(kk + 1, nxt); MPCQP_SCHED_FENCE(); kcomp(cur, true, true); MPCQP_SCHED_FENCE(); cur = nxt; }
                     else { kload(kk, cur); kcomp(cur, true, true); }
                 }
             }
             }
-            if (Hg && VREG) hload();
+            if (Hg && VREG && !MSK) hload();
             entry_base();
             if (ow) {
                 // plain stores of H̃ + scale acc (or scale acc alone) on the stored triangle
@@ -1253,11 +1308,11 @@ struct Qp {
     // P[pk(i,i')] += scale * sum_r E[r,i] dd[r] E[r,i']   (i >= i' < nDU).  When `tb` is given
     // and the matrix-core path runs, the ϵ row P[pk(nDU, i')] += sum_r tb[r] E[r,i'] is added for the
     // rows of the steps t >= the returned value; the caller adds the rest (Et_apply_add; -1: all of it).
-    template <bool PH = false>
+    template <bool PH = false, bool MK = false>
     MPCQP_HD int EtDE_add(const double* dd, double* P, double scale = 1.0, const double* tb = nullptr,
                           const double* Hg = nullptr, bool ow = false) {
 #if defined(__HIP_DEVICE_COMPILE__)
-        if constexpr (DM::is_static) return EtDE_add_mfma<PH>(dd, P, scale, tb, Hg, ow);
+        if constexpr (DM::is_static) return EtDE_add_mfma<PH, MK>(dd, P, scale, tb, Hg, ow);
 #endif
         // Strips of four: the packed layout (pk) stores row i as (i/4 + 1) aligned chunks of four
         // columns, chunk s of the whole triangle at P[4s..4s+3].  A lane takes a strip (i, ip0..ip0+3):
@@ -2617,17 +2672,22 @@ struct Step {
     }
 
     // ---- Phi (+)= G' diag(dd) G, dd(Row&) evaluated on finite rows (see phi_direct) ---------------
-    template <class Fn>
+    // POL (the polish, whose dd is rho on the working set and exactly 0 on every other row), where the matrix-core pass
+    // writes the whole triangle: Phi = H̃ + rho G_A'G_A with H̃ as K2 left it in global memory (Model::Hpk) -- the weights of H̃
+    // stay out of the row factors (fold_H makes them 2 M_r + dd_r: a full E'DE that recomputes the constant 2 E'ME), and
+    // the pass skips the K steps whose row factors are all zero (EtDE_share_, MK).  Elsewhere POL changes nothing.
+    template <bool POL = false, class Fn>
     MPCQP_HD void add_GtDG(Fn dd) {
         MPCQP_TIC();
         const int nu = d.nu, nDU = d.nDU, nZ = d.nZ;
+        const bool fold_here = fold_H && !(POL && etde_overwrites());      // (this assembly's view of it)
         double ee = 0.0;
         for_pairs([&](int p, int k, Row* r0, Row* r1) {
             double dmin = 0.0, dmax = 0.0, cmin = 0.0, cmax = 0.0;
             if (r0 && fin(*r0)) { dmin = dd(*r0); cmin = r0->cs; }
             if (r1 && fin(*r1)) { dmax = dd(*r1); cmax = r1->cs; }
             double hw = 0.0;        // H̃'s own term of this primitive (fold_H)
-            if (fold_H) {
+            if (fold_here) {
                 if (p == P_Y) hw = hwy_cached() ? hwy(k) : (k < d.nY ? 2.0 * m.Mdiag[(size_t)b * d.nY + k] : 0.0);
                 else if (p == P_U) hw = H2L(k);
             }
@@ -2639,7 +2699,7 @@ struct Step {
         });
         ee = w.sum(ee);
         w.sync();
-        if (fold_H && !etde_overwrites()) {      // (scalar E'DE adds in place: start from zero instead of from H̃)
+        if (fold_here && !etde_overwrites()) {      // (scalar E'DE adds in place: start from zero instead of from H̃)
             for (int i = w.lane; i < d.npk; i += WAVE) Phi[i] = 0.0;
             w.sync();
         }
@@ -2655,8 +2715,8 @@ struct Step {
         int eps_t0 = -1;          // first step whose Ŷ rows the matrix-core path put into the ϵ row
         if (qp.pair_on(P_Y)) {
             MPCQP_TIC();
-            eps_t0 = qp.template EtDE_add<PHL>(sm + c.tA[P_Y], Phi, 1.0, d.neps ? sm + c.tB[P_Y] : nullptr,
-                                 (phi_direct() && !fold_H) ? m.Hpk + (size_t)b * d.npk : nullptr, fold_H && etde_overwrites());
+            eps_t0 = qp.template EtDE_add<PHL, POL>(sm + c.tA[P_Y], Phi, 1.0, d.neps ? sm + c.tB[P_Y] : nullptr,
+                                 (phi_direct() && !fold_here) ? m.Hpk + (size_t)b * d.npk : nullptr, fold_here && etde_overwrites());
             w.sync();      // the MFMA write-back uses its own entry->lane map
             MPCQP_TOC(4);
         }
@@ -2726,7 +2786,7 @@ struct Step {
             if (qp.pair_on(P_BOX)) acc += sm[c.tA[P_BOX] + k];
             if (k < nDU && qp.pair_on(P_DU)) acc += sm[c.tA[P_DU] + k];
             if (k == nZ - 1 && d.neps) acc += ee;
-            if (fold_H) acc += one_row_per_lane<DM>() ? h2n_ : H2N_load(k);
+            if (fold_here) acc += one_row_per_lane<DM>() ? h2n_ : H2N_load(k);
             Phi[ix(k, k)] += acc;
         }
         // ϵ row: Phi[eps, k] += sum_pairs L_P' tB     (staged in dz, which is free here)
@@ -3803,6 +3863,7 @@ struct Step {
     // Measured (C port, 65536 C3 instances): mean 12.4 instead of 13.5 factorisations including the
     // polish's own, worst error against the certified optimum 6e-9 (1e-8 without).
     MPCQP_HD bool polish(int& nfact) {
+        MPCQP_MTIC();                             // (scripts/isa_phase_table.py: the polish has a table of its own)
         const int n = d.nZ;
         const double rho = 1e10;
         double zkeep = 0.0;                       // compile-time dims: nZ <= 64, one entry per lane
@@ -3821,7 +3882,7 @@ struct Step {
         for (int fact = 0; fact < MPCQP_POLISH_FACTS && !ok; ++fact) {
             ++nfact;
             if (!phi_direct()) load_H();
-            add_GtDG([&](Row& r) { return rho * r.rp; });
+            add_GtDG<true>([&](Row& r) { return rho * r.rp; });
             cholesky();
             if (chol_broke) break;
             double rpa = 0.0;
@@ -3940,6 +4001,7 @@ struct Step {
                 for (int k = w.lane; k < n; k += WAVE) z[k] = zb[k];
             w.sync();
         }
+        MPCQP_MTOC("polish");
         return ok;
     }
 

@@ -138,3 +138,33 @@ for r in order + [r for r in tab if r not in order]:
     if r != "14":
         tot.update(c); tot["VALU"] += v; tot["nopst"] += nopstates[r]
 print("%-38s" % "TOTAL (without the polish)" + "".join("%7.0f" % tot[k] for k in cols) + "%8.0f%8.0f" % (tot["VALU"], tot["nopst"]))
+
+# The polish (Step::polish, its own tic / toc "polish" inside the body): STATIC counts of the phases laid out between the two
+# markers.  One attempt runs the assembly phases (row pass, E'DE, U rows / diagonal / eps row, Cholesky) once and the phases
+# of a round (G'w, H~ z, solves, G v) once per round; the E'DE of the polish is a chain of scalar branches, one per K step of a
+# pass, so its line is what an attempt with EVERY K step in the working set executes -- the mfma column of an attempt is the
+# count of the K steps its mask keeps (scripts/polish_active_steps.py).
+pol = [(a, b) for a, b, nm in spans if nm == "polish"]
+if pol:
+    a, b = pol[0]
+    ptab = collections.defaultdict(collections.Counter)
+    pnop = collections.Counter()
+    for i in range(a, b):
+        op, s = insts[i]
+        r = region[i] if region[i] != "polish" else "polish: rounds' tests, working set, restore"
+        k = kind(op, s)
+        ptab[r][k] += 1
+        if k == "nop":
+            pnop[r] += int(s.split()[1]) + 1
+    print()
+    print(f"polish, one attempt: instructions {a}..{b - 1} of the kernel ({b - a} static); static count per phase")
+    print("%-38s" % "phase" + "".join("%7s" % c for c in cols) + "%8s%8s" % ("VALU", "nopst"))
+    ptot = collections.Counter()
+    for r in order + [r for r in ptab if r not in order]:
+        if r not in ptab:
+            continue
+        c = ptab[r]
+        v = sum(c[k] for k in valu_c)
+        print("%-38s" % (PH.get(r, r))[:38] + "".join("%7.0f" % c[k] for k in cols) + "%8.0f%8.0f" % (v, pnop[r]))
+        ptot.update(c); ptot["VALU"] += v; ptot["nopst"] += pnop[r]
+    print("%-38s" % "TOTAL (static)" + "".join("%7.0f" % ptot[k] for k in cols) + "%8.0f%8.0f" % (ptot["VALU"], ptot["nopst"]))
