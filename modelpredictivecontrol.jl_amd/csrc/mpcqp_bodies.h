@@ -132,6 +132,9 @@
 #ifndef MPCQP_ETAPPLY_NB
 #define MPCQP_ETAPPLY_NB 3        // steps per (double-buffered) batch of E'w
 #endif
+#ifndef MPCQP_ETW_NB
+#define MPCQP_ETW_NB 4            // steps per batch of E'w on the 16 x 4 lane map (nu = ny = 4, one wavefront): two 8-byte loads per step
+#endif
 
 namespace mpcqp {
 
@@ -795,6 +798,89 @@ struct Qp {
     MPCQP_HD void Et_apply_share_(const double* wv, double* out, double scale, int t_hi, double& mine_k) {
         const int ny = d.ny, nu = d.nu;
         if (t_hi < 0) t_hi = d.Hp;          // only the steps t < t_hi contribute
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (DM::is_static) {
+            if constexpr (W::NTEAM == 1 && DM::ny == 4 && DM::nu == 4 && DM::nDU <= WAVE && DM::default_nb != 0 && DM::zpad >= 3) {
+                // The lane map of the register operands of E'DE (EtDE_share_, V): lane (li, lk) = (lane & 15, lane >> 4) reads
+                // ONE double per step, X[s] = Σ(s - q)[a][c] with q = li >> 2, c = li & 3 and a = lkp(lk) (the rows of a block
+                // in the order 0,2,1,3; zero blocks in front of the table for s < q: zpad >= 3), and serves column
+                // i = 16 J + li of every tile column J with it -- block column 4 J + q sees step t through block t - 4 J - q:
+                //   (E'w)[16 J + li] = sum_a sum_s X[s] w[s + 4 J, a],     acc[J] = fma(X[t - 4 J], w[t, a], acc[J]), t rising.
+                // All 64 lanes work, a step costs two 8-byte LDS reads (X[t], and w[t, a] once for all J), and the steps
+                // t < 4 J of tile column J -- products with a zero block -- are not formed.
+                // The four partials of a column (a = 0..3) sit in lanes l, l ^ 16, l ^ 32, l ^ 48.  They are added as
+                // (P0 + P1) + (P2 + P3) in the Σ-row index a: across l ^ 32 first (a ^ 1), then across l ^ 16 (a ^ 2) -- two rounds
+                // of lane swaps that at the same time hand tile column J to row J of the wave, so lane k = 16 J + li ends up
+                // with column k: round one leaves columns J = 0 / 1 on rows 0-1 and J = 2 / 3 on rows 2-3, round two the even J
+                // on the even rows and the odd J on the odd rows.
+                // BIT-IDENTICAL to the form below (which the CPU emulator keeps): per a the same products enter the same
+                // chain in the same order (the products left out are those with a zero block, +-0 added to a sum that is
+                // still +0), and the tree over a is the quad sum's; an entry can differ in the sign of a zero at most.
+                // t_hi < Hp is honoured as below: w[t, :] of the steps t >= t_hi enters as 0, whole batches beyond are skipped.
+                // (the lane id laundered, DevWave::relane() for this call alone: otherwise the lane's operand addresses are formed once
+                //  in front of the interior-point loop and held for the whole kernel -- one more spilled double in k_step_s<C3>)
+                int ln = w.lane;
+                asm volatile("" : "+v"(ln));
+                const int li = ln & 15, lk = ln >> 4;
+                const int a = ((lk & 1) << 1) | (lk >> 1);
+                const double* Xb = S - (li >> 2) * DM::sp + a * DM::rs + (li & 3);
+                const double* wa = wv + a;
+                constexpr int NT = (DM::nDU + 15) / 16;
+                // batches of NB steps: the loads of batch bt + 1 are in flight while batch bt is consumed; X stays live for
+                // the 4 (NT - 1) steps the later tile columns lag behind
+                constexpr int NB = MPCQP_ETW_NB, NBAT = (DM::Hp + NB - 1) / NB;
+                double X[DM::Hp], wt[DM::Hp];
+                double acc[4] = {0.0, 0.0, 0.0, 0.0};
+                // (volatile LDS reads: the compiler pairs plain ones into ds_read2_b64, which is banked by 32 dwords over 16
+                //  contiguous lanes -- there the four block columns of a row collide two by two, 24 q = 8 q mod 16 doubles -- and
+                //  takes 8 LDS cycles for two values; ds_read_b64 is banked by 64 dwords over half-waves: the 32 doubles
+                //  -24 q + 6 a + c of a half-wave fall in 32 different bank pairs, 2 cycles per value)
+                auto lds_b64 = [](const double* p) { return *(const volatile __attribute__((address_space(3))) double*)p; };
+                auto ld = [&](int bt) {
+                    MPCQP_UNROLL
+                    for (int u = 0; u < NB; ++u) {
+                        const int t = bt * NB + u;
+                        if (t >= DM::Hp) break;
+                        X[t] = lds_b64(Xb + t * DM::sp);
+                        wt[t] = lds_b64(wa + t * 4);
+                    }
+                };
+                ld(0);
+                MPCQP_UNROLL
+                for (int bt = 0; bt < NBAT; ++bt) {
+                    if (bt * NB >= t_hi) break;
+                    if (bt + 1 < NBAT) ld(bt + 1);
+                    MPCQP_SCHED_FENCE();
+                    MPCQP_UNROLL
+                    for (int u = 0; u < NB; ++u) {
+                        const int t = bt * NB + u;
+                        if (t >= DM::Hp) break;
+                        const double wv_ = t < t_hi ? wt[t] : 0.0;
+                        MPCQP_UNROLL
+                        for (int J = 0; J < NT; ++J)
+                            if (t - 4 * J >= 0) acc[J] = fma(X[t - 4 * J], wv_, acc[J]);
+                    }
+                    MPCQP_SCHED_FENCE();
+                }
+                // (a tile column that does not exist is stood in for by one that does: only rows without a column see it)
+                double r02 = acc[0], y02 = acc[NT > 2 ? 2 : 0];
+                W::swap32(r02, y02);
+                r02 += y02;
+                double r13 = r02;
+                if constexpr (NT > 1) {
+                    double y13 = acc[NT > 3 ? 3 : 1];
+                    r13 = acc[1];
+                    W::swap32(r13, y13);
+                    r13 += y13;
+                }
+                W::swap16(r02, r13);
+                const double mine = r02 + r13;
+                if constexpr (REG) { if (w.lane < DM::nDU) mine_k += scale * mine; }
+                else { if (w.lane < DM::nDU) out[w.lane] += scale * mine; }
+                return;
+            }
+        }
+#endif
         if constexpr (DM::is_static) {
             if (W::NTEAM == 1 && DM::ny == 4 && DM::nu == 4 && DM::nDU <= WAVE && d.default_nb) {
                 // lane (j, a) reads whole rows S_{t-j}[a][0..3] (two 16-byte loads instead of four

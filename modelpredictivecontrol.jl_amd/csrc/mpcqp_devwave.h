@@ -81,6 +81,23 @@ struct DevWave {
         v += dpp<0x4E>(v);
         return v;
     }
+    // gfx950 lane swaps between two registers (VALU, no LDS): rows 2-3 of x change places with rows 0-1 of y -- afterwards
+    // x = (x.r0, x.r1, y.r0, y.r1) and y = (x.r2, x.r3, y.r2, y.r3), by 16-lane rows: x + y adds lanes l and l ^ 32 of the old
+    // x on rows 0-1 and of the old y on rows 2-3
+    static __device__ __forceinline__ void swap32(double& x, double& y) {
+        const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(x), __double2loint(y), false, false);
+        const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(x), __double2hiint(y), false, false);
+        x = __hiloint2double(hi[0], lo[0]);
+        y = __hiloint2double(hi[1], lo[1]);
+    }
+    // the odd rows of x change places with the even rows of y: x = (x.r0, y.r0, x.r2, y.r2), y = (x.r1, y.r1, x.r3, y.r3) --
+    // x + y adds lanes l and l ^ 16 of the old x on the even rows and of the old y on the odd rows
+    static __device__ __forceinline__ void swap16(double& x, double& y) {
+        const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(x), __double2loint(y), false, false);
+        const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(x), __double2hiint(y), false, false);
+        x = __hiloint2double(hi[0], lo[0]);
+        y = __hiloint2double(hi[1], lo[1]);
+    }
     __device__ __forceinline__ double sum(double v) { return reduce<false>(v, [](double x, double y) { return x + y; }); }
     // (v_min_f64 / v_max_f64 directly: llvm.minnum / maxnum put a canonicalising v_max_f64 x, x, x in front of every operand)
     static __device__ __forceinline__ double mn_(double x, double y) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y)); return r; }
