@@ -466,6 +466,43 @@ int mpcqp_kf_solve_steady_device(mpcqp_handle h, void* stream);
 int mpcqp_kf_steady_iters(mpcqp_handle h, int32_t* out);
 int mpcqp_kf_steady_path(mpcqp_handle h, int32_t* out);
 
+/* ---- the Luenberger observer from its poles: the gain placed on the device ---------------------------
+ * What the reference computes once per estimator on the host, K̂ = place(Â, Ĉ, poles, :o; direct) (luenberger.jl:38-42),
+ * and refuses to redo after setmodel! (luenberger.jl:150-157): here every member of the batch places its poles on the
+ * model that is resident, by the robust placement of Kautsky, Nichols and Van Dooren ("method 0", csrc/kf_place_bodies.h),
+ * on the dual pair F = Â', G = (Ĉm Â)'.  The gain that lands in the gain buffer is the filter-form gain of mpcqp_kf_set:
+ * the poles are the eigenvalues of Â (I - K̂ Ĉm), whatever mpcqp_kf_set_direct says (direct = false: the reference's own
+ * gain is Â K̂, with the same poles).  Real poles only; a pole may be repeated up to nym times.  Ĉm is the measured rows of
+ * Ĉ: the reference places on all of Ĉ and drops the unmeasured columns afterwards, which agrees with this only when every
+ * output is measured.  A singular Â forces eigenvalues at 0: unless 0 is among the poles such a member gets status 2.
+ * nym > nx̂: the first nx̂ measured outputs carry the gain, the other columns of K̂ are zero.
+ *
+ * mpcqp_kf_set_poles: poles (nx̂,B), i_ym [nym] validated as in mpcqp_kf_set_covariances.  A pole that is not finite or has
+ * |p| >= 1: MPCQP_ERR_ARG.  Needs the model (MPCQP_ERR_ORDER).  max(nx̂, nym) > 32, or a build without the kernel:
+ * MPCQP_ERR_UNSUPPORTED, and the handle keeps what it had.  Otherwise: stores the poles, fills K̂, the status and the sweep
+ * counts with zeros, and places (host-synchronous).  In every other respect the handle is then one with a steady gain: no
+ * launch is added to a period, and mpcqp_kf_correct / _predict / _update, mpcqp_loop_device, mpcqp_sim (the fused path
+ * wherever a gain from mpcqp_kf_set qualifies) and mpcqp_est_initstate are those of mpcqp_kf_set, in both forms.
+ * mpcqp_kf_place / _place_device: place again on the model resident now (host-synchronous / enqueued on `stream`).
+ * mpcqp_set_model does NOT do this by itself: until the caller places again, the gain of the previous model stays in use.
+ * mpcqp_kf_set_place_cap: most sweeps of the next placements, 0 .. 100 (default 30; 0 returns the starting vectors);
+ * anything else MPCQP_ERR_ARG.  The sweeps stop earlier once |det X| moves by no more than 1e-3 of its value.
+ * mpcqp_kf_place_sweeps: out [B], sweeps of the last placement.
+ * On such a handle
+ *       mpcqp_kf_status   answers, per member, 0 placed; 2 broke down: (Ĉm Â)' has no full column rank, a mode is
+ *                         unobservable, a pole is repeated more often than there are outputs, or a value was not finite.
+ *                         With 2 the member's K̂ keeps its previous contents (zeros after mpcqp_kf_set_poles); the rest of
+ *                         the batch is unaffected, bit for bit;
+ *       MPCQP_GET_KF_GAIN returns K̂;  MPCQP_GET_KF_COV answers MPCQP_ERR_ORDER (an observer has no covariance);
+ *       mpcqp_kf_lanes_per_estimator answers 64.
+ * A later mpcqp_kf_set, mpcqp_kf_set_steady or mpcqp_kf_set_covariances leaves the mode: the four calls below
+ * mpcqp_kf_set_poles then answer MPCQP_ERR_ORDER, as mpcqp_kf_steady_* do on a handle in this mode. */
+int mpcqp_kf_set_poles(mpcqp_handle h, const double* poles, const int32_t* i_ym, int32_t nym);
+int mpcqp_kf_place(mpcqp_handle h);
+int mpcqp_kf_place_device(mpcqp_handle h, void* stream);
+int mpcqp_kf_set_place_cap(mpcqp_handle h, int32_t cap);
+int mpcqp_kf_place_sweeps(mpcqp_handle h, int32_t* out);
+
 /* ---- sim!: closed loops of the whole batch with the plant on the device (src/plot_sim.jl:241-319) ----------------
  * mpcqp_sim_set_plant attaches one LinModel per controller, the `plant` keyword of sim!: A (nxp,nxp,B), Bu (nxp,nu,B),
  * C (ny,nxp,B), Bd (nxp,nd,B), Dd (ny,nd,B), fx = fop - xop (nxp,B); Bd, Dd and fx may be NULL (zero).  Layouts of

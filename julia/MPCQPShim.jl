@@ -281,6 +281,48 @@ function steadykalmanfilter_iters(b::BatchLinMPC)
 end
 
 # ------------------------------------------------------------------------------------------------
+# Luenberger observer behind the batch (include/mpcqp.h, "the Luenberger observer from its poles"): the gain of every member is
+# placed on the device from the resident model and the observer poles, and placed again on request after a setmodel! ->
+# mpcqp_set_model (which the reference's Luenberger refuses).  Real poles inside the unit circle, max(nx̂, nym) <= 32; the gain is
+# the filter-form gain in both forms of `direct`.  pull_luenberger reads K̂, the status (0 placed, 2 broke down) and the sweep
+# counts back.  Call sequence = BatchLinMPC.setestimator(luenberger=...) of api.py; these ccalls have not been run.
+import ModelPredictiveControl: Luenberger
+
+"The poles of the batch's Luenberger observers ((nx̂, B), real) to the device, and the first placement."
+function push_luenberger!(b::BatchLinMPC, poles::AbstractMatrix{<:Real})
+    es = [c.estim for c in b.mpcs]
+    all(e -> e isa Luenberger && e.direct == es[1].direct, es) || throw(ArgumentError("Luenberger observers of one form (direct)"))
+    size(poles) == (es[1].nx̂, length(es)) || throw(ArgumentError("poles: (nx̂, B)"))
+    p = Matrix{Float64}(poles)
+    i_ym = Cint.(es[1].i_ym .- 1)                                            # 0-based
+    GC.@preserve p i_ym check(ccall((:mpcqp_kf_set_poles, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cint}, Cint), b.h, p, i_ym, length(i_ym)))
+    set_direct!(b, es[1].direct)
+    return b
+end
+
+"Place again on the model resident now (after mpcqp_set_model): until then the gain of the previous model is in use."
+place_luenberger!(b::BatchLinMPC) = check(ccall((:mpcqp_kf_place, lib), Cint, (Ptr{Cvoid},), b.h))
+
+"The same, asynchronous on `stream`."
+place_luenberger_device!(b::BatchLinMPC, stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:mpcqp_kf_place_device, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), b.h, stream))
+
+"Most sweeps of the placements that follow, 0 .. 100 (default 30)."
+set_luenberger_cap!(b::BatchLinMPC, cap::Integer) = check(ccall((:mpcqp_kf_set_place_cap, lib), Cint, (Ptr{Cvoid}, Cint), b.h, cap))
+
+"K̂ (nx̂, nym, B), the status and the sweeps of the last placement, per member."
+function pull_luenberger(b::BatchLinMPC)
+    B, e = length(b.mpcs), b.mpcs[1].estim
+    K̂ = Array{Float64}(undef, e.nx̂, e.nym, B)
+    st, sw = Vector{Cint}(undef, B), Vector{Cint}(undef, B)
+    check(ccall((:mpcqp_get, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), b.h, 11, K̂))      # MPCQP_GET_KF_GAIN
+    check(ccall((:mpcqp_kf_status, lib), Cint, (Ptr{Cvoid}, Ptr{Cint}), b.h, st))
+    check(ccall((:mpcqp_kf_place_sweeps, lib), Cint, (Ptr{Cvoid}, Ptr{Cint}), b.h, sw))
+    return (; K̂, status=st, sweeps=sw)
+end
+
+# ------------------------------------------------------------------------------------------------
 # InternalModel behind the batch (include/mpcqp.h, "InternalModel"): the stochastic model on the measured outputs goes to the
 # device once, Âs and B̂s are computed there; per period correct (ŷs, Ŷs, B + Ŷs for the steps), the unchanged step, update.
 # Call sequence = BatchLinMPC.setestimator(internal=...) of api.py; these ccalls have not been run.

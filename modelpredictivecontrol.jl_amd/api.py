@@ -51,6 +51,7 @@ EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_cre
            "mpcqp_kf_set_direct", "mpcqp_kf_update", "mpcqp_kf_update_device",
            "mpcqp_kf_set_steady", "mpcqp_kf_solve_steady", "mpcqp_kf_solve_steady_device", "mpcqp_kf_steady_iters",
            "mpcqp_kf_steady_path",
+           "mpcqp_kf_set_poles", "mpcqp_kf_place", "mpcqp_kf_place_device", "mpcqp_kf_set_place_cap", "mpcqp_kf_place_sweeps",
            "mpcqp_explicit_prepare", "mpcqp_explicit_status", "mpcqp_explicit_step", "mpcqp_explicit_step_device",
            "mpcqp_explicit_law", "mpcqp_explicit_law_device",
            "mpcqp_sim_set_plant", "mpcqp_sim", "mpcqp_sim_device", "mpcqp_sim_path",
@@ -209,6 +210,12 @@ def load_library(path: str | None = None):
         lib.mpcqp_kf_steady_iters.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(lib, "mpcqp_kf_steady_path"):       # (a build without the square-root pass: Handle then has no kf_steady_path)
         lib.mpcqp_kf_steady_path.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "mpcqp_kf_set_poles"):         # (an older build of the library: Handle then has no kf_set_poles ... methods)
+        lib.mpcqp_kf_set_poles.argtypes = [C.c_void_p] * 3 + [C.c_int32]
+        lib.mpcqp_kf_place.argtypes = [C.c_void_p]
+        lib.mpcqp_kf_place_device.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mpcqp_kf_set_place_cap.argtypes = [C.c_void_p, C.c_int32]
+        lib.mpcqp_kf_place_sweeps.argtypes = [C.c_void_p, C.c_void_p]
     lib.mpcqp_set_current_setpoint.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(lib, "mpcqp_explicit_prepare"):
         lib.mpcqp_explicit_prepare.argtypes = [C.c_void_p, C.c_int32]
@@ -316,6 +323,40 @@ def _kf_steady_path(self):
 _STEADY_METHODS = {f.__name__[1:]: f for f in (_kf_set_steady, _kf_solve_steady, _kf_solve_steady_device, _kf_steady_iters)}
 
 
+# -- Luenberger observer from its poles: the gain placed on the device (csrc/kf_place_bodies.h).  Methods of Handle, bound only
+# when the library exports the entry points
+def _kf_set_poles(self, poles, i_ym):
+    """poles (B,nx̂) real, inside the unit circle.  Places them on the resident model: the eigenvalues of Â (I - K̂ Ĉm);
+    kf_gain() / kf_status() / kf_place_sweeps() read the result back."""
+    iy = np.ascontiguousarray(i_ym, dtype=np.int32)
+    _chk(self.lib, self.lib.mpcqp_kf_set_poles(self.h, _ptr(_f64(poles)), _ptr(iy), int(iy.size)))
+    self.nym = int(iy.size)
+
+
+def _kf_place(self):
+    """Place again on the model that is resident now (after set_model); host-synchronous."""
+    _chk(self.lib, self.lib.mpcqp_kf_place(self.h))
+
+
+def _kf_place_device(self, stream=0):
+    _chk(self.lib, self.lib.mpcqp_kf_place_device(self.h, C.c_void_p(stream)))
+
+
+def _kf_set_place_cap(self, cap):
+    """Most sweeps of the placements that follow, 0 .. 100 (default 30)."""
+    _chk(self.lib, self.lib.mpcqp_kf_set_place_cap(self.h, int(cap)))
+
+
+def _kf_place_sweeps(self):
+    """(B,) int32 sweeps of the last placement."""
+    out = np.empty(self.B, np.int32)
+    _chk(self.lib, self.lib.mpcqp_kf_place_sweeps(self.h, _ptr(out)))
+    return out
+
+
+_PLACE_METHODS = {f.__name__[1:]: f for f in (_kf_set_poles, _kf_place, _kf_place_device, _kf_set_place_cap, _kf_place_sweeps)}
+
+
 class Handle:
     """Thin binding of the C-ABI; array arguments are already in ABI layout."""
 
@@ -344,6 +385,9 @@ class Handle:
             return types.MethodType(f, self)
         if name == "kf_steady_path" and hasattr(self.__dict__.get("lib"), "mpcqp_kf_steady_path"):
             return types.MethodType(_kf_steady_path, self)
+        f = _PLACE_METHODS.get(name)
+        if f is not None and hasattr(self.__dict__.get("lib"), "mpcqp_kf_set_poles"):
+            return types.MethodType(f, self)
         raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     def close(self):
@@ -1041,6 +1085,9 @@ class BatchLinMPC:
         if getattr(self, "kf_steady", False):      # SteadyKalmanFilter from Q̂ and R̂: the gain follows the model
             self.hd.kf_solve_steady()
             self._warn_steady()
+        if getattr(self, "kf_luenberger", False):  # Luenberger from its poles: so does this one
+            self.hd.kf_place()
+            self._warn_luenberger()
         est = getattr(self, "mhe", None)
         if est is not None:                        # the attached MovingHorizonEstimator: the measured rows of Ĉ and D̂d
             ops = self.__dict__.pop("_mhe_ops", {})
@@ -1267,10 +1314,11 @@ class BatchLinMPC:
                 raise ValueError(f"the estimator's {name} must be the controller's")
         self.hd.mhe_attach(est.handle, i_ym)
         self.i_ym, self.mhe, self.direct, self.internal = i_ym, est, est.direct, False
-        self.kf_timevarying = self.kf_steady = False
+        self.kf_timevarying = self.kf_steady = self.kf_luenberger = False
         return self
 
-    def setestimator(self, Khat=None, i_ym=None, xhat0=None, *, covariances=None, steady=None, direct=None, mhe=None, internal=None):
+    def setestimator(self, Khat=None, i_ym=None, xhat0=None, *, covariances=None, steady=None, direct=None, mhe=None, internal=None,
+                     luenberger=None):
         """Attach a SteadyKalmanFilter: Khat (B,nx̂,nym) steady-state gain (see
         `steady_kalman_gain`), i_ym measured-output indices (default all).  The estimate x̂0
         (deviation, (B,nx̂)) is then carried by this object like `mpc.estim.x̂0`.
@@ -1299,10 +1347,14 @@ class BatchLinMPC:
         `setmodel` (the rows i_ym of Ĉ and D̂d) forward to it, `mpc.xhat0` is `est.x̂0`, `moveinput(None, …)` reads it,
         `getinfo()["estim"]` is `est.getinfo()`, and `sim` / `hd.loop_device` run it on the device without a copy of x̂0.
 
-        `internal=dict(stoch_ym=None | (As, Bs, Cs, Ds))` attaches the `InternalModel` (see `setinternalmodel`)."""
-        if (Khat is not None) + (covariances is not None) + (steady is not None) + (mhe is not None) + (internal is not None) > 1:
+        `internal=dict(stoch_ym=None | (As, Bs, Cs, Ds))` attaches the `InternalModel` (see `setinternalmodel`).
+
+        `luenberger=dict(poles=None)` attaches the `Luenberger` observer (see `setluenberger`): the gain of every member is
+        placed on the device from the observer poles."""
+        if ((Khat is not None) + (covariances is not None) + (steady is not None) + (mhe is not None) + (internal is not None)
+                + (luenberger is not None)) > 1:
             raise ValueError("give one of Khat (SteadyKalmanFilter), steady (SteadyKalmanFilter from Q̂ and R̂), covariances (KalmanFilter), "
-                             "mhe (MovingHorizonEstimator) or internal (InternalModel)")
+                             "mhe (MovingHorizonEstimator), internal (InternalModel) or luenberger (Luenberger)")
         if internal is not None:
             if direct is not None and not direct:
                 raise ValueError("direct=False: the InternalModel is always in the filter form")
@@ -1317,10 +1369,12 @@ class BatchLinMPC:
             return self.setkalmanfilter(**covariances, i_ym=i_ym, xhat0=xhat0, direct=direct)
         if steady is not None:
             return self.setsteadykalmanfilter(**steady, i_ym=i_ym, xhat0=xhat0, direct=direct)
+        if luenberger is not None:
+            return self.setluenberger(**luenberger, i_ym=i_ym, xhat0=xhat0, direct=direct)
         if Khat is None:
-            raise ValueError("setestimator needs Khat, steady, covariances or mhe")
+            raise ValueError("setestimator needs Khat, steady, covariances, luenberger or mhe")
         self.__dict__.pop("mhe", None)              # (mpcqp_kf_set detaches a MovingHorizonEstimator)
-        self.kf_timevarying = self.kf_steady = False
+        self.kf_timevarying = self.kf_steady = self.kf_luenberger = False
         self.i_ym = np.arange(self.ny) if i_ym is None else np.asarray(i_ym, int)
         Khat = np.asarray(Khat, float)
         if Khat.shape != (self.B, self.nxh, len(self.i_ym)):
@@ -1367,7 +1421,7 @@ class BatchLinMPC:
         self.hd.im_set(stoch, i_ym)
         self.__dict__.pop("mhe", None)
         self.i_ym, self.internal, self.direct, self._hd_direct = i_ym, True, True, True      # (mpcqp_im_set puts the handle in the filter form)
-        self.kf_timevarying = self.kf_steady = False
+        self.kf_timevarying = self.kf_steady = self.kf_luenberger = False
         self.xhat0 = np.zeros((B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (B, self.nxh))).copy()
         n = int(np.count_nonzero(self.hd.im_status()))
         if n:
@@ -1417,7 +1471,7 @@ class BatchLinMPC:
         self.__dict__.pop("mhe", None)
         self.internal = False
         self._P0 = P0.copy()                        # P̂_0, for initstate (init_estimate_cov!)
-        self.kf_timevarying, self.kf_steady = True, False
+        self.kf_timevarying, self.kf_steady, self.kf_luenberger = True, False, False
         self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
         return self
 
@@ -1431,10 +1485,52 @@ class BatchLinMPC:
         self.hd.kf_set_steady(Qhat, Rhat, self.i_ym)
         self.__dict__.pop("mhe", None)
         self.internal = False
-        self.kf_timevarying, self.kf_steady = False, True
+        self.kf_timevarying, self.kf_steady, self.kf_luenberger = False, True, False
         self._warn_steady()
         self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
         return self
+
+    def setluenberger(self, poles=None, i_ym=None, xhat0=None, direct=True):
+        """The `Luenberger` observer (src/estimator/luenberger.jl): `poles` are the nx̂ observer poles, (nx̂,) shared or (B,nx̂),
+        real and inside the unit circle (default: the reference's `1e-3*(1:nx̂) .+ 0.5`).  The gain of every member is placed
+        on the device (robust placement of Kautsky, Nichols and Van Dooren; max(nx̂, nym) <= 32; a pole may be repeated up to
+        nym times): the eigenvalues of Â (I - K̂ Ĉm) are the poles in both forms of `direct`.  From then on the estimator runs
+        like one with a given steady gain, and `setmodel` places again on the new model -- which the reference's Luenberger
+        refuses.  Members whose placement broke down (an unobservable mode, a singular Â without a pole at 0, ...) keep the
+        previous gain (or zero) and are counted in one RuntimeWarning; `getinfo` shows `K̂`, `kf_status` and `place_sweeps`.
+        Deviations from the reference: complex poles are not implemented, and the placement works on the measured rows Ĉm
+        (the reference places on all of Ĉ and drops the unmeasured columns, which agrees when every output is measured)."""
+        i_ym = np.arange(self.ny) if i_ym is None else np.asarray(i_ym, int)
+        if len(i_ym) < 1 or i_ym.min() < 0 or i_ym.max() >= self.ny or len(set(i_ym.tolist())) != len(i_ym):
+            raise ValueError("i_ym: unique indices of measured outputs in 0 .. ny-1")
+        p = 1e-3 * np.arange(1, self.nxh + 1) + 0.5 if poles is None else np.asarray(poles)
+        if np.iscomplexobj(p):
+            if np.any(p.imag != 0):
+                raise NotImplementedError("complex observer poles are not implemented: real poles only")
+            p = p.real
+        p = np.asarray(p, float)
+        if p.ndim not in (1, 2) or p.shape[-1] != self.nxh or (p.ndim == 2 and p.shape[0] != self.B):
+            raise ValueError(f"poles length ({p.shape[-1] if p.ndim else 0}) ≠ nx̂ ({self.nxh})")
+        if not np.all(np.abs(p) < 1.0):
+            raise ValueError("Observer poles should be inside the unit circles.")
+        if not hasattr(self.hd, "kf_set_poles"):
+            raise NotImplementedError("luenberger=dict(poles): this handle has no mpcqp_kf_set_poles")
+        p = _f64(np.broadcast_to(p, (self.B, self.nxh)))
+        self._set_direct(direct)
+        self.hd.kf_set_poles(p, i_ym)
+        self.i_ym = i_ym
+        self.__dict__.pop("mhe", None)
+        self.internal = False
+        self.kf_timevarying, self.kf_steady, self.kf_luenberger = False, False, True
+        self._warn_luenberger()
+        self.xhat0 = np.zeros((self.B, self.nxh)) if xhat0 is None else _f64(np.broadcast_to(xhat0, (self.B, self.nxh))).copy()
+        return self
+
+    def _warn_luenberger(self):
+        """One warning for the members whose poles could not be placed (luenberger.jl:38-42)."""
+        n = int(np.count_nonzero(self.hd.kf_status()))
+        if n:
+            warnings.warn(f"Cannot compute the Luenberger gain K̂ with specified poles. ({n} of {self.B} estimators)", RuntimeWarning)
 
     def _warn_steady(self):
         """One warning for the members whose steady-state gain could not be computed (kalman.jl:211-221)."""
@@ -1463,6 +1559,8 @@ class BatchLinMPC:
             self.mhe.setstate(self._bc(xhat, self.nxh, "x̂"), Phat)
             return self
         if Phat is not None:
+            if getattr(self, "kf_luenberger", False):
+                raise ValueError("Luenberger does not compute an estimation covariance matrix P̂.")
             if not getattr(self, "kf_timevarying", False):
                 raise ValueError("the SteadyKalmanFilter has no covariance estimate P̂ to set")
             self.hd.kf_set_state_covariance(self._cov(Phat, self.nxh, "P̂"))
@@ -1894,6 +1992,8 @@ class BatchLinMPC:
             info["P̂"], info["K̂"], info["kf_status"] = self.hd.kf_covariance(), self.hd.kf_gain(), self.hd.kf_status()
             if getattr(self, "kf_steady", False) and hasattr(self.hd, "kf_steady_path"):
                 info["kf_steady_path"] = self.hd.kf_steady_path()      # 1: solved by the square-root form (semidefinite Q̂)
+        if getattr(self, "kf_luenberger", False):  # the placed gain, per-member status and sweep counts
+            info["K̂"], info["kf_status"], info["place_sweeps"] = self.hd.kf_gain(), self.hd.kf_status(), self.hd.kf_place_sweeps()
         if getattr(self, "mhe", None) is not None:
             info["estim"] = self.mhe.getinfo()
         # decision vector in the transcription's layout: [ΔU; ϵ] or [ΔU; X̂0(k+1..k+Hp); ϵ] (get_nZ_mpc, transcription.jl:2-7)

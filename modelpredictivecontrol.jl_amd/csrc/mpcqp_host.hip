@@ -16,6 +16,7 @@
 #include "im_launch.h"
 #include "kf_cov_launch.h"
 #include "kf_dare_launch.h"
+#include "kf_place_launch.h"
 #include "mpcqp_hostutil.h"
 #include "mpcqp_launch.h"
 #include "ms_bodies.h"
@@ -80,6 +81,11 @@ struct mpcqp_handle_s {
     DBuf kf_it;
     DBuf kf_path;     // which body produced each estimator's result (kf_dare_launch.h: DareArgs::path)
     int kf_dare_waves = 0;
+    // Luenberger observer from its poles (mpcqp_kf_set_poles): kf_K holds the gain the placement kernel (kf_place_bodies.h)
+    // found, kf_st / kf_it its status and sweep count; kf_tv and kf_steady stay false
+    bool kf_place = false;
+    DBuf kf_poles;
+    int kf_place_cap = kf::PLACE_CAP_DEFAULT;
     // mpcqp_kf_set_direct: 1 filter form (mpcqp_loop_device: correction, step, prediction), 0 predictor form (step, correction,
     // prediction).  A property of the handle: the setters of the gain and of the covariances leave it alone
     int kf_direct = 1;
@@ -1313,6 +1319,7 @@ int mpcqp_kf_set(mpcqp_handle h, const double* Khat, const int32_t* i_ym, int32_
     h->mhe = nullptr;           // (a Kalman handle again)
     h->kf_tv = false;           // (back to the steady gain: the covariance kernel no longer runs)
     h->kf_steady = false;       // (a gain of the caller's: nothing to re-solve)
+    h->kf_place = false;
     return MPCQP_OK;
 }
 
@@ -1368,6 +1375,7 @@ int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* R
     h->mhe = nullptr;
     h->kf_tv = true;
     h->kf_steady = false;
+    h->kf_place = false;
     return MPCQP_OK;
 }
 
@@ -1429,6 +1437,7 @@ int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, 
     h->mhe = nullptr;
     h->kf_tv = false;
     h->kf_steady = true;
+    h->kf_place = false;
     return mpcqp_kf_solve_steady(h);
 }
 
@@ -1466,6 +1475,91 @@ int mpcqp_kf_steady_path(mpcqp_handle h, int32_t* out) {
     return MPCQP_OK;
 }
 
+// One placement of a handle in pole mode (kf_place_kernels.hip: k_kf_place) on the model that is resident now.
+static int kf_place_launch(mpcqp_handle h, hipStream_t st) {
+    if (!kf::kf_place_available()) return MPCQP_ERR_UNSUPPORTED;
+    ON_DEVICE(h);
+    const Dims& d = h->d;
+    kf::PlaceArgs a{};
+    a.Ahat = h->m.Ahat; a.C = h->m.C; a.i_ym = h->kf.i_ym;
+    a.poles = (const double*)h->kf_poles.p;
+    a.K = (double*)h->kf_K.p;
+    a.status = (int32_t*)h->kf_st.p; a.sweeps = (int32_t*)h->kf_it.p;
+    a.B = d.B; a.nx = d.nxh; a.ny = d.ny; a.nym = h->kf.nym;
+    a.cap = h->kf_place_cap;
+    a.stored = kf::place_stored_for(a.nx, a.nym) ? 1 : 0;
+    HIPCHK(kf::launch_kf_place(a, st));
+    return MPCQP_OK;
+}
+
+int mpcqp_kf_set_poles(mpcqp_handle h, const double* poles, const int32_t* i_ym, int32_t nym) {
+    if (!h || !poles || !i_ym) return MPCQP_ERR_NULL;
+    const Dims& d = h->d;
+    if (nym < 1 || nym > d.ny) return MPCQP_ERR_DIMS;
+    for (int i = 0; i < nym; ++i) {
+        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;     // validate_ym, construct.jl:190-196
+        for (int j = 0; j < i; ++j)
+            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
+    }
+    if (std::max(d.nxh, (int)nym) > kf::PLACE_NMAX || !kf::kf_place_available()) return MPCQP_ERR_UNSUPPORTED;
+    const size_t B = d.B, nk = (size_t)d.nxh * nym, sz = sizeof(double);
+    for (size_t i = 0; i < B * d.nxh; ++i)
+        if (!(std::fabs(poles[i]) < 1.0)) return MPCQP_ERR_ARG;      // inside the unit circle (luenberger.jl:108-115); a NaN fails
+    if (!h->have_model) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    int rc = upload(h, h->kf_poles, poles, B * d.nxh * sz);
+    if (!rc) rc = upload(h, h->kf_iym, i_ym, (size_t)nym * sizeof(int32_t));
+    if (!rc) rc = dev_alloc(h, h->kf_K, B * nk * sz);
+    if (!rc) rc = dev_alloc(h, h->kf_st, B * sizeof(int32_t));
+    if (!rc) rc = dev_alloc(h, h->kf_it, B * sizeof(int32_t));
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(h->kf_K.p, 0, B * nk * sz, h->stream));
+    HIPCHK(hipMemsetAsync(h->kf_st.p, 0, B * sizeof(int32_t), h->stream));
+    HIPCHK(hipMemsetAsync(h->kf_it.p, 0, B * sizeof(int32_t), h->stream));
+    h->kf.Khat = (const double*)h->kf_K.p;
+    h->kf.i_ym = (const int*)h->kf_iym.p;
+    h->kf.nym = nym;
+    h->have_kf = true;
+    h->have_im = false;
+    h->mhe = nullptr;
+    h->kf_tv = false;
+    h->kf_steady = false;
+    h->kf_place = true;
+    return mpcqp_kf_place(h);
+}
+
+int mpcqp_kf_place_device(mpcqp_handle h, void* stream) {
+    if (!h) return MPCQP_ERR_NULL;
+    if (!h->kf_place || !h->have_model) return MPCQP_ERR_ORDER;
+    return kf_place_launch(h, (hipStream_t)stream);
+}
+
+int mpcqp_kf_place(mpcqp_handle h) {
+    if (!h) return MPCQP_ERR_NULL;
+    int rc = mpcqp_kf_place_device(h, h->stream);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
+int mpcqp_kf_set_place_cap(mpcqp_handle h, int32_t cap) {
+    if (!h) return MPCQP_ERR_NULL;
+    if (!h->kf_place) return MPCQP_ERR_ORDER;
+    if (cap < 0 || cap > kf::PLACE_CAP_MAX) return MPCQP_ERR_ARG;
+    h->kf_place_cap = cap;
+    return MPCQP_OK;
+}
+
+int mpcqp_kf_place_sweeps(mpcqp_handle h, int32_t* out) {
+    if (!h || !out) return MPCQP_ERR_NULL;
+    if (!h->kf_place) return MPCQP_ERR_ORDER;
+    ON_DEVICE(h);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, h->kf_it.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MPCQP_OK;
+}
+
 int mpcqp_kf_set_state_covariance(mpcqp_handle h, const double* P) {
     if (!h || !P) return MPCQP_ERR_NULL;
     if (!h->kf_tv) return MPCQP_ERR_ORDER;
@@ -1481,7 +1575,7 @@ int mpcqp_kf_set_state_covariance(mpcqp_handle h, const double* P) {
 
 int mpcqp_kf_status(mpcqp_handle h, int32_t* out) {
     if (!h || !out) return MPCQP_ERR_NULL;
-    if (!h->kf_tv && !h->kf_steady) return MPCQP_ERR_ORDER;
+    if (!h->kf_tv && !h->kf_steady && !h->kf_place) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipDeviceSynchronize());
@@ -1491,6 +1585,7 @@ int mpcqp_kf_status(mpcqp_handle h, int32_t* out) {
 
 int mpcqp_kf_lanes_per_estimator(mpcqp_handle h) {
     if (!h) return MPCQP_ERR_NULL;
+    if (h->kf_place) return WAVE;       // (the placement: one member per wavefront at every size)
     return (h->kf_tv || h->kf_steady) ? kf::kf_cov_lanes_for(h->kf_NX) : 0;
 }
 
@@ -1659,7 +1754,7 @@ int mpcqp_im_set(mpcqp_handle h, int32_t nxs, const double* As, const double* Bs
     h->kf.i_ym = (const int*)h->kf_iym.p;
     h->kf.nym = nym;
     h->im_nxs = nxs;
-    h->have_kf = h->kf_tv = h->kf_steady = false;       // (replaces a Kalman filter or an attached MovingHorizonEstimator)
+    h->have_kf = h->kf_tv = h->kf_steady = h->kf_place = false;       // (replaces a Kalman filter or an attached MovingHorizonEstimator)
     h->mhe = nullptr;
     h->kf_direct = 1;
     h->have_im = true;
@@ -1754,7 +1849,7 @@ int mpcqp_mhe_attach(mpcqp_handle h, mpcqp_mhe e, const int32_t* i_ym, int32_t n
     h->kf.Khat = nullptr;
     h->kf.i_ym = (const int*)h->kf_iym.p;
     h->kf.nym = nym;
-    h->have_kf = h->kf_tv = h->kf_steady = false;       // (the attachment replaces a Kalman filter)
+    h->have_kf = h->kf_tv = h->kf_steady = h->kf_place = false;       // (the attachment replaces a Kalman filter)
     h->have_im = false;
     h->mhe = e;
     return MPCQP_OK;
