@@ -1078,10 +1078,25 @@ struct Qp {
         // then every further row on its own.  A pass starts at the first K step that reaches its
         // first block column (E is block lower triangular).
         constexpr int IE = NDU / 16, LE = NDU % 16;     // tile row / lane column of the ϵ row
+        constexpr int QK = NY % 4 == 0 ? NY / 4 : 1;                  // K steps per step of the horizon
+        constexpr int DJ = (16 % NU == 0) ? QK * (16 / NU) : 1;       // K steps by which a tile column's operands lag those of the one before
+        constexpr bool VREG = NY % 4 == 0 && 16 % NU == 0 && DM::zpad > 0 && DM::zpad >= 16 / NU - 1 &&
+                              NK <= MPCQP_ETDE_VREG_MAX;
+        // B4: the ragged last tile row (one or two block rows of nu = 4 variables in 16 operand rows) runs on
+        // v_mfma_f64_4x4x4_4b instead: four independent 4 x 4 x 4 products per instruction, A and B lane = 16 k + 4 q + (row i
+        // or column j) with q the product, D lane = 16 i + 4 q + j -- the lane map of V, so V[s] is directly a B operand whose
+        // four products see the Σ blocks of four consecutive block columns, and the one new operand is the block row's own
+        // Σ(t - bi) repeated in all four quads (VA below).  Per block row and K step one instruction per group of four
+        // block columns, a quarter of the 16x16x4 form's cycles each, and the accumulators are one double per lane and
+        // instruction, entry (4 bi + lk, 16 J + li): reg = block row in the write-back's maps.  A full A block has no room
+        // for the ϵ row: it goes to the caller whole (eps_t0 = -1) and the row is initialised behind the passes.
+        // nDU mod 16 = 12 does not pay (three block rows: 3 (NT) quarter instructions against NT whole ones); the masked
+        // pass of the polish (MK), teams and operands from LDS keep the 16x16x4 form.
+        constexpr bool B4 = W::NTEAM == 1 && VREG && NU == 4 && NY == 4 && !MK && NT >= 3 && (LE == 4 || LE == 8);
         // first step whose rows the ϵ row is accumulated for by the pass of its tile row (kfirst() below; known up front: in a
         // team that pass may run on another wavefront)
         int eps_t0 = -1;
-        if (DM::neps && has_tb && IE < NT) {
+        if (DM::neps && has_tb && IE < NT && !B4) {
             int v = (jl((16 * IE) / NU) * NY) / 4;
             v = v < NK ? v : NK;
             if ((4 * v) % NY != 0) v = 0;
@@ -1089,10 +1104,6 @@ struct Qp {
         }
         // operands in registers: V[k] = operand of tile column 0 at K step k = (t, a0): Sigma(t - li / nu)[a0 + row, li % nu]
         // (zero blocks in front of the table for t < li / nu)
-        constexpr int QK = NY % 4 == 0 ? NY / 4 : 1;                  // K steps per step of the horizon
-        constexpr int DJ = (16 % NU == 0) ? QK * (16 / NU) : 1;       // K steps by which a tile column's operands lag those of the one before
-        constexpr bool VREG = NY % 4 == 0 && 16 % NU == 0 && DM::zpad > 0 && DM::zpad >= 16 / NU - 1 &&
-                              NK <= MPCQP_ETDE_VREG_MAX;
         double V[VREG ? NK : 1];
         if constexpr (VREG) {
             const int cbv = li / NU, civ = li - cbv * NU;
@@ -1117,7 +1128,7 @@ struct Qp {
             }
             // ϵ row (index NDU, when present): row NDU of Phi is sum_r tb[r] E[r,:], i.e. the same
             // contraction with A operand tb instead of E*dd -- rides in its tile row for free
-            const bool erow = DM::neps && has_tb && IE >= I0 && IE <= I1;
+            const bool erow = !B4 && DM::neps && has_tb && IE >= I0 && IE <= I1;
             // entry (reg) of tile (I, J) held by this lane: row i = 16 I + 4 reg + lk, column ip = 16 J + li; with
             // G = 4 I + reg the packed index pk(i, ip) = 8 G (G + 1) + 16 J + 4 (G + 1) lk + li is linear in the lane's
             // (lk, li) with compile-time coefficients
@@ -1171,6 +1182,93 @@ struct Qp {
             //  spilled; the loop is long enough there to cover the loads from its last steps on)
             constexpr bool LATEH = !VREG && NT > 4;
             if (Hg && !VREG && !LATEH) hload();
+            if constexpr (B4 && I0 == NT - 1) {
+                // The ragged tile row on 4x4x4 blocks (B4 above).  Block row bi = 4 I0 + r, r < NBR, at step t >= bi:
+                //   A = VA[t - bi] * d(t)   (Σ(t - bi)[a(lk)][li & 3], the same block in every quad, times the step's row factors)
+                //   B = V[t - 4 J]          (quad q: Σ(t - 4 J - q), block column 4 J + q), J = 0 .. I0
+                // the last group holds the diagonal: quad q < NBR is block (bi, 4 I0 + q), the others lie right of the
+                // stored triangle.  VA[t - bi] of block row r is the previous step's operand of block row r - 1: one
+                // 8-byte LDS read per lane and step (lanes of equal (li & 3, lk) read one address), requested a batch
+                // ahead together with the row factors.  K order per entry: t rising, k as in V -- the 16x16x4 form's.
+                constexpr int NBR = B4 ? LE / 4 : 1, T0 = DJ * I0;       // block rows of the tile row; its first K step
+                constexpr int CH = MPCQP_ETDE_VREG_CHUNK;
+                double a4[NBR][NT];
+                MPCQP_UNROLL
+                for (int r = 0; r < NBR; ++r) {
+                    MPCQP_UNROLL
+                    for (int J = 0; J < NT; ++J) a4[r][J] = 0.0;
+                }
+                double dvb[2][CH], vab[2][CH];
+                const double* ddl = dd + lkp;
+                const double* VAb = S + lkp * RS + (li & 3) - T0 * SP;
+                auto ldc = [&](int c0, int buf) {
+                    MPCQP_UNROLL
+                    for (int u = 0; u < CH; ++u) {
+                        const int kk = c0 + u;
+                        if (kk >= NK) break;
+                        dvb[buf][u] = ddl[4 * kk];
+                        vab[buf][u] = VAb[kk * SP];
+                    }
+                };
+                double vprev = 0.0;
+                ldc(T0, 0);
+                MPCQP_UNROLL
+                for (int c0 = T0; c0 < NK; c0 += CH) {
+                    const int buf = ((c0 - T0) / CH) & 1;
+                    if (c0 + CH < NK) ldc(c0 + CH, buf ^ 1);
+                    MPCQP_SCHED_FENCE();
+                    MPCQP_UNROLL
+                    for (int u = 0; u < CH; ++u) {
+                        const int kk = c0 + u;
+                        if (kk >= NK) break;
+                        MPCQP_UNROLL
+                        for (int r = 0; r < NBR; ++r) {
+                            if (kk < T0 + r) continue;
+                            const double ad = (r == 0 ? vab[buf][u] : vprev) * dvb[buf][u];
+                            MPCQP_UNROLL
+                            for (int J = 0; J <= I0; ++J)
+                                a4[r][J] = __builtin_amdgcn_mfma_f64_4x4x4f64(ad, V[kk - DJ * J], a4[r][J], 0, 0, 0);
+                        }
+                        vprev = vab[buf][u];
+                    }
+                    MPCQP_SCHED_FENCE();
+                }
+                double h4[NBR][NT];
+                if (Hg) {
+                    MPCQP_UNROLL
+                    for (int J = 0; J <= I0; ++J) {
+                        MPCQP_UNROLL
+                        for (int r = 0; r < NBR; ++r) h4[r][J] = Hg[entry_ok(I0, J, r) ? (unsigned)entry_idx_pk(I0, J, r) : 0u];
+                    }
+                }
+                entry_base();
+                if (ow) {
+                    MPCQP_UNROLL
+                    for (int J = 0; J <= I0; ++J) {
+                        MPCQP_UNROLL
+                        for (int r = 0; r < NBR; ++r)
+                            if (entry_ok(I0, J, r)) P[entry_idx(I0, J, r)] = Hg ? fma(scale, a4[r][J], h4[r][J]) : scale * a4[r][J];
+                    }
+                    return;
+                }
+                double* const trash = sm + c.zero + 4;
+                double* pp_[NBR][NT];
+                double old_[NBR][NT];
+                MPCQP_UNROLL
+                for (int J = 0; J <= I0; ++J) {
+                    MPCQP_UNROLL
+                    for (int r = 0; r < NBR; ++r) {
+                        pp_[r][J] = entry_ok(I0, J, r) ? P + entry_idx(I0, J, r) : trash;
+                        old_[r][J] = *pp_[r][J];
+                    }
+                }
+                MPCQP_UNROLL
+                for (int J = 0; J <= I0; ++J) {
+                    MPCQP_UNROLL
+                    for (int r = 0; r < NBR; ++r) *pp_[r][J] = fma(scale, a4[r][J], old_[r][J]);
+                }
+                return;
+            } else {
             // First K step at which tile row I sees a block column that has started (t >= j_l of
             // its first column); the ϵ row needs every step.  The K loop is split at these points
             // so that its bodies are branch-free (accumulators stay in place across iterations).
@@ -1367,12 +1465,13 @@ struct Qp {
                     for (int reg = 0; reg < 4; ++reg) *pp_[reg] = fma(scale, acc[I - I0][J][reg], old_[reg]);
                 }
             }
+            }
         };
         etde_passes<0, NT>(pass);
         auto pix = [](int i, int j) { if constexpr (PH) return phi(DM::nZ, i, j); else return pk(i, j); };
         if constexpr (DM::neps != 0 && W::WV == 0) {
             if (ow && !Hg) {             // (same as below with H̃'s ϵ row: zero off the diagonal; the caller adds 2 C to the diagonal)
-                if constexpr (IE >= NT) {
+                if constexpr (IE >= NT || B4) {      // (B4: the ragged row's pass leaves the ϵ row out, as if it were a tile row of its own)
                     for (int k = w.lane; k < NDU; k += WAVE) P[pix(NDU, k)] = 0.0;
                 }
                 if (w.lane == 0) P[pix(NDU, NDU)] = 0.0;
@@ -1381,7 +1480,7 @@ struct Qp {
                 // the overwrite mode nothing else initialises it (the caller adds E'tb to it: eps_t0 stays -1), and the
                 // row would keep the previous factor's entries: a wrong Newton matrix, twice the iterations and
                 // failed solves on every shape with nu Hc = 16, 32, 48, .. (found at nZ~ = 81, round 3)
-                if constexpr (IE >= NT) {
+                if constexpr (IE >= NT || B4) {
                     for (int k = w.lane; k < NDU; k += WAVE) P[pix(NDU, k)] = Hg[pk(NDU, k)];
                 }
                 if (w.lane == 0) P[pix(NDU, NDU)] = Hg[pk(NDU, NDU)];     // Ñ's slack weight (construct.jl:842)
