@@ -285,7 +285,74 @@ int mpcqp_recondense_device(mpcqp_handle h, void* stream);
 #define MPCQP_GET_IM_YS     14  /* (ny,B):  ŷs of its last correction (0 in the unmeasured rows) */
 #define MPCQP_GET_IM_YHATS  15  /* (nY,B):  Ŷs of its last correction, the term the steps add to the model's B */
 #define MPCQP_GET_EXPLICIT_LAW 12 /* (nZ, 1+nx̂+nu+ny+nd, B): the law [g0 Gx Gu Gr Gd] of mpcqp_explicit_prepare(h, MPCQP_EXPLICIT_LAW) */
+/* the resident model, in the layouts of mpcqp_set_model (what mpcqp_set_model_continuous wrote, or the arrays of the last
+ * mpcqp_set_model): Â (nx̂,nx̂,B), B̂u (nx̂,nu,B), Ĉ (ny,nx̂,B), B̂d (nx̂,nd,B), D̂d (ny,nd,B) -- MPCQP_ERR_ARG for the last two
+ * when nd = 0 -- and f̂op - x̂op (nx̂,B), zeros when none is set */
+#define MPCQP_GET_MODEL_AHAT 16
+#define MPCQP_GET_MODEL_BU   17
+#define MPCQP_GET_MODEL_C    18
+#define MPCQP_GET_MODEL_BD   19
+#define MPCQP_GET_MODEL_DD   20
+#define MPCQP_GET_MODEL_DOP  21
 int mpcqp_get(mpcqp_handle h, int which, double* out);
+
+/* ---- LinModel(sys, Ts) and augment_model for the whole batch, on the device --------------------------------------------
+ * What the reference does on the host before LinMPC(model) exists: LinModel(sys, Ts) (src/model/linmodel.jl:165-198) turns a
+ * continuous model into a discrete one -- c2d(sysu, Ts, :zoh) for the manipulated inputs, c2d(sysd, Ts, :tustin) for the
+ * measured disturbances, stacked as [sysu_dis sysd_dis] -- and augment_model (src/estimator/construct.jl:305-323, with
+ * init_estimstoch / init_integrators :172-252) appends the integrators of nint_u / nint_ym.  Here every member of the batch is
+ * discretised and augmented in one launch (csrc/c2d_bodies.h), each with its own sample time.
+ *
+ *   inputs   A (nx,nx,B), Bu (nx,nu,B), C (ny,nx,B), Bd (nx,nd,B), Dd (ny,nd,B) continuous time, layouts of mpcqp_set_model;
+ *            Ts (B); dop (nx_dis,B) = fop - xop of the discrete plant's states, may be NULL; Bd and Dd only with nd > 0
+ *   spec     dimensions; nint_u [nu], nint_ym [nym] (NULL: no integrator), i_ym [nym] (NULL: 0 .. nym-1), shared by the batch;
+ *            d_method: MPCQP_C2D_TUSTIN, the reference's treatment of the measured disturbances, or MPCQP_C2D_ZOH, a
+ *            deviation that keeps one state vector
+ *   ZOH      exp([[A, Bu(, Bd)], [0, 0]] Ts) = [[Φ, Γu(, Γd)], [0, I]]; Bd is in the block only with MPCQP_C2D_ZOH
+ *   Tustin   (nd > 0 and MPCQP_C2D_TUSTIN) a = Ts/2, W = (I - aA)⁻¹: At = W (I + aA), Bt = W Bd Ts, Ct = C W, Dt = Dd + a C W Bd.
+ *            The plant is then x = [xu; xd]: A = blkdiag(Φ, At), Bu = [Γu; 0], Bd = [0; Bt], C = [C, Ct], Dd = Dt, so that
+ *            nx_dis = 2 nx; otherwise nx_dis = nx
+ *   outputs  Â = [A, Bu Cs_u; 0, As], B̂u = [Bu; 0], Ĉ = [C, Cs_y], B̂d = [Bd; 0], D̂d = Dd, dop padded with zeros;
+ *            nx̂ = nx_dis + Σ nint_u + Σ nint_ym (mpcqp_c2d_sizes).  Cs_u and Cs_y hold 0 and 1: those blocks are copies
+ *   status   (B) int32: 0 written; 2 refused -- an input that is not finite, Ts not finite or <= 0, I - aA or the Padé
+ *            denominator singular (a pivot at or below 64 eps times the largest), a scaled norm beyond 5.37 x 2^64, a result
+ *            that is not finite.  NOTHING is written for a refused member: its outputs keep what they held (on a handle: the
+ *            model it had; zeros on a handle that had none), and the other members are unaffected, bit for bit.
+ * Not done: the reference's sminreal / minreal after the discretisation (they change the realisation, not the input-output
+ * map), the pruning of integrators by default_nint and the observability check of augment_model -- nint_ym is what the
+ * caller gives.  Limits (MPCQP_ERR_UNSUPPORTED): nx + nu (+ nd with MPCQP_C2D_ZOH) > 32; with the Tustin block also ny > 32 or
+ * nd > 32; nx̂ > 64; a shard of mpcqp_multi_create; a library built without the kernel.  MPCQP_ERR_DIMS / _ARG: dimensions
+ * below 1, nym > ny, an unknown d_method, a negative nint, i_ym out of range or repeated.
+ *
+ * mpcqp_c2d         host pointers, synchronous, no handle.
+ * mpcqp_c2d_device  DEVICE pointers (status too), enqueued on `stream`.
+ * mpcqp_set_model_continuous[_device]  the kernel writes straight into the handle's resident model; then everything
+ *                   mpcqp_set_model / mpcqp_recondense_device do (K1, K2, the InternalModel's B + Ŷs, the refresh of a prepared
+ *                   explicit factor) -- in the _device form on `stream`, with no host synchronisation; `in` and `status` are
+ *                   DEVICE pointers there.  dop NULL: the handle has no f̂op - x̂op afterwards, as with mpcqp_set_model.  The
+ *                   handle's batch, nx̂, nu, ny, nd must be those the spec implies: MPCQP_ERR_ARG otherwise, and the handle keeps
+ *                   what it had, as after every other refusal.  Like mpcqp_set_model it does NOT re-solve estimator gains. */
+#define MPCQP_C2D_TUSTIN 0
+#define MPCQP_C2D_ZOH    1
+typedef struct mpcqp_c2d_spec {
+    int32_t batch, nx, nu, ny, nd, nym;
+    int32_t d_method;
+    const int32_t* nint_u;
+    const int32_t* nint_ym;
+    const int32_t* i_ym;
+} mpcqp_c2d_spec;
+typedef struct mpcqp_c2d_in {
+    const double *A, *Bu, *C, *Bd, *Dd, *Ts, *dop;
+} mpcqp_c2d_in;
+typedef struct mpcqp_c2d_out {
+    double *Ahat, *Bu, *C, *Bd, *Dd, *dop;
+} mpcqp_c2d_out;
+int mpcqp_c2d_sizes(const mpcqp_c2d_spec* spec, int32_t* nx_dis, int32_t* nxhat);
+int mpcqp_c2d(const mpcqp_c2d_spec* spec, const mpcqp_c2d_in* in, const mpcqp_c2d_out* out, int32_t* status);
+int mpcqp_c2d_device(const mpcqp_c2d_spec* spec, const mpcqp_c2d_in* in, const mpcqp_c2d_out* out, int32_t* status, void* stream);
+int mpcqp_set_model_continuous(mpcqp_handle h, const mpcqp_c2d_spec* spec, const mpcqp_c2d_in* in, int32_t* status);
+int mpcqp_set_model_continuous_device(mpcqp_handle h, const mpcqp_c2d_spec* spec, const mpcqp_c2d_in* in, int32_t* status,
+                                      void* stream);
 
 /* ---- ExplicitMPC (src/controller/explicitmpc.jl): the unconstrained LinMPC, H̃ factored once, Z̃ = -H̃⁻¹ q̃ every period ------
  * Two per-period paths on the handle of a controller WITHOUT constraints, beside mpcqp_step (which goes on working):

@@ -323,6 +323,78 @@ function pull_luenberger(b::BatchLinMPC)
 end
 
 # ------------------------------------------------------------------------------------------------
+# Continuous-time models (include/mpcqp.h, "LinModel(sys, Ts) and augment_model for the whole batch"): what LinModel(sys, Ts)
+# and augment_model do per model on the host, for every member in one launch.  Declarations only: not run here.
+struct C2dSpec                         # == mpcqp_c2d_spec
+    batch::Cint; nx::Cint; nu::Cint; ny::Cint; nd::Cint; nym::Cint; d_method::Cint     # d_method: 0 Tustin, 1 zero-order hold
+    nint_u::Ptr{Cint}; nint_ym::Ptr{Cint}; i_ym::Ptr{Cint}                             # C_NULL: none / none / 1:nym
+end
+struct C2dIn                           # == mpcqp_c2d_in; Bd, Dd: nd > 0; dop = fop - xop (nx_dis, B) or C_NULL
+    A::Ptr{Float64}; Bu::Ptr{Float64}; C::Ptr{Float64}; Bd::Ptr{Float64}; Dd::Ptr{Float64}; Ts::Ptr{Float64}; dop::Ptr{Float64}
+end
+struct C2dOut                          # == mpcqp_c2d_out
+    Â::Ptr{Float64}; B̂u::Ptr{Float64}; Ĉ::Ptr{Float64}; B̂d::Ptr{Float64}; D̂d::Ptr{Float64}; dop::Ptr{Float64}
+end
+
+"(nx_dis, nx̂) of a discretisation: nx_dis = 2nx with the Tustin block, nx̂ = nx_dis + sum(nint_u) + sum(nint_ym)."
+function c2d_sizes(spec::C2dSpec)
+    nxd, nx̂ = Ref{Cint}(0), Ref{Cint}(0)
+    check(ccall((:mpcqp_c2d_sizes, lib), Cint, (Ref{C2dSpec}, Ref{Cint}, Ref{Cint}), spec, nxd, nx̂))
+    return Int(nxd[]), Int(nx̂[])
+end
+
+"""
+    c2d(A, Bu, C, Ts; Bd, Dd, nint_u, nint_ym, i_ym, d_method=:tustin) -> (; Â, B̂u, Ĉ, B̂d, D̂d, status)
+
+Discretise and augment a batch of continuous-time models: A (nx, nx, B), Bu (nx, nu, B), C (ny, nx, B), Bd (nx, nd, B),
+Dd (ny, nd, B), Ts (B).  `i_ym` is one-based.  status 2: the member was refused and its slices are zero.
+"""
+function c2d(A::Array{Float64,3}, Bu::Array{Float64,3}, C::Array{Float64,3}, Ts::Vector{Float64};
+             Bd::Array{Float64,3}=zeros(size(A, 1), 0, size(A, 3)), Dd::Array{Float64,3}=zeros(size(C, 1), 0, size(A, 3)),
+             nint_u::Vector{<:Integer}=zeros(Int, size(Bu, 2)), nint_ym::Vector{<:Integer}=zeros(Int, size(C, 1)),
+             i_ym::Vector{<:Integer}=collect(1:length(nint_ym)), d_method::Symbol=:tustin)
+    nx, nu, B = size(Bu); ny, nd = size(C, 1), size(Bd, 2)
+    nu_, nym_, iy = Cint.(nint_u), Cint.(nint_ym), Cint.(i_ym .- 1)
+    st = zeros(Cint, B)
+    GC.@preserve nu_ nym_ iy A Bu C Bd Dd Ts begin
+        spec = C2dSpec(B, nx, nu, ny, nd, length(iy), d_method === :zoh ? 1 : 0, pointer(nu_), pointer(nym_), pointer(iy))
+        _, nx̂ = c2d_sizes(spec)
+        Â, B̂u, Ĉ, B̂d, D̂d = zeros(nx̂, nx̂, B), zeros(nx̂, nu, B), zeros(ny, nx̂, B), zeros(nx̂, nd, B), zeros(ny, nd, B)
+        p(M) = isempty(M) ? Ptr{Float64}(C_NULL) : pointer(M)
+        cin = C2dIn(pointer(A), pointer(Bu), pointer(C), p(Bd), p(Dd), pointer(Ts), C_NULL)
+        GC.@preserve Â B̂u Ĉ B̂d D̂d begin
+            cout = C2dOut(pointer(Â), pointer(B̂u), pointer(Ĉ), p(B̂d), p(D̂d), C_NULL)
+            check(ccall((:mpcqp_c2d, lib), Cint, (Ref{C2dSpec}, Ref{C2dIn}, Ref{C2dOut}, Ptr{Cint}), spec, cin, cout, st))
+        end
+    end
+    return (; Â, B̂u, Ĉ, B̂d, D̂d, status=st)
+end
+
+"`setmodel!` of the batch from continuous-time matrices (host arrays): the kernel writes the resident model, K1 and K2 follow.
+Estimator gains are not solved again (solve_steadykalmanfilter!, place_luenberger!).  Returns the per-member status."
+function setmodel_continuous!(b::BatchLinMPC, spec::C2dSpec, cin::C2dIn)
+    st = zeros(Cint, length(b.mpcs))
+    check(ccall((:mpcqp_set_model_continuous, lib), Cint, (Ptr{Cvoid}, Ref{C2dSpec}, Ref{C2dIn}, Ptr{Cint}), b.h, spec, cin, st))
+    return st
+end
+
+"The same with device pointers (`cin` and `status`), asynchronous on `stream`: no host synchronisation up to and including K2."
+setmodel_continuous_device!(b::BatchLinMPC, spec::C2dSpec, cin::C2dIn, status::Ptr{Cint}, stream::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:mpcqp_set_model_continuous_device, lib), Cint, (Ptr{Cvoid}, Ref{C2dSpec}, Ref{C2dIn}, Ptr{Cint}, Ptr{Cvoid}),
+                b.h, spec, cin, status, stream))
+
+"The resident model read back: (; Â, B̂u, Ĉ, B̂d, D̂d) in the layouts of mpcqp_set_model (MPCQP_GET_MODEL_*)."
+function pull_model(b::BatchLinMPC)
+    B, m = length(b.mpcs), b.mpcs[1]
+    e = m.estim
+    nu, ny, nd = e.model.nu, e.model.ny, e.model.nd
+    get(which, dims...) = (M = Array{Float64}(undef, dims...); check(ccall((:mpcqp_get, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), b.h, which, M)); M)
+    Â, B̂u, Ĉ = get(16, e.nx̂, e.nx̂, B), get(17, e.nx̂, nu, B), get(18, ny, e.nx̂, B)
+    B̂d, D̂d = nd > 0 ? (get(19, e.nx̂, nd, B), get(20, ny, nd, B)) : (zeros(e.nx̂, 0, B), zeros(ny, 0, B))
+    return (; Â, B̂u, Ĉ, B̂d, D̂d)
+end
+
+# ------------------------------------------------------------------------------------------------
 # InternalModel behind the batch (include/mpcqp.h, "InternalModel"): the stochastic model on the measured outputs goes to the
 # device once, Âs and B̂s are computed there; per period correct (ŷs, Ŷs, B + Ŷs for the steps), the unchanged step, update.
 # Call sequence = BatchLinMPC.setestimator(internal=...) of api.py; these ccalls have not been run.

@@ -5,7 +5,7 @@ The directory name carries a dot, so it is imported through the `mpcqp` alias pa
 repository root (`import mpcqp`), which points its `__path__` here.
 """
 from .api import (BatchLinMPC, BatchExplicitMPC, SimResult, Handle, MultiHandle, MpcqpError, load_library, move_blocking, colmajor,  # noqa: F401
-                  steady_kalman_gain,
+                  steady_kalman_gain, c2d, c2d_device, C2dOptions,
                   STATUS_OPTIMAL, STATUS_ITERATION_LIMIT, STATUS_ERROR, EXPORTS,
                   FLAG_RY_CONSTANT, FLAG_COLD_START, FLAG_KEEP_QP, FLAG_WARM_DUAL,
                   GET_HESSIAN, GET_STEPRESP, GET_KMAT, GET_BVEC, GET_QTILDE, GET_FVEC)

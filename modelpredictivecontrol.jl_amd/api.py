@@ -36,6 +36,9 @@ GET_HESSIAN, GET_STEPRESP, GET_KMAT, GET_BVEC, GET_QTILDE, GET_FVEC, GET_AUDIT, 
 GET_KF_COV, GET_KF_GAIN = 10, 11
 GET_EXPLICIT_LAW = 12
 GET_IM_XS, GET_IM_YS, GET_IM_YHATS = 13, 14, 15
+GET_MODEL_AHAT, GET_MODEL_BU, GET_MODEL_C, GET_MODEL_BD, GET_MODEL_DD, GET_MODEL_DOP = 16, 17, 18, 19, 20, 21
+C2D_TUSTIN, C2D_ZOH = 0, 1                       # mpcqp_c2d_spec.d_method
+C2D_OK, C2D_REFUSED = 0, 2                       # per-member status of mpcqp_c2d / mpcqp_set_model_continuous
 IM_STATUS_OK, IM_STATUS_SINGULAR = 0, 2          # mpcqp_im_status
 EXPLICIT_LAW = 1       # bit of mpcqp_explicit_prepare's with_law
 SIM_FLAG_RY_PER_PERIOD, SIM_FLAG_NO_FUSE = 1, 2     # mpcqp_sim_io.flags
@@ -55,6 +58,7 @@ EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_cre
            "mpcqp_explicit_prepare", "mpcqp_explicit_status", "mpcqp_explicit_step", "mpcqp_explicit_step_device",
            "mpcqp_explicit_law", "mpcqp_explicit_law_device",
            "mpcqp_sim_set_plant", "mpcqp_sim", "mpcqp_sim_device", "mpcqp_sim_path",
+           "mpcqp_set_model_continuous", "mpcqp_set_model_continuous_device",
            "mpcqp_im_set", "mpcqp_im_status", "mpcqp_im_correct", "mpcqp_im_correct_device", "mpcqp_im_update", "mpcqp_im_update_device",
            "mpcqp_set_output_weight_blocks", "mpcqp_set_dense_weights", "mpcqp_set_custom_constraints", "mpcqp_set_custom_bounds",
            "mpcqp_set_flags", "mpcqp_set_iteration_limit", "mpcqp_set_transcription", "mpcqp_transcription_supported", "mpcqp_set_current_setpoint", "mpcqp_prepare", "mpcqp_kernel_kind", "mpcqp_lds_bytes", "mpcqp_row_groups", "mpcqp_step_consts_builds", "mpcqp_prebuild",
@@ -63,6 +67,7 @@ EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_cre
            "mpcqp_multi_set_bounds", "mpcqp_multi_prepare", "mpcqp_multi_step", "mpcqp_multi_gather_device",
            "mpcqp_multi_scatter_device")
 
+_ct = C                     # (ctypes under a name that a parameter called C does not shadow)
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 
@@ -85,6 +90,19 @@ BOUND_FIELDS = ("U0min", "U0max", "DUmin", "DUmax", "Y0min", "Y0max", "x0min", "
 
 class Bounds(C.Structure):
     _fields_ = [(k, _dp) for k in BOUND_FIELDS]
+
+
+class C2dSpec(C.Structure):
+    """mpcqp_c2d_spec of include/mpcqp.h"""
+    _fields_ = [(k, C.c_int32) for k in ("batch", "nx", "nu", "ny", "nd", "nym", "d_method")] + [(k, _ip) for k in ("nint_u", "nint_ym", "i_ym")]
+
+
+class C2dIn(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("A", "Bu", "C", "Bd", "Dd", "Ts", "dop")]
+
+
+class C2dOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("Ahat", "Bu", "C", "Bd", "Dd", "dop")]
 
 
 SIM_IO_IN = ("ry", "Ru", "d", "u_step", "y_step", "d_step", "sigma_u", "sigma_y", "sigma_d", "sigma_x", "w_u", "w_y", "w_d", "w_x")
@@ -241,6 +259,12 @@ def load_library(path: str | None = None):
         lib.mpcqp_im_correct_device.argtypes = [C.c_void_p] * 5
         lib.mpcqp_im_update.argtypes = [C.c_void_p] * 4
         lib.mpcqp_im_update_device.argtypes = [C.c_void_p] * 5
+    if hasattr(lib, "mpcqp_c2d"):                  # (LinModel(sys, Ts) + augment_model on the device)
+        lib.mpcqp_c2d_sizes.argtypes = [C.POINTER(C2dSpec), _ip, _ip]
+        lib.mpcqp_c2d.argtypes = [C.POINTER(C2dSpec), C.POINTER(C2dIn), C.POINTER(C2dOut), C.c_void_p]
+        lib.mpcqp_c2d_device.argtypes = [C.POINTER(C2dSpec), C.POINTER(C2dIn), C.POINTER(C2dOut), C.c_void_p, C.c_void_p]
+        lib.mpcqp_set_model_continuous.argtypes = [C.c_void_p, C.POINTER(C2dSpec), C.POINTER(C2dIn), C.c_void_p]
+        lib.mpcqp_set_model_continuous_device.argtypes = [C.c_void_p, C.POINTER(C2dSpec), C.POINTER(C2dIn), C.c_void_p, C.c_void_p]
     lib.mpcqp_prepare.argtypes = [C.c_void_p]
     lib.mpcqp_kernel_kind.argtypes = [C.c_void_p]
     lib.mpcqp_lds_bytes.argtypes = [C.c_void_p]
@@ -284,6 +308,109 @@ def _ptr(a):
 def colmajor(M):
     """(B, rows, cols) logical -> the ABI's column-major-per-problem buffer (= Julia (rows,cols,B))."""
     return _f64(np.asarray(M, float).transpose(0, 2, 1))
+
+
+# -- LinModel(sys, Ts) + augment_model for a batch of continuous-time models (csrc/c2d_bodies.h)
+class C2dOptions:
+    """Dimensions and options of a discretisation, validated the way the reference validates them (init_integrators,
+    validate_ym: ValueError), and the mpcqp_c2d_spec that carries them.  `nint_u` / `nint_ym`: 0 (no integrator) or one count
+    per input / measured output; `nint_ym=None`: one per measured output, none when any nint_u != 0 (nothing is pruned: the
+    reference's default_nint checks observability per model, which cannot vary inside a batch of one shape)."""
+
+    def __init__(self, B, nx, nu, ny, nd, nint_u=0, nint_ym=0, i_ym=None, d_method="tustin"):
+        self.B, self.nx, self.nu, self.ny, self.nd = int(B), int(nx), int(nu), int(ny), int(nd)
+        iy = np.arange(ny) if i_ym is None else np.asarray(i_ym, int).reshape(-1)
+        if iy.size and (len(set(iy.tolist())) != iy.size or iy.min() < 0 or iy.max() >= ny):
+            raise ValueError("Measured output indices i_ym should contains valid and unique indices")
+        def counts(v, n, name):
+            a = np.zeros(n, int) if np.isscalar(v) and v == 0 else np.full(n, int(v)) if np.isscalar(v) else np.asarray(v, int).reshape(-1)
+            if a.size != n:
+                raise ValueError(f"nint_{name} length ({a.size}) ≠ n{name} ({n})")
+            if np.any(a < 0):
+                raise ValueError(f"nint_{name} values should be ≥ 0")
+            return a
+        self.nint_u = counts(nint_u, nu, "u")
+        if nint_ym is None:
+            nint_ym = 0 if self.nint_u.any() else 1
+        self.nint_ym = counts(nint_ym, iy.size, "ym")
+        if d_method not in ("tustin", "zoh"):
+            raise ValueError("d_method should be \"tustin\" or \"zoh\"")
+        self.d_method, self.i_ym = d_method, iy
+        self.tustin = nd > 0 and d_method == "tustin"
+        self.nxd = 2 * nx if self.tustin else nx
+        self.nxh = self.nxd + int(self.nint_u.sum()) + int(self.nint_ym.sum())
+        self._keep = [np.ascontiguousarray(a, np.int32) for a in (self.nint_u, self.nint_ym, iy)]
+        k = self._keep
+        self.spec = C2dSpec(batch=B, nx=nx, nu=nu, ny=ny, nd=nd, nym=iy.size, d_method=C2D_ZOH if d_method == "zoh" else C2D_TUSTIN,
+                            nint_u=k[0].ctypes.data_as(_ip), nint_ym=k[1].ctypes.data_as(_ip) if iy.size else None,
+                            i_ym=k[2].ctypes.data_as(_ip) if iy.size else None)
+
+
+def _c2d_inputs(A, Bu, Cm, Ts, Bd, Dd):
+    """(B,·,·) logical arrays -> ABI buffers; Ts scalar or (B,)."""
+    A, Bu, Cm, Bd, Dd = _c2d_batch(A, Bu, Cm, Bd, Dd)
+    B, nx, nu = Bu.shape
+    ny = Cm.shape[1]
+    if A.shape != (B, nx, nx) or Cm.shape != (B, ny, nx):
+        raise ValueError("DimensionMismatch between A, Bu, C")
+    nd = 0 if Bd is None else np.asarray(Bd).shape[2]
+    if nd > 0:
+        Bd = np.asarray(Bd, float)
+        Dd = np.zeros((B, ny, nd)) if Dd is None else np.asarray(Dd, float)
+        if Bd.shape != (B, nx, nd) or Dd.shape != (B, ny, nd):
+            raise ValueError("DimensionMismatch between A, Bd, Dd")
+    ts = np.broadcast_to(np.asarray(Ts, float), (B,)).copy()
+    bufs = [colmajor(A), colmajor(Bu), colmajor(Cm), colmajor(Bd) if nd > 0 else None, colmajor(Dd) if nd > 0 else None, ts]
+    return (B, nx, nu, ny, nd), bufs
+
+
+def _c2d_batch(*mats):
+    """A single model given without the batch axis (scalars included) gets one."""
+    def one(M):
+        if M is None:
+            return None
+        M = np.asarray(M, float)
+        return M if M.ndim == 3 else np.atleast_2d(M)[None]
+    return tuple(one(M) for M in mats)
+
+
+def c2d(A, Bu, C, Ts, Bd=None, Dd=None, *, nint_u=0, nint_ym=0, i_ym=None, d_method="tustin", dop=None, out=None, lib=None):
+    """`LinModel(sys, Ts)` + `augment_model` for a batch of continuous-time models (include/mpcqp.h: mpcqp_c2d): zero-order hold
+    for the manipulated inputs, Tustin (or, with d_method="zoh", zero-order hold) for the measured disturbances, the integrators
+    of nint_u / nint_ym appended.  A (B,nx,nx), Bu (B,nx,nu), C (B,ny,nx), Bd (B,nx,nd), Dd (B,ny,nd), Ts scalar or (B,).
+    Returns (Ahat, Bhu, Chat, Bhd, Dhd, status) with a leading batch axis (Bhd, Dhd None when nd = 0), and the padded dop
+    behind them when `dop` (B,nx_dis) is given.  A member with status 2 was refused: its slices hold zeros, or what `out` (a
+    tuple of arrays of the result's shapes, e.g. the model in use) held."""
+    lib = lib or load_library()
+    if not hasattr(lib, "mpcqp_c2d"):
+        raise NotImplementedError("this library has no mpcqp_c2d")
+    (B, nx, nu, ny, nd), bufs = _c2d_inputs(A, Bu, C, Ts, Bd, Dd)
+    o = C2dOptions(B, nx, nu, ny, nd, nint_u, nint_ym, i_ym, d_method)
+    nxh = o.nxh
+    shapes = [(B, nxh, nxh), (B, nu, nxh), (B, nxh, ny), (B, nd, nxh), (B, nd, ny)]       # (ABI: column-major per member)
+    res = [np.zeros(sh) for sh in shapes]
+    if out is not None:
+        for r_, src in zip(res, out):
+            if src is not None and r_.size:
+                r_[...] = np.asarray(src, float).transpose(0, 2, 1)
+    dopv = None if dop is None else _f64(np.broadcast_to(np.asarray(dop, float), (B, o.nxd)))
+    doph = None if dop is None else np.zeros((B, nxh))
+    status = np.zeros(B, np.int32)
+    cin = C2dIn(*[_ptr(b) for b in bufs], _ptr(dopv))
+    cout = C2dOut(_ptr(res[0]), _ptr(res[1]), _ptr(res[2]), _ptr(res[3]) if nd else None, _ptr(res[4]) if nd else None, _ptr(doph))
+    _chk(lib, lib.mpcqp_c2d(_ct.byref(o.spec), _ct.byref(cin), _ct.byref(cout), _ptr(status)))
+    mats = [np.ascontiguousarray(r_.transpose(0, 2, 1)) for r_ in res]
+    ret = (mats[0], mats[1], mats[2], mats[3] if nd else None, mats[4] if nd else None, status)
+    return ret if dop is None else ret + (doph,)
+
+
+def c2d_device(opts, A, Bu, C, Ts, Ahat, Bhu, Chat, status, Bd=0, Dd=0, dop=0, Bhd=0, Dhd=0, dophat=0, stream=0, lib=None):
+    """mpcqp_c2d_device: `opts` a C2dOptions, everything else raw device addresses in ABI layout; enqueued on `stream`."""
+    lib = lib or load_library()
+    v = lambda p: _ct.c_void_p(int(p)) if p else None
+    cin = C2dIn(*[v(p) for p in (A, Bu, C, Bd, Dd, Ts, dop)])
+    cout = C2dOut(*[v(p) for p in (Ahat, Bhu, Chat, Bhd, Dhd, dophat)])
+    _chk(lib, lib.mpcqp_c2d_device(_ct.byref(opts.spec), _ct.byref(cin), _ct.byref(cout), v(status), v(stream)))
 
 
 # -- SteadyKalmanFilter from Q̂ and R̂: the gain solved for on the device (csrc/kf_dare_bodies.h).  Methods of Handle, bound
@@ -404,6 +531,40 @@ class Handle:
     def set_model(self, Ahat, Bu, Cm, Bd=None, Dd=None, dop=None):
         args = [None if a is None else _f64(a) for a in (Ahat, Bu, Cm, Bd, Dd, dop)]
         _chk(self.lib, self.lib.mpcqp_set_model(self.h, *[_ptr(a) for a in args]))
+
+    def set_model_continuous(self, opts, A, Bu, Cm, Ts, Bd=None, Dd=None, dop=None):
+        """mpcqp_set_model_continuous: `opts` a C2dOptions, the arrays in ABI layout (host).  Returns status (B,) int32."""
+        if not hasattr(self.lib, "mpcqp_set_model_continuous"):
+            raise NotImplementedError("this library has no mpcqp_set_model_continuous")
+        args = [None if a is None else _f64(a) for a in (A, Bu, Cm, Bd, Dd, Ts, dop)]
+        cin = C2dIn(*[_ptr(a) for a in args])
+        st = np.zeros(self.B, np.int32)
+        _chk(self.lib, self.lib.mpcqp_set_model_continuous(self.h, C.byref(opts.spec), C.byref(cin), _ptr(st)))
+        return st
+
+    def set_model_continuous_device(self, opts, A, Bu, Cm, Ts, status, Bd=0, Dd=0, dop=0, stream=0):
+        """mpcqp_set_model_continuous_device: raw device addresses; the launch, K1, K2 and the refreshes are enqueued on `stream`."""
+        if not hasattr(self.lib, "mpcqp_set_model_continuous_device"):
+            raise NotImplementedError("this library has no mpcqp_set_model_continuous_device")
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        cin = C2dIn(*[v(p) for p in (A, Bu, Cm, Bd, Dd, Ts, dop)])
+        _chk(self.lib, self.lib.mpcqp_set_model_continuous_device(self.h, C.byref(opts.spec), C.byref(cin), v(status), v(stream)))
+
+    def get_model(self):
+        """The resident model read back: (Ahat, Bhu, Chat, Bhd, Dhd, dop) with a leading batch axis (Bhd, Dhd None when nd = 0)."""
+        shapes = {GET_MODEL_AHAT: (self.nxhat, self.nxhat), GET_MODEL_BU: (self.nu, self.nxhat), GET_MODEL_C: (self.nxhat, self.ny),
+                  GET_MODEL_BD: (self.nd, self.nxhat), GET_MODEL_DD: (self.nd, self.ny)}
+        res = []
+        for which, sh in shapes.items():
+            if self.nd == 0 and which in (GET_MODEL_BD, GET_MODEL_DD):
+                res.append(None)
+                continue
+            out = np.empty((self.B,) + sh)
+            _chk(self.lib, self.lib.mpcqp_get(self.h, which, _ptr(out)))
+            res.append(np.ascontiguousarray(out.transpose(0, 2, 1)))
+        dop = np.empty((self.B, self.nxhat))
+        _chk(self.lib, self.lib.mpcqp_get(self.h, GET_MODEL_DOP, _ptr(dop)))
+        return tuple(res) + (dop,)
 
     def set_weights(self, Mdiag, Ndiag, Ldiag, Cwt=None):
         args = [None if a is None else _f64(a) for a in (Mdiag, Ndiag, Ldiag, Cwt)]
@@ -1082,6 +1243,10 @@ class BatchLinMPC:
                           None if self.nd == 0 else colmajor(Bhd),
                           None if self.nd == 0 else colmajor(Dhd),
                           dopv if np.any(dopv != 0) else None)
+        self._model_changed()
+
+    def _model_changed(self):
+        """What follows a new resident model: the estimator gains that are solved from it, and the attached estimator."""
         if getattr(self, "kf_steady", False):      # SteadyKalmanFilter from Q̂ and R̂: the gain follows the model
             self.hd.kf_solve_steady()
             self._warn_steady()
@@ -1093,6 +1258,64 @@ class BatchLinMPC:
             ops = self.__dict__.pop("_mhe_ops", {})
             est.setmodel(self._Ahat, self._Bhu, self._Chat[:, self.i_ym], self._Bhd,
                          None if self.nd == 0 else self._Dhd[:, self.i_ym], **ops)
+
+    # -- continuous-time models: LinModel(sys, Ts) + augment_model on the device (csrc/c2d_bodies.h) --------------
+    @classmethod
+    def from_continuous(cls, A, Bu, C, Ts, Bd=None, Dd=None, *, nint_u=0, nint_ym=None, i_ym=None, d_method="tustin",
+                        xop=None, fop=None, lib=None, **kw):
+        """`LinMPC(LinModel(sys, Ts))` for a batch of continuous-time models: A (B,nx,nx), Bu (B,nx,nu), C (B,ny,nx), Bd
+        (B,nx,nd), Dd (B,ny,nd) (a single model may come without the batch axis, scalars included), Ts scalar or (B,).  Every
+        member is discretised on the device -- zero-order hold for the manipulated inputs, Tustin for the measured
+        disturbances (linmodel.jl:165-198; d_method="zoh": zero-order hold for them too, one state vector) -- and augmented
+        with the integrators of nint_u / nint_ym (construct.jl:305-323; nint_ym=None: one per measured output, none when any
+        nint_u != 0; nothing is pruned, there is no sminreal / minreal).  `xop` / `fop` (nx_dis values) are padded with zeros
+        to x̂op / f̂op.  The other keywords are the constructor's.  `c2d_status` holds the per-member status: a member with
+        2 was refused (one RuntimeWarning with the count) and has a zero model."""
+        (B, nx, nu, ny, nd), _ = _c2d_inputs(A, Bu, C, Ts, Bd, Dd)
+        o = C2dOptions(B, nx, nu, ny, nd, nint_u, nint_ym, i_ym, d_method)
+        A, Bu, C, Bd, Dd = _c2d_batch(A, Bu, C, Bd, Dd)
+        Ah, Bh, Ch, Bdh, Ddh, st = c2d(A, Bu, C, Ts, Bd, Dd, nint_u=o.nint_u, nint_ym=o.nint_ym, i_ym=o.i_ym, d_method=d_method, lib=lib)
+        pad = lambda v: None if v is None else np.hstack([np.broadcast_to(np.asarray(v, float), (B, o.nxd)), np.zeros((B, o.nxh - o.nxd))])
+        self = cls(Ah, Bh, Ch, Bdh, Ddh, xhop=pad(xop), fhop=pad(fop), lib=lib, **kw)
+        self._c2d_opts, self.c2d_status = o, st
+        self._warn_c2d()
+        return self
+
+    def setmodel_continuous(self, A, Bu, C, Ts, Bd=None, Dd=None, *, nint_u=None, nint_ym=None, i_ym=None, d_method=None,
+                            xop=None, fop=None):
+        """`setmodel!` from continuous-time matrices: the discretisation and augmentation of `from_continuous`, written by the
+        kernel straight into the resident model, then the re-condensation -- one call, nothing computed on the host -- and
+        everything `setmodel` does once the model is in place (the steady gain solved again, the poles placed again, an
+        attached MovingHorizonEstimator handed the new model, x̂op / f̂op).  The options default to those of `from_continuous`.
+        A refused member (status 2 in `c2d_status`, one RuntimeWarning with the count) keeps the model it had."""
+        (B, nx, nu, ny, nd), bufs = _c2d_inputs(A, Bu, C, Ts, Bd, Dd)
+        prev = getattr(self, "_c2d_opts", None)
+        pick = lambda v, name, default: v if v is not None else (getattr(prev, name) if prev is not None else default)
+        o = C2dOptions(B, nx, nu, ny, nd, pick(nint_u, "nint_u", 0), nint_ym if nint_ym is not None or prev is None else prev.nint_ym,
+                       pick(i_ym, "i_ym", None), pick(d_method, "d_method", "tustin"))
+        if (B, o.nxh, nu, ny, nd) != (self.B, self.nxh, self.nu, self.ny, self.nd):
+            raise ValueError("DimensionMismatch between the continuous model with its integrators and the controller")
+        pad = lambda v: np.hstack([np.broadcast_to(np.asarray(v, float), (B, o.nxd)), np.zeros((B, o.nxh - o.nxd))])
+        if xop is not None:
+            new = pad(xop)
+            if getattr(self, "mhe", None) is None and "_xhat0" in self.__dict__:
+                self.xhat0 = self.xhat0 + self.xhop - new
+            self.xhop = new
+        if fop is not None:
+            self.fhop = pad(fop)
+        dopv = (self.fhop - self.xhop)[:, :o.nxd]
+        st = self.hd.set_model_continuous(o, *bufs[:3], bufs[5], bufs[3], bufs[4], _f64(dopv) if np.any(dopv != 0) else None)
+        self._Ahat, self._Bhu, self._Chat, self._Bhd, self._Dhd, _ = self.hd.get_model()     # (the mirrors: what the device produced)
+        self._c2d_opts, self.c2d_status = o, st
+        self._warn_c2d()
+        self._model_changed()
+
+    def _warn_c2d(self):
+        """One warning for the members whose continuous model could not be discretised."""
+        n = int(np.count_nonzero(self.c2d_status))
+        if n:
+            warnings.warn("Cannot discretise the continuous model: a value is not finite, Ts is not positive or I - Ts/2 A is "
+                          f"singular, the previous model (or zero) stays ({n} of {self.B} controllers)", RuntimeWarning)
 
     def setweights(self, Mwt=None, Nwt=None, Lwt=None, M_Hp=None, N_Hc=None, L_Hp=None):
         """Defaults of src/general.jl:3-6 (Mwt=1, Nwt=0.1, Lwt=0).  `M_Hp` (nY,nY), `N_Hc` (nΔU,nΔU), `L_Hp`

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mpcqp_mhe.h"
+#include "c2d_launch.h"
 #include "est_init_launch.h"
 #include "explicit_launch.h"
 #include "im_launch.h"
@@ -127,6 +128,8 @@ struct mpcqp_handle_s {
     bool in_multi = false;      // a shard of mpcqp_multi_create
     int im_nxs = 0;
     DBuf im_As, im_Bs, im_Cs, im_Ds, im_Ahs, im_Bhs, im_xs, im_ys, im_Yhs, im_Beff, im_z, im_st;
+    // mpcqp_set_model_continuous: staging of the host-pointer call (A, Bu, C, Bd, Dd, Ts, dop) and the status of the kernel
+    DBuf c2d_s[7], c2d_st;
 };
 
 static int dev_alloc(mpcqp_handle h, DBuf& b, size_t bytes) {
@@ -938,6 +941,199 @@ int mpcqp_recondense_device(mpcqp_handle h, void* stream) {
     return rc ? rc : explicit_refresh(h, (hipStream_t)stream);
 }
 
+// ---- LinModel(sys, Ts) + augment_model for the whole batch (linmodel.jl:165-198, construct.jl:305-323; c2d_bodies.h) ----
+
+// Dimensions, options and the table of stochastic states of a call; everything but the arrays of C2dArgs.
+static int c2d_fill(const mpcqp_c2d_spec* s, c2d::C2dArgs& a) {
+    if (!s) return MPCQP_ERR_NULL;
+    if (s->batch < 1 || s->nx < 1 || s->nu < 1 || s->ny < 1 || s->nd < 0 || s->nym < 0 || s->nym > s->ny) return MPCQP_ERR_DIMS;
+    if (s->d_method != MPCQP_C2D_TUSTIN && s->d_method != MPCQP_C2D_ZOH) return MPCQP_ERR_ARG;
+    if (s->nint_ym && s->nym < 1) return MPCQP_ERR_DIMS;
+    a.B = s->batch; a.nx = s->nx; a.nu = s->nu; a.ny = s->ny; a.nd = s->nd;
+    a.method = s->d_method == MPCQP_C2D_ZOH ? c2d::C2D_ZOH : c2d::C2D_TUSTIN;
+    long nsu = 0, nsy = 0;
+    for (int i = 0; s->nint_u && i < s->nu; ++i) {
+        if (s->nint_u[i] < 0) return MPCQP_ERR_ARG;
+        nsu += s->nint_u[i];
+    }
+    for (int i = 0; i < s->nym; ++i) {
+        const int q = s->i_ym ? s->i_ym[i] : i;
+        if (q < 0 || q >= s->ny) return MPCQP_ERR_ARG;          // validate_ym, construct.jl:188-194
+        for (int j = 0; j < i; ++j)
+            if ((s->i_ym ? s->i_ym[j] : j) == q) return MPCQP_ERR_ARG;
+        if (s->nint_ym) {
+            if (s->nint_ym[i] < 0) return MPCQP_ERR_ARG;
+            nsy += s->nint_ym[i];
+        }
+    }
+    const bool tust = a.nd > 0 && a.method == c2d::C2D_TUSTIN;
+    const long nxd = tust ? 2L * a.nx : a.nx, nxh = nxd + nsu + nsy;
+    if (nxh > c2d::C2D_NXH_MAX || nsu + nsy > c2d::C2D_NXH_MAX) return MPCQP_ERR_UNSUPPORTED;
+    a.nsu = (int)nsu; a.nsy = (int)nsy; a.nxd = (int)nxd; a.nxh = (int)nxh;
+    if (!c2d::c2d_supported(a) || !c2d::c2d_available()) return MPCQP_ERR_UNSUPPORTED;
+    int p = 0;
+    for (int i = 0; s->nint_u && i < s->nu; ++i)
+        for (int k = 0; k < s->nint_u[i]; ++k, ++p) {
+            a.s_in[p] = (signed char)(k == s->nint_u[i] - 1 ? i : -1);
+            a.s_out[p] = -1;
+            a.s_prev[p] = k > 0;
+        }
+    for (int i = 0; s->nint_ym && i < s->nym; ++i)
+        for (int k = 0; k < s->nint_ym[i]; ++k, ++p) {
+            a.s_in[p] = -1;
+            a.s_out[p] = (signed char)(k == s->nint_ym[i] - 1 ? (s->i_ym ? s->i_ym[i] : i) : -1);
+            a.s_prev[p] = k > 0;
+        }
+    return MPCQP_OK;
+}
+
+static bool c2d_in_ok(const c2d::C2dArgs& a, const mpcqp_c2d_in* in) {
+    return in && in->A && in->Bu && in->C && in->Ts && (a.nd == 0 || (in->Bd && in->Dd));
+}
+
+int mpcqp_c2d_sizes(const mpcqp_c2d_spec* spec, int32_t* nx_dis, int32_t* nxhat) {
+    c2d::C2dArgs a{};
+    const int rc = c2d_fill(spec, a);
+    if (rc && rc != MPCQP_ERR_UNSUPPORTED) return rc;
+    if (rc && a.nxh == 0) return rc;                            // (beyond 64 states: no size to report)
+    if (nx_dis) *nx_dis = a.nxd;
+    if (nxhat) *nxhat = a.nxh;
+    return rc;
+}
+
+int mpcqp_c2d_device(const mpcqp_c2d_spec* spec, const mpcqp_c2d_in* in, const mpcqp_c2d_out* out, int32_t* status, void* stream) {
+    c2d::C2dArgs a{};
+    if (!spec || !in || !out || !status) return MPCQP_ERR_NULL;
+    int rc = c2d_fill(spec, a);
+    if (rc) return rc;
+    if (!c2d_in_ok(a, in) || !out->Ahat || !out->Bu || !out->C || (a.nd > 0 && (!out->Bd || !out->Dd)) || (in->dop && !out->dop))
+        return MPCQP_ERR_NULL;
+    a.A = in->A; a.Bu = in->Bu; a.C = in->C; a.Bd = in->Bd; a.Dd = in->Dd; a.Ts = in->Ts; a.dop = in->dop;
+    a.Ahat = out->Ahat; a.Bhu = out->Bu; a.Chat = out->C; a.Bhd = out->Bd; a.Dhd = out->Dd;
+    a.dophat = in->dop ? out->dop : nullptr;
+    a.status = status;
+    HIPCHK(c2d::launch_c2d(a, (hipStream_t)stream));
+    return MPCQP_OK;
+}
+
+int mpcqp_c2d(const mpcqp_c2d_spec* spec, const mpcqp_c2d_in* in, const mpcqp_c2d_out* out, int32_t* status) {
+    c2d::C2dArgs a{};
+    if (!spec || !in || !out || !status) return MPCQP_ERR_NULL;
+    int rc = c2d_fill(spec, a);
+    if (rc) return rc;
+    if (!c2d_in_ok(a, in) || !out->Ahat || !out->Bu || !out->C || (a.nd > 0 && (!out->Bd || !out->Dd)) || (in->dop && !out->dop))
+        return MPCQP_ERR_NULL;
+    const size_t B = a.B, sz = sizeof(double);
+    // device copies of the inputs and of the outputs AS THE CALLER HAS THEM: a refused member's outputs come back unchanged
+    struct Tmp {
+        std::vector<void*> p;
+        ~Tmp() { for (void* q : p) (void)hipFree(q); }
+    } tmp;
+    auto dev = [&](const void* src, size_t bytes, void** dst) -> int {
+        *dst = nullptr;
+        if (!src) return MPCQP_OK;
+        hipError_t e = hipMalloc(dst, bytes ? bytes : 8);
+        if (e != hipSuccess) { g_hip_err = std::string("hipMalloc: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? MPCQP_ERR_NOMEM : MPCQP_ERR_DEVICE; }
+        tmp.p.push_back(*dst);
+        HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+        return MPCQP_OK;
+    };
+    const size_t nin[7] = {B * a.nx * a.nx * sz, B * a.nx * a.nu * sz, B * a.ny * a.nx * sz, B * a.nx * a.nd * sz, B * a.ny * a.nd * sz,
+                           B * sz, B * a.nxd * sz};
+    const size_t nout[6] = {B * a.nxh * a.nxh * sz, B * a.nxh * a.nu * sz, B * a.ny * a.nxh * sz, B * a.nxh * a.nd * sz,
+                            B * a.ny * a.nd * sz, B * a.nxh * sz};
+    const void* hin[7] = {in->A, in->Bu, in->C, a.nd > 0 ? in->Bd : nullptr, a.nd > 0 ? in->Dd : nullptr, in->Ts, in->dop};
+    void* hout[6] = {out->Ahat, out->Bu, out->C, a.nd > 0 ? out->Bd : nullptr, a.nd > 0 ? out->Dd : nullptr, in->dop ? out->dop : nullptr};
+    void *din[7], *dout[6], *dst = nullptr;
+    for (int i = 0; i < 7 && !rc; ++i) rc = dev(hin[i], nin[i], &din[i]);
+    for (int i = 0; i < 6 && !rc; ++i) rc = dev(hout[i], nout[i], &dout[i]);
+    if (!rc) rc = dev(status, B * sizeof(int32_t), &dst);
+    if (rc) return rc;
+    mpcqp_c2d_in di{(const double*)din[0], (const double*)din[1], (const double*)din[2], (const double*)din[3], (const double*)din[4],
+                    (const double*)din[5], (const double*)din[6]};
+    mpcqp_c2d_out dout_{(double*)dout[0], (double*)dout[1], (double*)dout[2], (double*)dout[3], (double*)dout[4], (double*)dout[5]};
+    rc = mpcqp_c2d_device(spec, &di, &dout_, (int32_t*)dst, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    for (int i = 0; i < 6; ++i)
+        if (hout[i]) HIPCHK(hipMemcpy(hout[i], dout[i], nout[i], hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(status, dst, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MPCQP_OK;
+}
+
+int mpcqp_set_model_continuous_device(mpcqp_handle h, const mpcqp_c2d_spec* spec, const mpcqp_c2d_in* in, int32_t* status, void* stream) {
+    if (!h || !spec || !in || !status) return MPCQP_ERR_NULL;
+    c2d::C2dArgs a{};
+    int rc = c2d_fill(spec, a);
+    if (rc) return rc;
+    const Dims& d = h->d;
+    if (a.B != d.B || a.nxh != d.nxh || a.nu != d.nu || a.ny != d.ny || a.nd != d.nd) return MPCQP_ERR_ARG;
+    if (h->in_multi) return MPCQP_ERR_UNSUPPORTED;
+    if (!c2d_in_ok(a, in)) return MPCQP_ERR_NULL;
+    ON_DEVICE(h);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t B = d.B, sz = sizeof(double);
+    const bool first = !h->have_model;                          // (no model to keep: a refused member then has a zero model)
+    struct { DBuf* b; size_t n; bool on; } bufs[6] = {
+        {&h->Ahat, B * d.nxh * d.nxh * sz, true}, {&h->Bu, B * d.nxh * d.nu * sz, true}, {&h->C, B * d.ny * d.nxh * sz, true},
+        {&h->Bd, B * d.nxh * d.nd * sz, d.nd > 0}, {&h->Dd, B * d.ny * d.nd * sz, d.nd > 0}, {&h->dop, B * d.nxh * sz, in->dop != nullptr}};
+    for (auto& e : bufs) {
+        if (!e.on) continue;
+        const bool fresh = !e.b->p || e.b->bytes < e.n;
+        rc = dev_alloc(h, *e.b, e.n);
+        if (rc) return rc;
+        if (first || fresh) HIPCHK(hipMemsetAsync(e.b->p, 0, e.n, st));
+    }
+    if (h->step_timed) HIPCHK(hipStreamWaitEvent(st, h->ev_s1, 0));    // (a step on another stream may still read the model)
+    a.A = in->A; a.Bu = in->Bu; a.C = in->C; a.Bd = in->Bd; a.Dd = in->Dd; a.Ts = in->Ts; a.dop = in->dop;
+    a.Ahat = (double*)h->Ahat.p; a.Bhu = (double*)h->Bu.p; a.Chat = (double*)h->C.p;
+    a.Bhd = d.nd > 0 ? (double*)h->Bd.p : nullptr; a.Dhd = d.nd > 0 ? (double*)h->Dd.p : nullptr;
+    a.dophat = in->dop ? (double*)h->dop.p : nullptr;
+    a.status = status;
+    HIPCHK(c2d::launch_c2d(a, st));
+    h->m.Ahat = (const double*)h->Ahat.p; h->m.Bu = (const double*)h->Bu.p; h->m.C = (const double*)h->C.p;
+    h->m.Bd = d.nd > 0 ? (const double*)h->Bd.p : nullptr;
+    h->m.Dd = d.nd > 0 ? (const double*)h->Dd.p : nullptr;
+    h->m.dop = in->dop ? (const double*)h->dop.p : nullptr;
+    h->have_model = true;
+    invalidate_stepc(h);
+    rc = condense(h, st, true);
+    if (!rc) rc = im_refresh(h, st);
+    return rc ? rc : explicit_refresh(h, st);
+}
+
+int mpcqp_set_model_continuous(mpcqp_handle h, const mpcqp_c2d_spec* spec, const mpcqp_c2d_in* in, int32_t* status) {
+    if (!h || !spec || !in || !status) return MPCQP_ERR_NULL;
+    c2d::C2dArgs a{};
+    int rc = c2d_fill(spec, a);
+    if (rc) return rc;
+    const Dims& d = h->d;
+    if (a.B != d.B || a.nxh != d.nxh || a.nu != d.nu || a.ny != d.ny || a.nd != d.nd) return MPCQP_ERR_ARG;
+    if (h->in_multi) return MPCQP_ERR_UNSUPPORTED;
+    if (!c2d_in_ok(a, in)) return MPCQP_ERR_NULL;
+    ON_DEVICE(h);
+    const size_t B = d.B, sz = sizeof(double);
+    const size_t nin[7] = {B * a.nx * a.nx * sz, B * a.nx * a.nu * sz, B * a.ny * a.nx * sz, B * a.nx * a.nd * sz, B * a.ny * a.nd * sz,
+                           B * sz, B * a.nxd * sz};
+    const void* hin[7] = {in->A, in->Bu, in->C, a.nd > 0 ? in->Bd : nullptr, a.nd > 0 ? in->Dd : nullptr, in->Ts, in->dop};
+    const double* din[7];
+    for (int i = 0; i < 7; ++i) {
+        din[i] = nullptr;
+        if (!hin[i]) continue;
+        rc = upload(h, h->c2d_s[i], hin[i], nin[i]);
+        if (rc) return rc;
+        din[i] = (const double*)h->c2d_s[i].p;
+    }
+    rc = dev_alloc(h, h->c2d_st, B * sizeof(int32_t));
+    if (rc) return rc;
+    mpcqp_c2d_in di{din[0], din[1], din[2], din[3], din[4], din[5], din[6]};
+    rc = mpcqp_set_model_continuous_device(h, spec, &di, (int32_t*)h->c2d_st.p, h->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(status, h->c2d_st.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
 int mpcqp_get(mpcqp_handle h, int which, double* out) {
     if (!h || !out) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
@@ -1042,8 +1238,25 @@ int mpcqp_get(mpcqp_handle h, int which, double* out) {
                     out[(R / n) * (size_t)n * ncol + (size_t)k * n + R % n] = tmp[ex::law_index(R, k, kp)];
             return MPCQP_OK;
         }
+        case MPCQP_GET_MODEL_AHAT: case MPCQP_GET_MODEL_BU: case MPCQP_GET_MODEL_C: case MPCQP_GET_MODEL_BD: case MPCQP_GET_MODEL_DD:
+        case MPCQP_GET_MODEL_DOP: {
+            if (!h->have_model) return MPCQP_ERR_ORDER;
+            const void* src = which == MPCQP_GET_MODEL_AHAT ? h->m.Ahat : which == MPCQP_GET_MODEL_BU ? h->m.Bu
+                            : which == MPCQP_GET_MODEL_C ? h->m.C : which == MPCQP_GET_MODEL_BD ? h->m.Bd
+                            : which == MPCQP_GET_MODEL_DD ? h->m.Dd : h->m.dop;
+            const size_t n = which == MPCQP_GET_MODEL_AHAT ? (size_t)d.nxh * d.nxh : which == MPCQP_GET_MODEL_BU ? (size_t)d.nxh * d.nu
+                           : which == MPCQP_GET_MODEL_C ? (size_t)d.ny * d.nxh : which == MPCQP_GET_MODEL_BD ? (size_t)d.nxh * d.nd
+                           : which == MPCQP_GET_MODEL_DD ? (size_t)d.ny * d.nd : (size_t)d.nxh;
+            if (!src) {                                     // (no measured disturbance: nothing to read; no f̂op - x̂op: zeros)
+                if (which != MPCQP_GET_MODEL_DOP) return MPCQP_ERR_ARG;
+                std::fill(out, out + B * n, 0.0);
+                return MPCQP_OK;
+            }
+            HIPCHK(hipMemcpy(out, src, B * n * sizeof(double), hipMemcpyDeviceToHost));
+            return MPCQP_OK;
+        }
 #ifdef MPCQP_PROFILE
-        case 99:     /* per-phase cycle counters of profiling builds (-DMPCQP_PROFILE): (16,B) */
+        case 99:    /* per-phase cycle counters of profiling builds (-DMPCQP_PROFILE): (16,B) */
             if (!h->prof.p) return MPCQP_ERR_ORDER;
             HIPCHK(hipMemcpy(out, h->prof.p, B * 16 * sizeof(double), hipMemcpyDeviceToHost));
             return MPCQP_OK;
