@@ -498,7 +498,7 @@ int mpcqp_kf_lanes_per_estimator(mpcqp_handle h);
  * delay states, a σQ with zeros).  The solve makes two passes over the batch: the first inverts H(k) (H(0) = Q̂) without
  * pivoting, which serves a definite Q̂; an estimator it leaves broken down, or whose Q̂ is numerically singular (smallest
  * pivot <= 1e-10 max diag Q̂), is solved again by the square-root form of
- * the same iteration (csrc/kf_dare_psd_bodies.h: H(k) = L L' without pivoting, columns of pivots <= 0 dropped,
+ * the same iteration (csrc/kf_dare_bodies.h, its square-root form: H(k) = L L' without pivoting, columns of pivots <= 0 dropped,
  * S = L (I + L'GL)⁻¹ L').  There a pivot of H(k) below -1e-8 max(1, max diag H(k)) is no rounding: an indefinite Q̂ keeps
  * status 2.  A build without the second pass (the kernel is missing) gives a semidefinite Q̂ status 2, as before.
  *

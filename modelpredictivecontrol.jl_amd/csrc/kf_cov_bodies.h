@@ -38,6 +38,30 @@
 namespace mpcqp {
 namespace kf {
 
+// Ĉm: the measured rows of Ĉ [ny x nx], lane r holds the row of measured output r (row my = i_ym[r] of Ĉ) ...
+template <int NX>
+MPCQP_HD void ld_cm(const double* Cb, int my, int ny, int nym, int nx, int r, double (&M)[NX]) {
+    mhe::sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; M[c] = (r < nym && c < nx) ? Cb[my + ny * c] : 0.0; });
+}
+// ... and Ĉm': lane r holds the row of state r, column c is measured output c
+template <int NX>
+MPCQP_HD void ld_cmt(const double* Cb, const int* i_ym, int ny, int nym, int nx, int r, double (&M)[NX]) {
+    mhe::sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; M[c] = (r < nx && c < nym) ? Cb[i_ym[c] + ny * r] : 0.0; });
+}
+
+// K̂ = P̂ Ĉm' (Ĉm P̂ Ĉm' + R̂)⁻¹ in the order of operations of correct_estimate_kf!.  M: in R̂ (the identity in the padding), out
+// M̂⁻¹;  PC: out P̂ Ĉm' (row = state, column = output).  false: a pivot of the LDL' of M̂ is not in (0, inf).
+template <class W, int NX>
+MPCQP_HD bool kf_gain(const mhe::Ops<W, NX>& op, int r, const double (&P)[NX], const double (&Cm)[NX], double (&M)[NX],
+                      double (&PC)[NX], double (&K)[NX]) {
+    mhe::sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; PC[c] = 0.0; });
+    op.mmt_acc(P, Cm, PC, 1.0);            // P̂ Ĉm'
+    op.mm_add(Cm, PC, M);                  // M̂ = R̂ + Ĉm (P̂ Ĉm')
+    const bool good = op.gj(M, r);         // M̂⁻¹
+    op.mm(PC, M, K);                       // K̂ = (P̂ Ĉm') M̂⁻¹
+    return good;
+}
+
 template <class W, int NX>
 MPCQP_HD void kf_cov_body(W& w, const CovArgs& a, int mode, int wave_id) {
     using O = mhe::Ops<W, NX>;
@@ -48,8 +72,6 @@ MPCQP_HD void kf_cov_body(W& w, const CovArgs& a, int mode, int wave_id) {
     const int lane = w.lane, r = lane & (RL - 1), g = lane / RL;
     const int nx = a.nx, ny = a.ny, nym = a.nym;
     const int my = r < nym ? a.i_ym[r] : 0;            // the row of Ĉ this lane holds as row r of Ĉm
-    // 1 on the lanes that own a row of the padded NX x NX operands (the others carry copies or zeros nobody reads)
-    const double idle = r < NX ? 0.0 : 1.0;
     for (int wg = wave_id; wg * GPW < a.B; wg += a.nwaves) {
         const int bq = wg * GPW + g;
         const bool live = bq < a.B;
@@ -60,7 +82,7 @@ MPCQP_HD void kf_cov_body(W& w, const CovArgs& a, int mode, int wave_id) {
         const double* Rb = a.R + (size_t)b * nym * nym;
         double* Pb = a.P + (size_t)b * nx * nx;
         double* Kb = a.K + (size_t)b * nym * nx;
-        sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; P[c] = (r < nx && c < nx) ? Pb[c * nx + r] : 0.0; });
+        O::ld_sq(Pb, nx, r, 0.0, P);
         bool dropped = false, changed = false;
         if (mode & COV_CORRECT) {
             // any(isnan, y0m) of this estimator (Inf is a measurement)
@@ -69,29 +91,14 @@ MPCQP_HD void kf_cov_body(W& w, const CovArgs& a, int mode, int wave_id) {
                 const double* yb = a.y0m + (size_t)b * nym;
                 for (int i = 0; i < nym; ++i) missed = missed || yb[i] != yb[i];
             }
-            sfor<NX>([&](auto ic) {
-                constexpr int c = decltype(ic)::v;
-                S[c] = (r < nym && c < nx) ? Cb[my + ny * c] : 0.0;                           // Ĉm (row = measured output)
-                M[c] = (r < nym && c < nym) ? Rb[c * nym + r] : (r == c ? 1.0 : 0.0);         // R̂, identity in the padding
-                G[c] = 0.0;
-            });
-            op.mmt_acc(P, S, G, 1.0);              // P̂ Ĉm'            (row = state, column = output)
-            op.mm_add(S, G, M);                    // M̂ = R̂ + Ĉm (P̂ Ĉm')
-            bool good = op.gj(M, r);               // M̂⁻¹; false: a pivot of its LDL' is not in (0, inf)
-            op.mm(G, M, X);                        // K̂ = (P̂ Ĉm') M̂⁻¹
+            ld_cm(Cb, my, ny, nym, nx, r, S);      // Ĉm (row = measured output)
+            O::ld_sq(Rb, nym, r, 1.0, M);          // R̂, identity in the padding
+            bool good = kf_gain(op, r, P, S, M, G, X);
             op.mm(X, S, G);                        // K̂ Ĉm
             sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; G[c] = (r == c ? 1.0 : 0.0) - G[c]; });
             op.mm(G, P, M);                        // (I - K̂ Ĉm) P̂
-            sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; S[c] = r == c ? 1.0 : 0.0; G[c] = 0.0; });
-            op.mmt_acc(S, M, G, 1.0);              // its transpose: I ((I - K̂ Ĉm) P̂)'
-            double fin = 1.0;
-            sfor<NX>([&](auto ic) {
-                constexpr int c = decltype(ic)::v;
-                M[c] = 0.5 * (M[c] + G[c]);
-                fin = (M[c] - M[c] == 0.0 && X[c] - X[c] == 0.0) ? fin : idle;
-            });
-            const bool fin_all = w.rmin(fin) > 0.5;          // (every lane takes part: not behind `good &&`)
-            good = good && fin_all;
+            op.symmetrise(M, G, r);
+            good = op.all_finite(r, M, X) && good;           // (every lane takes part in the vote: not behind `good &&`)
             const bool apply = good && !missed;
             sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; P[c] = apply ? M[c] : P[c]; });
             if (live && apply && r < nx)
@@ -105,18 +112,12 @@ MPCQP_HD void kf_cov_body(W& w, const CovArgs& a, int mode, int wave_id) {
             dropped = a.status[b] == COV_DROPPED;
         }
         if (mode & COV_PREDICT) {
-            sfor<NX>([&](auto ic) {
-                constexpr int c = decltype(ic)::v;
-                const bool in_x = r < nx && c < nx;
-                S[c] = in_x ? Ab[c * nx + r] : 0.0;
-                M[c] = in_x ? Qb[c * nx + r] : 0.0;
-                G[c] = 0.0;
-            });
+            O::ld_sq(Ab, nx, r, 0.0, S);
+            O::ld_sq(Qb, nx, r, 0.0, M);
+            sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; G[c] = 0.0; });
             op.mmt_acc(P, S, G, 1.0);              // P̂ Â'
             op.mm_add(S, G, M);                    // Q̂ + Â (P̂ Â')
-            double fin = 1.0;
-            sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; fin = (M[c] - M[c] == 0.0) ? fin : idle; });
-            const bool finite = w.rmin(fin) > 0.5;
+            const bool finite = op.all_finite(r, M);
             const bool keep = finite && !dropped;
             sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; P[c] = keep ? M[c] : P[c]; });
             if (live && r == 0 && !finite && !dropped) a.status[b] = COV_DROPPED;

@@ -16,7 +16,7 @@ namespace kf {
 // transition matrix, so 40 of them cover a spectral radius of 1 - 1e-11.)  Constants, not options.
 constexpr int DARE_MAX_ITER = 40;
 constexpr double DARE_TOL = 1e-13;
-// The square-root body (kf_dare_psd_bodies.h) factors H(k) = L L' without pivoting and drops the columns of pivots <= 0.  A
+// The square-root form of the body (kf_dare_bodies.h, PSD = true) factors H(k) = L L' without pivoting and drops the columns of pivots <= 0.  A
 // pivot below -DARE_PSD_NEG max(1, max diag H(k)) is not rounding: H(k) is indefinite and the estimator breaks down.
 // (Measured: rounding pivots down to -5.6e-14 on the shapes of the tests; the indefinite member of the tests has -1e-3.)
 constexpr double DARE_PSD_NEG = 1e-8;
@@ -28,7 +28,7 @@ constexpr double DARE_PSD_NEG = 1e-8;
 constexpr double DARE_PSD_SING = 1e-10;
 // The square-root body takes H for converged only once max|A(k+1)| <= DARE_PSD_STAB as well: the closed-loop transition
 // matrix over 2^(k+1) periods is dying out (it squares with every iteration, so any bound below 1 tells a stable mode from
-// one on the unit circle; see kf_dare_psd_bodies.h).
+// one on the unit circle; see kf_dare_bodies.h).
 constexpr double DARE_PSD_STAB = 0.5;
 
 // per-estimator status of the last solve.  DARE_NOT_CONVERGED: the cap was reached (the reference's "Cannot compute the

@@ -1,7 +1,7 @@
 // kf_kernels.hip -- gfx950 kernels of the covariance / gain recursion of the time-varying KalmanFilter (bodies:
 // kf_cov_bodies.h) and of the steady-state Riccati solve of the SteadyKalmanFilter (k_kf_dare<NX>, k_kf_dare_wide<NX>, the
-// same families; body: kf_dare_bodies.h).  One wavefront per workgroup, persistent grid, the same split as the
-// MovingHorizonEstimator:
+// same families; body: kf_dare_bodies.h, whose square-root form is k_kf_dare_psd<NX>, k_kf_dare_psd_wide<NX>).  One
+// wavefront per workgroup, persistent grid, the same split as the MovingHorizonEstimator:
 //   k_kf_cov<NX>,      NX = 4, 8, 12, 16: max(nx̂, nym) <= 16, four estimators per wavefront (one per DPP row, MheDevWave);
 //   k_kf_cov_wide<NX>, NX = 24, 32: 16 < max(nx̂, nym) <= 32, one estimator per wavefront, the NX^3 products on the
 //                      matrix cores through the LDS staging buffer of Ops::mm_staged.
@@ -13,6 +13,7 @@
 #include "kf_dare_launch.h"
 #include "kf_dare_psd_bodies.h"
 #include "mhe_devwave.h"
+#include "mhe_dispatch.h"
 #include "mhe_wide_devwave.h"
 #include "mpcqp_launch.h"
 
@@ -21,34 +22,49 @@ namespace kf {
 
 using mhe::MheDevWave;
 using WideWave = mhe::MheWideMfmaWave;
-static constexpr size_t kStageBytes = mhe::stage_doubles() * sizeof(double);
+
+// the wave of a kernel: 16-lane rows, or the whole wavefront with the staging buffer of its products in the dynamic LDS
+template <class W>
+__device__ __forceinline__ W make_wave() {
+    if constexpr (std::is_same<W, WideWave>::value) {
+        WideWave w;
+        w.lane = (int)threadIdx.x;
+        w.stage = mpcqp_smem;
+        return w;
+    } else {
+        return MheDevWave{(int)threadIdx.x};
+    }
+}
+
+// launch(Cols<NX>, dynamic LDS bytes) for the register columns of the arguments, on their persistent grid: `launch` picks
+// its narrow or its wide kernel by NX > mhe::RL
+template <class F>
+static hipError_t launch_for(int NX, F launch) {
+    const hipError_t e = mhe::dispatch_nx<mhe::NX_NARROW | mhe::NX_WIDE>(NX, [&](auto nx) {
+        launch(nx, decltype(nx)::value > mhe::RL ? mhe::stage_doubles() * sizeof(double) : (size_t)0);
+    });
+    return e != hipSuccess ? e : hipGetLastError();
+}
 
 template <int NX>
 __global__ __launch_bounds__(64) void k_kf_cov(CovArgs a, int mode) {
-    MheDevWave w{(int)threadIdx.x};
+    MheDevWave w = make_wave<MheDevWave>();
     kf_cov_body<MheDevWave, NX>(w, a, mode, (int)blockIdx.x);
 }
 // (registers: five rows of NX doubles, 320 at NX = 32 -- one wavefront per SIMD)
 template <int NX>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_kf_cov_wide(CovArgs a, int mode) {
-    WideWave w;
-    w.lane = (int)threadIdx.x;
-    w.stage = mpcqp_smem;
+    WideWave w = make_wave<WideWave>();
     kf_cov_body<WideWave, NX>(w, a, mode, (int)blockIdx.x);
 }
 
 hipError_t launch_kf_cov(const CovArgs& a, int mode, hipStream_t st) {
     if (!kf_cov_args_ok(a)) return hipErrorInvalidValue;
-    switch (a.NX) {
-        case 4: hipLaunchKernelGGL(k_kf_cov<4>, dim3(a.nwaves), dim3(WAVE), 0, st, a, mode); break;
-        case 8: hipLaunchKernelGGL(k_kf_cov<8>, dim3(a.nwaves), dim3(WAVE), 0, st, a, mode); break;
-        case 12: hipLaunchKernelGGL(k_kf_cov<12>, dim3(a.nwaves), dim3(WAVE), 0, st, a, mode); break;
-        case 16: hipLaunchKernelGGL(k_kf_cov<16>, dim3(a.nwaves), dim3(WAVE), 0, st, a, mode); break;
-        case 24: hipLaunchKernelGGL(k_kf_cov_wide<24>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a, mode); break;
-        case 32: hipLaunchKernelGGL(k_kf_cov_wide<32>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a, mode); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_for(a.NX, [&](auto nx, size_t lds) {
+        constexpr int NX = decltype(nx)::value;
+        if constexpr (NX > mhe::RL) hipLaunchKernelGGL(k_kf_cov_wide<NX>, dim3(a.nwaves), dim3(WAVE), lds, st, a, mode);
+        else hipLaunchKernelGGL(k_kf_cov<NX>, dim3(a.nwaves), dim3(WAVE), lds, st, a, mode);
+    });
 }
 
 // The grid: registers allow two wavefronts per SIMD for the 16-lane kernels (eight per CU), one for the wide ones (four per
@@ -67,29 +83,22 @@ int kf_cov_waves_for(int device, int B, int NX) {
 // the iterations: the wide kernels spill (lib/isa_resources.txt), which a solve per model swap can afford.
 template <int NX>
 __global__ __launch_bounds__(64) void k_kf_dare(DareArgs a) {
-    MheDevWave w{(int)threadIdx.x};
+    MheDevWave w = make_wave<MheDevWave>();
     kf_dare_body<MheDevWave, NX>(w, a, (int)blockIdx.x);
 }
 template <int NX>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_kf_dare_wide(DareArgs a) {
-    WideWave w;
-    w.lane = (int)threadIdx.x;
-    w.stage = mpcqp_smem;
+    WideWave w = make_wave<WideWave>();
     kf_dare_body<WideWave, NX>(w, a, (int)blockIdx.x);
 }
 
 hipError_t launch_kf_dare(const DareArgs& a, hipStream_t st) {
     if (!kf_dare_args_ok(a)) return hipErrorInvalidValue;
-    switch (a.NX) {
-        case 4: hipLaunchKernelGGL(k_kf_dare<4>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
-        case 8: hipLaunchKernelGGL(k_kf_dare<8>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
-        case 12: hipLaunchKernelGGL(k_kf_dare<12>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
-        case 16: hipLaunchKernelGGL(k_kf_dare<16>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
-        case 24: hipLaunchKernelGGL(k_kf_dare_wide<24>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a); break;
-        case 32: hipLaunchKernelGGL(k_kf_dare_wide<32>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_for(a.NX, [&](auto nx, size_t lds) {
+        constexpr int NX = decltype(nx)::value;
+        if constexpr (NX > mhe::RL) hipLaunchKernelGGL(k_kf_dare_wide<NX>, dim3(a.nwaves), dim3(WAVE), lds, st, a);
+        else hipLaunchKernelGGL(k_kf_dare<NX>, dim3(a.nwaves), dim3(WAVE), lds, st, a);
+    });
 }
 
 // the grid of the covariance kernels: what is not resident at once queues behind what is
@@ -101,29 +110,22 @@ int kf_dare_waves_for(int device, int B, int NX) { return kf_cov_waves_for(devic
 // lib/isa_resources.txt -- accepted as above.)
 template <int NX>
 __global__ __launch_bounds__(64) void k_kf_dare_psd(DareArgs a) {
-    MheDevWave w{(int)threadIdx.x};
+    MheDevWave w = make_wave<MheDevWave>();
     kf_dare_psd_body<MheDevWave, NX>(w, a, (int)blockIdx.x);
 }
 template <int NX>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_kf_dare_psd_wide(DareArgs a) {
-    WideWave w;
-    w.lane = (int)threadIdx.x;
-    w.stage = mpcqp_smem;
+    WideWave w = make_wave<WideWave>();
     kf_dare_psd_body<WideWave, NX>(w, a, (int)blockIdx.x);
 }
 
 hipError_t launch_kf_dare_psd(const DareArgs& a, hipStream_t st) {
     if (!kf_dare_args_ok(a) || !a.path) return hipErrorInvalidValue;
-    switch (a.NX) {
-        case 4: hipLaunchKernelGGL(k_kf_dare_psd<4>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
-        case 8: hipLaunchKernelGGL(k_kf_dare_psd<8>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
-        case 12: hipLaunchKernelGGL(k_kf_dare_psd<12>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
-        case 16: hipLaunchKernelGGL(k_kf_dare_psd<16>, dim3(a.nwaves), dim3(WAVE), 0, st, a); break;
-        case 24: hipLaunchKernelGGL(k_kf_dare_psd_wide<24>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a); break;
-        case 32: hipLaunchKernelGGL(k_kf_dare_psd_wide<32>, dim3(a.nwaves), dim3(WAVE), kStageBytes, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_for(a.NX, [&](auto nx, size_t lds) {
+        constexpr int NX = decltype(nx)::value;
+        if constexpr (NX > mhe::RL) hipLaunchKernelGGL(k_kf_dare_psd_wide<NX>, dim3(a.nwaves), dim3(WAVE), lds, st, a);
+        else hipLaunchKernelGGL(k_kf_dare_psd<NX>, dim3(a.nwaves), dim3(WAVE), lds, st, a);
+    });
 }
 
 }  // namespace kf

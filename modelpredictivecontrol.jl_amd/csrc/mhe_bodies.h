@@ -162,8 +162,9 @@ struct Ops {
         });
         return acc;
     }
-    MPCQP_HD void mm(const Row& X, const Row& Y, Row& C) const {  // C = X Y
-        if constexpr (STAGED) { mm_staged<P_SET>(X, Y, C, 1.0); return; }
+    template <int MODE>
+    MPCQP_HD void mm_as(const Row& X, const Row& Y, Row& C) const {     // P_SET: C = X Y,  P_ADD: C += X Y
+        if constexpr (STAGED) { mm_staged<MODE>(X, Y, C, 1.0); return; }
         sfor<NX>([&](auto ic) {
             constexpr int c = decltype(ic)::v;
             double acc = 0.0;
@@ -171,19 +172,12 @@ struct Ops {
                 constexpr int k = 4 * decltype(ij)::v;
                 w.template fmabc4<k, k + 1, k + 2, k + 3>(acc, Y[c], Y[c], Y[c], Y[c], X[k], X[k + 1], X[k + 2], X[k + 3]);
             });
-            C[c] = acc;
+            if constexpr (MODE == P_ADD) C[c] += acc;
+            else C[c] = acc;
         });
     }
-    // C += X Y
-    MPCQP_HD void mm_add(const Row& X, const Row& Y, Row& C) const {
-        if constexpr (STAGED) { mm_staged<P_ADD>(X, Y, C, 1.0); return; }
-        sfor<NX>([&](auto ic) {
-            constexpr int c = decltype(ic)::v;
-            double acc = 0.0;
-            sfor<NX / 4>([&](auto ij) { constexpr int k = 4 * decltype(ij)::v; w.template fmabc4<k, k + 1, k + 2, k + 3>(acc, Y[c], Y[c], Y[c], Y[c], X[k], X[k + 1], X[k + 2], X[k + 3]); });
-            C[c] += acc;
-        });
-    }
+    MPCQP_HD void mm(const Row& X, const Row& Y, Row& C) const { mm_as<P_SET>(X, Y, C); }          // C = X Y
+    MPCQP_HD void mm_add(const Row& X, const Row& Y, Row& C) const { mm_as<P_ADD>(X, Y, C); }      // C += X Y
     MPCQP_HD void mmt_sub(const Row& X, const Row& Y, Row& C) const {   // C -= X Y', accumulated in place
         if constexpr (STAGED) { mm_staged<P_SUBT>(X, Y, C, 1.0); return; }
         sfor<NX>([&](auto ic) {
@@ -291,6 +285,35 @@ struct Ops {
     MPCQP_HD static void add_diag(Row& M, int r, double v) {
         sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; M[c] += (r == c) ? v : 0.0; });
     }
+    // D = M' as the product I M' (every term is a value times 0 or 1, so it is exact): a transpose on the existing products
+    MPCQP_HD void transpose(const Row& M, Row& D, int r) const {
+        Row I;
+        sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; I[c] = r == c ? 1.0 : 0.0; D[c] = 0.0; });
+        mmt_acc(I, M, D, 1.0);
+    }
+    MPCQP_HD void symmetrise(Row& M, Row& Tmp, int r) const {      // M = ½ (M + M'); Tmp is used up
+        transpose(M, Tmp, r);
+        sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; M[c] = 0.5 * (M[c] + Tmp[c]); });
+    }
+    // every entry of the given operands is finite, voted over the group of lane r.  One reduction: every lane of the
+    // wavefront has to call it, never behind a `good &&`.
+    template <class... Rows>
+    MPCQP_HD bool all_finite(int r, const Rows&... Ms) const {
+        double fin = 1.0;
+        sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; fin = ((Ms[c] - Ms[c] == 0.0) && ...) ? fin : 0.0; });
+        return vote_finite(r, fin);
+    }
+    // its vote: fin is 1 on a lane whose row is finite, 0 otherwise (the lanes r >= NX own no row and carry anything)
+    MPCQP_HD bool vote_finite(int r, double fin) const { return w.rmin(r < NX ? fin : 1.0) > 0.5; }
+    // Padded operands from the ABI arrays (column-major inside an estimator).  Row r of the n x n matrix p, `pad` on the
+    // diagonal beyond n (1: the padded block is the identity and stays it through an inverse; 0: zeros) ...
+    MPCQP_HD static void ld_sq(const double* p, int n, int r, double pad, Row& M) {
+        sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; M[c] = (r < n && c < n) ? p[c * n + r] : (r == c ? pad : 0.0); });
+    }
+    // ... and row r of its transpose (column r of p), zeros beyond n
+    MPCQP_HD static void ld_sq_t(const double* p, int n, int r, Row& M) {
+        sfor<NX>([&](auto ic) { constexpr int c = decltype(ic)::v; M[c] = (r < n && c < n) ? p[r * n + c] : 0.0; });
+    }
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -313,6 +336,8 @@ MPCQP_HD void setup_body(W& w, const Dims& d, const Raw& in, double* cst_all, in
         const double* Qr = in.Q + (size_t)b * nx * nx;
         const double* Cr = in.Cm + (size_t)b * nym * nx;
         const double* Rr = in.R + (size_t)b * nym * nym;
+        // (one pass over the columns for all six operands, not Ops::ld_sq / ld_sq_t one after the other: the kernels need
+        // fewer registers and spill less this way)
         sfor<NX>([&](auto ic) {
             constexpr int c = decltype(ic)::v;
             const bool in_x = r < nx && c < nx;

@@ -6,6 +6,7 @@
 
 #include "mhe_bodies.h"
 #include "mhe_devwave.h"
+#include "mhe_dispatch.h"
 #include "mhe_launch.h"
 #include "mpcqp_launch.h"
 
@@ -35,33 +36,34 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CM == 1u ? M
     step_body<MheDevWave, NX, CM>(w, d, a, (int)blockIdx.x, mpcqp_smem);
 }
 
-#define MHE_DISPATCH(NXV, CALL)                 \
-    switch (NXV) {                              \
-        case 4: { constexpr int NX = 4; CALL; } break;   \
-        case 8: { constexpr int NX = 8; CALL; } break;   \
-        case 12: { constexpr int NX = 12; CALL; } break; \
-        case 16: { constexpr int NX = 16; CALL; } break; \
-        default: return hipErrorInvalidValue;   \
-    }
+// k<NX> for the register columns of the handle (16-lane family: 4 ... 16) on its persistent grid
+template <class F>
+static hipError_t launch_for(const Dims& d, F launch) {
+    const hipError_t e = dispatch_nx<NX_NARROW>(d.NX, launch);
+    return e != hipSuccess ? e : hipGetLastError();
+}
 
 hipError_t launch_setup(const Dims& d, const Raw& in, double* cst, hipStream_t st) {
-    MHE_DISPATCH(d.NX, hipLaunchKernelGGL(k_mhe_setup<NX>, dim3(d.nwaves), dim3(WAVE), 0, st, d, in, cst));
-    return hipGetLastError();
+    return launch_for(d, [&](auto nx) {
+        hipLaunchKernelGGL(k_mhe_setup<decltype(nx)::value>, dim3(d.nwaves), dim3(WAVE), 0, st, d, in, cst);
+    });
 }
 hipError_t launch_cov(const Dims& d, const Args& a, int mode, const double* P0, double* Pout, hipStream_t st) {
-    MHE_DISPATCH(d.NX, hipLaunchKernelGGL(k_mhe_cov<NX>, dim3(d.nwaves), dim3(WAVE), 0, st, d, a, mode, P0, Pout));
-    return hipGetLastError();
+    return launch_for(d, [&](auto nx) {
+        hipLaunchKernelGGL(k_mhe_cov<decltype(nx)::value>, dim3(d.nwaves), dim3(WAVE), 0, st, d, a, mode, P0, Pout);
+    });
+}
+template <unsigned CM>
+static hipError_t launch_step_as(const Dims& d, const Args& a, hipStream_t st) {
+    const size_t lds = step_lds_doubles(d.NX) * sizeof(double);
+    return launch_for(d, [&](auto nx) {
+        hipLaunchKernelGGL((k_mhe_step<decltype(nx)::value, CM>), dim3(d.nwaves), dim3(WAVE), lds, st, d, a);
+    });
 }
 hipError_t launch_step(const Dims& d, const Args& a, hipStream_t st) {
-    const size_t lds = step_lds_doubles(d.NX) * sizeof(double);
-    if ((d.cls & ~CLS_X) == 0) {
-        MHE_DISPATCH(d.NX, hipLaunchKernelGGL((k_mhe_step<NX, 1u>), dim3(d.nwaves), dim3(WAVE), lds, st, d, a));
-    } else if (d.cls & CLS_S) {       // soft constraints: all classes + the slack variable
-        MHE_DISPATCH(d.NX, hipLaunchKernelGGL((k_mhe_step<NX, 15u>), dim3(d.nwaves), dim3(WAVE), lds, st, d, a));
-    } else {
-        MHE_DISPATCH(d.NX, hipLaunchKernelGGL((k_mhe_step<NX, 7u>), dim3(d.nwaves), dim3(WAVE), lds, st, d, a));
-    }
-    return hipGetLastError();
+    if ((d.cls & ~CLS_X) == 0) return launch_step_as<1u>(d, a, st);
+    if (d.cls & CLS_S) return launch_step_as<15u>(d, a, st);       // soft constraints: all classes + the slack variable
+    return launch_step_as<7u>(d, a, st);
 }
 
 }  // namespace mhe

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "mhe_bodies.h"
+#include "mhe_dispatch.h"
 #include "mhe_wide_devwave.h"
 #include "mhe_wide_launch.h"
 #include "mpcqp_launch.h"
@@ -47,42 +48,44 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 8))) void
     step_body<WideWave, NX, CM>(w, d, a, (int)blockIdx.x, mpcqp_smem);
 }
 
-#define MHE_WIDE_DISPATCH(NXV, CALL)                     \
-    switch (NXV) {                                       \
-        case 24: { constexpr int NX = 24; CALL; } break; \
-        case 32: { constexpr int NX = 32; CALL; } break; \
-        default: return hipErrorInvalidValue;            \
-    }
-
 static size_t wide_step_lds_bytes(int NX) { return (step_lds_doubles(NX) + kStageDoubles) * sizeof(double); }
+
+// k<NX> for the register columns of the handle (wide family: 24, 32) on its persistent grid
+template <class F>
+static hipError_t launch_for(const Dims& d, F launch) {
+    const hipError_t e = dispatch_nx<NX_WIDE>(d.NX, launch);
+    return e != hipSuccess ? e : hipGetLastError();
+}
 
 hipError_t launch_wide_setup(const Dims& d, const Raw& in, double* cst, hipStream_t st) {
     const size_t lds = kStageDoubles * sizeof(double);
-    MHE_WIDE_DISPATCH(d.NX, hipLaunchKernelGGL(k_mhe_wide_setup<NX>, dim3(d.nwaves), dim3(WAVE), lds, st, d, in, cst));
-    return hipGetLastError();
+    return launch_for(d, [&](auto nx) {
+        hipLaunchKernelGGL(k_mhe_wide_setup<decltype(nx)::value>, dim3(d.nwaves), dim3(WAVE), lds, st, d, in, cst);
+    });
 }
 hipError_t launch_wide_cov(const Dims& d, const Args& a, int mode, const double* P0, double* Pout, hipStream_t st) {
     const size_t lds = kStageDoubles * sizeof(double);
-    MHE_WIDE_DISPATCH(d.NX, hipLaunchKernelGGL(k_mhe_wide_cov<NX>, dim3(d.nwaves), dim3(WAVE), lds, st, d, a, mode, P0, Pout));
-    return hipGetLastError();
+    return launch_for(d, [&](auto nx) {
+        hipLaunchKernelGGL(k_mhe_wide_cov<decltype(nx)::value>, dim3(d.nwaves), dim3(WAVE), lds, st, d, a, mode, P0, Pout);
+    });
 }
-template <int NX, unsigned CM>
+template <unsigned CM>
 static hipError_t launch_wide_step_as(const Dims& d, const Args& a, hipStream_t st) {
-    const size_t lds = wide_step_lds_bytes(NX);
-    const hipError_t e = ensure_lds((const void*)k_mhe_wide_step<NX, CM>, lds);       // (above 64 KB with the staging buffer at NX = 32)
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_mhe_wide_step<NX, CM>), dim3(d.nwaves), dim3(WAVE), lds, st, d, a);
-    return hipGetLastError();
+    hipError_t err = hipSuccess;
+    const hipError_t e = dispatch_nx<NX_WIDE>(d.NX, [&](auto nx) {
+        constexpr int NX = decltype(nx)::value;
+        const size_t lds = wide_step_lds_bytes(NX);
+        err = ensure_lds((const void*)k_mhe_wide_step<NX, CM>, lds);       // (above 64 KB with the staging buffer at NX = 32)
+        if (err != hipSuccess) return;
+        hipLaunchKernelGGL((k_mhe_wide_step<NX, CM>), dim3(d.nwaves), dim3(WAVE), lds, st, d, a);
+        err = hipGetLastError();
+    });
+    return e != hipSuccess ? e : err;
 }
 hipError_t launch_wide_step(const Dims& d, const Args& a, hipStream_t st) {
-    if ((d.cls & ~CLS_X) == 0) {
-        MHE_WIDE_DISPATCH(d.NX, return (launch_wide_step_as<NX, 1u>(d, a, st)));
-    } else if (d.cls & CLS_S) {       // soft constraints: all classes + the slack variable
-        MHE_WIDE_DISPATCH(d.NX, return (launch_wide_step_as<NX, 15u>(d, a, st)));
-    } else {
-        MHE_WIDE_DISPATCH(d.NX, return (launch_wide_step_as<NX, 7u>(d, a, st)));
-    }
-    return hipErrorInvalidValue;
+    if ((d.cls & ~CLS_X) == 0) return launch_wide_step_as<1u>(d, a, st);
+    if (d.cls & CLS_S) return launch_wide_step_as<15u>(d, a, st);      // soft constraints: all classes + the slack variable
+    return launch_wide_step_as<7u>(d, a, st);
 }
 
 // The grid: one wavefront per estimator up to what a CU holds.  Registers allow one wavefront per SIMD (four per CU);

@@ -18,11 +18,8 @@ hipError_t launch_kf_dare(const DareArgs& a, hipStream_t) {
         mhe::run_row_waves<W>(a.nwaves, 0, [&](W& w, int wv, double*) { kf_dare_body<W, NX>(w, a, wv); });
     });
 }
-// two "persistent" wavefronts: the grid-stride loop is exercised
-int kf_dare_waves_for(int, int B, int NX) {
-    const int groups = NX > mhe::RL ? B : (B + mhe::GPW - 1) / mhe::GPW;
-    return groups < 2 ? groups : 2;
-}
+// the grid of the covariance recursion (emu_kf_cov.cpp), as on the device
+int kf_dare_waves_for(int device, int B, int NX) { return kf_cov_waves_for(device, B, NX); }
 
 }  // namespace kf
 }  // namespace mpcqp

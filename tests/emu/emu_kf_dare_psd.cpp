@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE ONLY: the second pass of the steady-state Riccati solve (csrc/kf_dare_psd_bodies.h: the square-root form
+// TEST INFRASTRUCTURE ONLY: the second pass of the steady-state Riccati solve (csrc/kf_dare_bodies.h: its square-root form
 // for a semidefinite Q̂) on the CPU.  Defines the launcher that csrc/kf_dare_launch.h declares weak, over the waves of
 // emu_rowwave.h, like emu_kf_dare.cpp: the same wavefronts (a.nwaves comes from kf_dare_waves_for of that file), four
 // estimators per wavefront on 16-lane rows or one on the 64 lanes with the staged products.  Both of its votes -- "does this

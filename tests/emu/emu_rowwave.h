@@ -17,6 +17,7 @@
 
 #include "emu_fiber.h"
 #include "mhe_bodies.h"
+#include "mhe_dispatch.h"
 
 namespace mpcqp {
 namespace mhe {
@@ -165,29 +166,7 @@ void run_row_waves(int nwaves, size_t lds_doubles, F body) {
     if (dog.joinable()) dog.join();
 }
 
-// f(Cols<NX>) for the register columns of a handle: 4 ... 16 (NX_NARROW: 16 lanes per estimator), 24 and 32 (NX_WIDE: 64);
-// any other value is hipErrorInvalidValue
-enum { NX_NARROW = 1, NX_WIDE = 2 };
-template <int NX>
-using Cols = std::integral_constant<int, NX>;
-template <int SETS, class F>
-hipError_t dispatch_nx(int NX, F f) {
-    bool known = true;
-    auto at = [&](auto nx) {
-        if constexpr ((SETS & (decltype(nx)::value > RL ? NX_WIDE : NX_NARROW)) != 0) f(nx);
-        else known = false;
-    };
-    switch (NX) {
-        case 4: at(Cols<4>{}); break;
-        case 8: at(Cols<8>{}); break;
-        case 12: at(Cols<12>{}); break;
-        case 16: at(Cols<16>{}); break;
-        case 24: at(Cols<24>{}); break;
-        case 32: at(Cols<32>{}); break;
-        default: known = false;
-    }
-    return known ? hipSuccess : hipErrorInvalidValue;
-}
+// (the launchers pick NX with dispatch_nx of csrc/mhe_dispatch.h, like the device units)
 
 }  // namespace mhe
 }  // namespace mpcqp

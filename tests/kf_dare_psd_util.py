@@ -1,4 +1,4 @@
-"""Helpers of the tests of the steady-state Riccati solve with a positive SEMIdefinite Q̂ (csrc/kf_dare_psd_bodies.h: the
+"""Helpers of the tests of the steady-state Riccati solve with a positive SEMIdefinite Q̂ (csrc/kf_dare_bodies.h in its square-root form: the
 second pass behind mpcqp_kf_set_steady): the generators of such Q̂ on the shapes of tests/kf_util.py, and the case runners that
 tests/test_kf_dare_psd.py (emulator: the launcher of tests/emu/emu_kf_dare_psd.cpp in tests/emu/libmpcqp_emu_est_psd.so, built
 by tests/emu/psd.mk) and tests/test_gpu_kf_dare_psd.py (HIP library) share.  The reference is SciPy's solve_discrete_are

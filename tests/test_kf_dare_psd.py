@@ -1,5 +1,5 @@
 """CPU tests of the SteadyKalmanFilter built from a positive SEMIdefinite Q̂: the second pass of the Riccati solve
-(csrc/kf_dare_psd_bodies.h: H(k) = L L' without pivoting, S = L (I + L'GL)⁻¹ L') on the CPU wave emulator
+(csrc/kf_dare_bodies.h, square-root form: H(k) = L L' without pivoting, S = L (I + L'GL)⁻¹ L') on the CPU wave emulator
 (tests/emu/emu_kf_dare_psd.cpp in tests/emu/libmpcqp_emu_est_psd.so) through the C-ABI and the BatchLinMPC mirror, against
 SciPy's solve_discrete_are, and the host code under the address and undefined-behaviour sanitizers in a stand-alone program.
 The GPU tests are in tests/test_gpu_kf_dare_psd.py; inputs and runners in tests/kf_dare_psd_util.py.
