@@ -33,6 +33,18 @@ struct DBuf {                      // owned device array of doubles (or ints)
     size_t bytes = 0;
 };
 
+// Which estimator sits behind a handle: exactly one of these at a time (mpcqp_handle_s::est; the setters switch with
+// adopt_estimator).  The four Kalman kinds are contiguous: est_is_kf.
+enum {
+    EST_NONE = 0,
+    EST_KF_GAIN,        // mpcqp_kf_set: a gain of the caller's
+    EST_KF_TV,          // mpcqp_kf_set_covariances: the covariance kernel writes K̂(k) ahead of every estimator step
+    EST_KF_STEADY,      // mpcqp_kf_set_steady: the gain the Riccati kernel solved for
+    EST_KF_PLACE,       // mpcqp_kf_set_poles: the gain the placement kernel found
+    EST_MHE,            // mpcqp_mhe_attach: a MovingHorizonEstimator handle (mpcqp_handle_s::mhe)
+    EST_IM              // mpcqp_im_set: the InternalModel
+};
+
 struct mpcqp_handle_s {
     Dims d{};
     Model m{};
@@ -67,24 +79,23 @@ struct mpcqp_handle_s {
     // takes such weights (ms_bodies.h); the condensed kernels go on reading Mfull / Ndense / Ldense.
     bool sepM = false, sepN = false, sepL = false;
     DBuf ms_Mblk;               // [B][Hp][ny][ny] the blocks of a stage-separable Mfull, for the stage kernel (Model::Mblk there)
+    // the estimator behind the handle (EST_*); kf.i_ym / kf.nym hold the measured rows of every kind, kf.Khat the gain of
+    // the Kalman kinds
+    int est = EST_NONE;
     // SteadyKalmanFilter
     DBuf kf_K, kf_iym, kf_x, kf_y, kf_u, kf_d;
     KfParams kf{};
-    bool have_kf = false;
-    // time-varying KalmanFilter (mpcqp_kf_set_covariances): kf_K then holds K̂(k), written by the covariance kernel
+    // time-varying KalmanFilter (EST_KF_TV): kf_K then holds K̂(k), written by the covariance kernel
     // (kf_kernels.hip) ahead of every estimator step that reads it
-    bool kf_tv = false;
     DBuf kf_Q, kf_R, kf_P, kf_st;
     int kf_NX = 0, kf_waves = 0;   // register columns and persistent grid of the covariance kernel
-    // SteadyKalmanFilter from Q̂ and R̂ (mpcqp_kf_set_steady): kf_K holds the gain the Riccati kernel (kf_dare_bodies.h) solved
-    // for, kf_P its P̂∞, kf_st / kf_it the status and iteration count of the last solve; kf_tv stays false
-    bool kf_steady = false;
+    // SteadyKalmanFilter from Q̂ and R̂ (EST_KF_STEADY): kf_K holds the gain the Riccati kernel (kf_dare_bodies.h) solved
+    // for, kf_P its P̂∞, kf_st / kf_it the status and iteration count of the last solve
     DBuf kf_it;
     DBuf kf_path;     // which body produced each estimator's result (kf_dare_launch.h: DareArgs::path)
     int kf_dare_waves = 0;
-    // Luenberger observer from its poles (mpcqp_kf_set_poles): kf_K holds the gain the placement kernel (kf_place_bodies.h)
-    // found, kf_st / kf_it its status and sweep count; kf_tv and kf_steady stay false
-    bool kf_place = false;
+    // Luenberger observer from its poles (EST_KF_PLACE): kf_K holds the gain the placement kernel (kf_place_bodies.h)
+    // found, kf_st / kf_it its status and sweep count
     DBuf kf_poles;
     int kf_place_cap = kf::PLACE_CAP_DEFAULT;
     // mpcqp_kf_set_direct: 1 filter form (mpcqp_loop_device: correction, step, prediction), 0 predictor form (step, correction,
@@ -114,17 +125,16 @@ struct mpcqp_handle_s {
     bool sp_has_Bd = false, sp_has_Dd = false, sp_has_fx = false;
     DBuf sim_u0, sim_st, sim_it, sim_d0, sim_y0m, sim_ry, sim_dh;
     DBuf sim_s[26];
-    // LinMPC(MovingHorizonEstimator): the estimator behind this controller (mpcqp_mhe_attach; borrowed).  kf.i_ym / kf.nym
-    // then hold the attachment's measured rows, have_kf is false.  sim_est: its status array after every period of the last
-    // mpcqp_sim[_device], [N][B]; ei_*: staging of the host-pointer mpcqp_est_initstate
+    // LinMPC(MovingHorizonEstimator): the estimator behind this controller (mpcqp_mhe_attach; borrowed), NULL unless est is
+    // EST_MHE.  sim_est: its status array after every period of the last mpcqp_sim[_device], [N][B]; ei_*: staging of the
+    // host-pointer mpcqp_est_initstate
     mpcqp_mhe mhe = nullptr;
     DBuf sim_est;
     int sim_est_N = 0;
     DBuf ei_x, ei_u, ei_y, ei_d, ei_st;
     // InternalModel (mpcqp_im_set): the stochastic model as given (im_As .. im_Ds), Âs and B̂s of the set-up, x̂s, ŷs, Ŷs, the
     // B + Ŷs every step of the handle reads in place of Model::Bvec, z = Âs x̂s + B̂s ŷs of the last correction (next period's
-    // x̂s) and the set-up's status.  kf.i_ym / kf.nym hold the measured rows, have_kf is false and mhe null.
-    bool have_im = false;
+    // x̂s) and the set-up's status (EST_IM).
     bool in_multi = false;      // a shard of mpcqp_multi_create
     int im_nxs = 0;
     DBuf im_As, im_Bs, im_Cs, im_Ds, im_Ahs, im_Bhs, im_xs, im_ys, im_Yhs, im_Beff, im_z, im_st;
@@ -165,6 +175,73 @@ static int upload(mpcqp_handle h, DBuf& b, const void* src, size_t bytes) {
     HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, h->stream));
     return MPCQP_OK;
 }
+
+static bool est_is_kf(mpcqp_handle h) { return h->est >= EST_KF_GAIN && h->est <= EST_KF_PLACE; }     // a gain in kf.Khat
+static bool est_has_cov(mpcqp_handle h) { return h->est == EST_KF_TV || h->est == EST_KF_STEADY; }     // a P̂ in kf_P
+static bool est_any(mpcqp_handle h) { return h->est != EST_NONE; }
+
+// The one place where a handle changes its estimator: the measured rows are those just uploaded into kf_iym, `Khat` the
+// gain of a Kalman kind (NULL otherwise), and whatever was there before -- an attachment included -- is gone.
+static void adopt_estimator(mpcqp_handle h, int kind, const double* Khat, int32_t nym) {
+    h->kf.Khat = Khat;
+    h->kf.i_ym = (const int*)h->kf_iym.p;
+    h->kf.nym = nym;
+    h->est = kind;
+    h->mhe = nullptr;
+}
+
+// validate_ym, construct.jl:190-196: every measured row inside 0 .. ny-1 and named once (the bounds of nym are the caller's)
+static int check_iym(const Dims& d, const int32_t* i_ym, int32_t nym) {
+    for (int i = 0; i < nym; ++i) {
+        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;
+        for (int j = 0; j < i; ++j)
+            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
+    }
+    return MPCQP_OK;
+}
+
+// `count` int32 of a status-like array for the host, after everything that may still write it: the handle's stream, and
+// the device, because the producer may have been enqueued on a stream of the caller's
+static int read_back_i32(mpcqp_handle h, const DBuf& b, size_t count, int32_t* out) {
+    ON_DEVICE(h);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, b.p, count * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MPCQP_OK;
+}
+
+// The host-pointer twin of a _device entry point: inputs go up into staging buffers of the handle, outputs are allocated
+// there, the device entry runs on the handle's stream, the results come down, finish() waits.  The first error sticks:
+// every later member does nothing, so a twin looks at `rc` once after its uploads and once at its end.
+struct Staging {
+    mpcqp_handle h;
+    int rc = MPCQP_OK;
+    template <class T>
+    T* in(DBuf& b, const T* host, size_t count) {           // the device copy of `host`; NULL stays NULL
+        if (!host || rc) return nullptr;
+        rc = upload(h, b, host, count * sizeof(T));
+        return (T*)b.p;
+    }
+    template <class T>
+    T* out(DBuf& b, size_t count) {
+        if (rc) return nullptr;
+        rc = dev_alloc(h, b, count * sizeof(T));
+        return (T*)b.p;
+    }
+    void down(void* host, const DBuf& b, size_t bytes) {    // (an output the caller did not ask for: nothing)
+        if (!host || rc) return;
+        const hipError_t e = hipMemcpyAsync(host, b.p, bytes, hipMemcpyDeviceToHost, h->stream);
+        if (e != hipSuccess) {
+            g_hip_err = std::string("hipMemcpyAsync to the host: ") + hipGetErrorString(e);
+            rc = MPCQP_ERR_DEVICE;
+        }
+    }
+    int finish() {
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return MPCQP_OK;
+    }
+};
 
 // slice of a problem-major array with `per` values per problem (NULL stays NULL)
 template <class T>
@@ -340,9 +417,6 @@ int mpcqp_get_sizes(mpcqp_handle h, mpcqp_sizes* out) {
     return MPCQP_OK;
 }
 
-static int explicit_refresh(mpcqp_handle h, hipStream_t st);
-static int im_refresh(mpcqp_handle h, hipStream_t st);
-
 static bool terminal_on(const Dims& d) { return (d.gmask >> (2 * P_X)) & 3u; }
 
 // the condensed kernels keep one problem's tables in the LDS of a CU: a handle whose problem does not fit (nZ~ beyond ~165 at
@@ -404,6 +478,136 @@ static int condense(mpcqp_handle h, hipStream_t st, bool timed) {
     return MPCQP_OK;
 }
 
+// ---- ExplicitMPC (src/controller/explicitmpc.jl): H~ factored once per model, a solve or a gain per period ----------------
+
+// what mpcqp_explicit_prepare refuses with MPCQP_ERR_ARG, and what turns a prepared handle away from the explicit calls later
+static bool explicit_constrained(mpcqp_handle h) {
+    return h->d.neps != 0 || h->d.gmask != 0 || h->transcription != MPCQP_SINGLE_SHOOTING;
+}
+
+static void explicit_step_args(mpcqp_handle h, ex::StepArgs& a, uint32_t flags) {
+    a.d = h->d;
+    a.d.flags = flags;
+    a.m = h->m;
+    a.Hinv = (const double*)h->ex_Hinv.p;
+    a.Lsum = (const double*)h->ex_Lsum.p;
+    a.fstatus = (const int32_t*)h->ex_st.p;
+}
+
+// Factor (and law) of a prepared handle for the H~ that is resident now, enqueued on `st` behind K2.  Nothing on the host.
+// A handle that has become constrained since (its explicit calls answer MPCQP_ERR_ORDER, and with the row groups its problem
+// may have outgrown the condensed kernels) is only marked: the setter that called goes on serving the other kernels.
+static int explicit_refresh(mpcqp_handle h, hipStream_t st) {
+    if (!h->ex_prepared) return MPCQP_OK;
+    if (!h->have_model || !h->have_weights) return MPCQP_OK;
+    if (explicit_constrained(h)) { h->ex_stale = true; return MPCQP_OK; }
+    const Dims& d = h->d;
+    const size_t B = d.B, sz = sizeof(double);
+    { int rc = ensure_hessian(h, st); if (rc) return rc; }
+    if (!h->hessian_valid) return MPCQP_ERR_UNSUPPORTED;
+    h->ex_stale = false;
+    if (h->step_timed) HIPCHK(hipStreamWaitEvent(st, h->ev_s1, 0));     // (an explicit call on another stream may still read the tables)
+    ex::FactorArgs f{};
+    f.Hpk = h->m.Hpk; f.Ldiag = h->m.Ldiag; f.jl = h->m.jl;
+    f.Hinv = (double*)h->ex_Hinv.p; f.Lsum = (double*)h->ex_Lsum.p;
+    f.status = (int32_t*)h->ex_st.p; f.B = d.B; f.n = d.nZ; f.npk = d.npk; f.nu = d.nu; f.Hp = d.Hp;
+    HIPCHK(ex::launch_explicit_factor(f, st));
+    if (!h->ex_law) return MPCQP_OK;
+    // the law by superposition: the explicit step itself on the 1 + nx + nu + ny + nd unit inputs, held over the horizon
+    ex::LawBuildArgs lb{};
+    lb.xhat0 = (double*)h->ex_bx.p; lb.lastu0 = (double*)h->ex_blu.p; lb.ry = (double*)h->ex_bry.p;
+    lb.d0 = d.nd > 0 ? (double*)h->ex_bd0.p : nullptr; lb.Dhat0 = d.nd > 0 ? (double*)h->ex_bdh.p : nullptr;
+    lb.Z0 = (const double*)h->ex_bZ0.p; lb.Zk = (const double*)h->ex_bZk.p;
+    lb.table_z = (double*)h->ex_law_z.p; lb.table_u = (double*)h->ex_law_u.p;
+    lb.B = d.B; lb.n = d.nZ; lb.nx = d.nxh; lb.nu = d.nu; lb.ny = d.ny; lb.nd = d.nd; lb.Hp = d.Hp; lb.kp = ex::law_kp(d);
+    ex::StepArgs a{};
+    explicit_step_args(h, a, MPCQP_FLAG_RY_CONSTANT);
+    a.xhat0 = lb.xhat0; a.lastu0 = lb.lastu0; a.Ry = lb.ry; a.Ru = nullptr; a.d0 = lb.d0; a.Dhat0 = lb.Dhat0;
+    a.u0 = (double*)h->ex_bu0.p; a.status = (int32_t*)h->ex_bst.p;
+    const int ncol = ex::law_ncol(d);
+    for (int k = 0; k < ncol; ++k) {
+        HIPCHK(hipMemsetAsync(lb.xhat0, 0, B * d.nxh * sz, st));
+        HIPCHK(hipMemsetAsync(lb.lastu0, 0, B * d.nu * sz, st));
+        HIPCHK(hipMemsetAsync(lb.ry, 0, B * d.ny * sz, st));
+        if (d.nd > 0) {
+            HIPCHK(hipMemsetAsync(lb.d0, 0, B * d.nd * sz, st));
+            HIPCHK(hipMemsetAsync(lb.Dhat0, 0, B * d.nD * sz, st));
+        }
+        lb.k = k;
+        if (k > 0) HIPCHK(ex::launch_explicit_law_unit(lb, st));
+        a.Z = k == 0 ? (double*)h->ex_bZ0.p : (double*)h->ex_bZk.p;
+        HIPCHK(ex::launch_explicit_step(a, st));
+        HIPCHK(ex::launch_explicit_law_pack(lb, st));
+    }
+    return MPCQP_OK;
+}
+
+// what every explicit call does first: the factor of a handle whose H~ changed while it was constrained
+static int explicit_current(mpcqp_handle h, hipStream_t st) { return h->ex_stale ? explicit_refresh(h, st) : MPCQP_OK; }
+
+// ---- InternalModel (include/mpcqp.h; kernels: im_bodies.h) -------------------------------------------------------------------
+
+static void im_args(mpcqp_handle h, im::ImArgs& a) {
+    const Dims& d = h->d;
+    a.Ahat = h->m.Ahat; a.Bu = h->m.Bu; a.C = h->m.C; a.Bd = d.nd > 0 ? h->m.Bd : nullptr; a.Dd = d.nd > 0 ? h->m.Dd : nullptr;
+    a.dop = h->m.dop; a.Bvec = h->m.Bvec; a.i_ym = h->kf.i_ym;
+    a.B = d.B; a.nx = d.nxh; a.nu = d.nu; a.ny = d.ny; a.nd = d.nd; a.nym = h->kf.nym; a.nxs = h->im_nxs; a.Hp = d.Hp;
+    a.G = im::group_lanes(a.nx, a.nu, a.ny, a.nd, a.nxs);
+    a.As = (const double*)h->im_As.p; a.Bs = (const double*)h->im_Bs.p; a.Cs = (const double*)h->im_Cs.p; a.Ds = (const double*)h->im_Ds.p;
+    a.Ahs = (double*)h->im_Ahs.p; a.Bhs = (double*)h->im_Bhs.p;
+    a.xs = (double*)h->im_xs.p; a.ys = (double*)h->im_ys.p; a.Yhs = (double*)h->im_Yhs.p; a.Beff = (double*)h->im_Beff.p;
+    a.z = (double*)h->im_z.p; a.status = (int32_t*)h->im_st.p;
+}
+
+// B_eff = B + Ŷs after k_predmat wrote a new B (mpcqp_set_model, mpcqp_recondense_device)
+static int im_refresh(mpcqp_handle h, hipStream_t st) {
+    if (h->est != EST_IM) return MPCQP_OK;
+    im::ImArgs a{};
+    im_args(h, a);
+    HIPCHK(im::launch_im(a, im::IM_BEFF, st));
+    return MPCQP_OK;
+}
+
+// ---- what the setters share: the tail that brings the handle's derived data up to date ------------------------------------------
+
+// A new model lies in Ahat .. dop: the kernels read it from now on, and everything derived from it is rebuilt on `st` -- the
+// prediction tables and H~, B_eff of an InternalModel (the new B + the Ŷs of the last correction), the explicit factor.
+static int model_resident(mpcqp_handle h, bool with_dop, hipStream_t st) {
+    const Dims& d = h->d;
+    h->m.Ahat = (const double*)h->Ahat.p; h->m.Bu = (const double*)h->Bu.p; h->m.C = (const double*)h->C.p;
+    h->m.Bd = d.nd > 0 ? (const double*)h->Bd.p : nullptr;
+    h->m.Dd = d.nd > 0 ? (const double*)h->Dd.p : nullptr;
+    h->m.dop = with_dop ? (const double*)h->dop.p : nullptr;
+    h->have_model = true;
+    invalidate_stepc(h);
+    int rc = condense(h, st, true);
+    if (!rc) rc = im_refresh(h, st);
+    return rc ? rc : explicit_refresh(h, st);
+}
+
+// A weight changed: the step constants go, H~ and the explicit factor follow it, and the setter returns with them complete.
+static int weights_changed(mpcqp_handle h) {
+    invalidate_stepc(h);
+    int rc = refresh_hessian(h, h->stream);
+    if (!rc) rc = explicit_refresh(h, h->stream);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
+// The row groups changed: the new layout, then H~ again if it had been skipped (the row groups decide whether the problem
+// fits the LDS).  `terminal`: mpcqp_set_bounds, the one setter that can add terminal rows -- their tables come first.
+static int rows_changed(mpcqp_handle h, bool terminal = false) {
+    layout_rows(h);
+    if (terminal && terminal_on(h->d) && !h->terminal_built && h->have_model) {
+        int rc = condense(h, h->stream, false);
+        if (rc) return rc;
+    }
+    { int rc = ensure_hessian(h, h->stream); if (rc) return rc; }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MPCQP_OK;
+}
+
 int mpcqp_set_model(mpcqp_handle h, const double* Ahat, const double* Bu, const double* C,
                     const double* Bd, const double* Dd, const double* dop) {
     if (!h || !Ahat || !Bu || !C) return MPCQP_ERR_NULL;
@@ -418,18 +622,7 @@ int mpcqp_set_model(mpcqp_handle h, const double* Ahat, const double* Bu, const 
     if (!rc && d.nd > 0) rc = upload(h, h->Dd, Dd, B * d.ny * d.nd * sz);
     if (!rc && dop) rc = upload(h, h->dop, dop, B * d.nxh * sz);
     if (rc) return rc;
-    h->m.Ahat = (const double*)h->Ahat.p; h->m.Bu = (const double*)h->Bu.p;
-    h->m.C = (const double*)h->C.p;
-    h->m.Bd = d.nd > 0 ? (const double*)h->Bd.p : nullptr;
-    h->m.Dd = d.nd > 0 ? (const double*)h->Dd.p : nullptr;
-    h->m.dop = dop ? (const double*)h->dop.p : nullptr;
-    h->have_model = true;
-    invalidate_stepc(h);
-    rc = condense(h, h->stream, true);
-    if (rc) return rc;
-    rc = im_refresh(h, h->stream);              // (InternalModel: B_eff = the new B + the Ŷs of the last correction)
-    if (rc) return rc;
-    rc = explicit_refresh(h, h->stream);
+    rc = model_resident(h, dop != nullptr, h->stream);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
@@ -451,11 +644,7 @@ int mpcqp_set_weights(mpcqp_handle h, const double* Mdiag, const double* Ndiag,
     h->m.Ldiag = (const double*)h->Ldiag.p;
     h->m.Cwt = d.neps ? (const double*)h->Cwt.p : nullptr;
     h->have_weights = true;
-    invalidate_stepc(h);
-    { int rc = refresh_hessian(h, h->stream); if (rc) return rc; }
-    { int rc = explicit_refresh(h, h->stream); if (rc) return rc; }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    return weights_changed(h);
 }
 
 int mpcqp_set_output_weight_blocks(mpcqp_handle h, const double* Mblk) {
@@ -470,11 +659,7 @@ int mpcqp_set_output_weight_blocks(mpcqp_handle h, const double* Mblk) {
     } else {
         h->m.Mblk = nullptr;
     }
-    invalidate_stepc(h);
-    { int rc = refresh_hessian(h, h->stream); if (rc) return rc; }
-    { int rc = explicit_refresh(h, h->stream); if (rc) return rc; }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    return weights_changed(h);
 }
 
 int mpcqp_set_dense_weights(mpcqp_handle h, const double* M_Hp, const double* N_Hc, const double* L_Hp) {
@@ -524,11 +709,7 @@ int mpcqp_set_dense_weights(mpcqp_handle h, const double* M_Hp, const double* N_
     }
     h->lam_valid = false;
     d.dense_w = (h->m.Mfull || h->m.Ldense) ? 1 : 0;     // (a dense N_Hc only changes H̃: any step kernel serves it)
-    invalidate_stepc(h);
-    { int rc = refresh_hessian(h, h->stream); if (rc) return rc; }
-    { int rc = explicit_refresh(h, h->stream); if (rc) return rc; }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    return weights_changed(h);
 }
 
 int mpcqp_set_flags(mpcqp_handle h, uint32_t flags) {
@@ -546,7 +727,7 @@ int mpcqp_set_custom_constraints(mpcqp_handle h, int nw, const double* Wy, const
     Dims& d = h->d;
     if (nw < 0) return MPCQP_ERR_ARG;
     if (nw > 0 && (!Wy || !Wu)) return MPCQP_ERR_NULL;
-    if (nw > 0 && h->have_im) return MPCQP_ERR_UNSUPPORTED;      // (the ŷ(k) term of the custom rows would need ŷs inside the kernel)
+    if (nw > 0 && h->est == EST_IM) return MPCQP_ERR_UNSUPPORTED;      // (the ŷ(k) term of the custom rows would need ŷs inside the kernel)
     ON_DEVICE(h);
     Model& m = h->m;
     d.nw = nw; d.nW = nw * (d.Hp + 1);
@@ -566,10 +747,7 @@ int mpcqp_set_custom_constraints(mpcqp_handle h, int nw, const double* Wy, const
         m.Wr = Wr ? (const double*)h->Wr.p : nullptr;
         m.w_op = w_op ? (const double*)h->w_op.p : nullptr;
     }
-    layout_rows(h);
-    { int rc = ensure_hessian(h, h->stream); if (rc) return rc; }      // (the row groups decide whether the problem fits the LDS)
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    return rows_changed(h);
 }
 
 int mpcqp_set_current_setpoint(mpcqp_handle h, const double* ry_now) {
@@ -609,10 +787,7 @@ int mpcqp_set_custom_bounds(mpcqp_handle h, const double* Wmin, const double* Wm
     d.gmask &= ~(3u << (2 * P_W));
     if (m.Wmin) d.gmask |= 1u << (2 * P_W);
     if (m.Wmax) d.gmask |= 1u << (2 * P_W + 1);
-    layout_rows(h);
-    { int rc = ensure_hessian(h, h->stream); if (rc) return rc; }      // (the row groups decide whether the problem fits the LDS)
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    return rows_changed(h);
 }
 
 int mpcqp_set_bounds(mpcqp_handle h, const mpcqp_bounds* bin) {
@@ -671,14 +846,7 @@ int mpcqp_set_bounds(mpcqp_handle h, const mpcqp_bounds* bin) {
     if (m.x0max) g |= 1u << (2 * P_X + 1);
     g |= d.gmask & (3u << (2 * P_W));                    // custom rows: mpcqp_set_custom_bounds
     d.gmask = g;
-    layout_rows(h);
-    if (terminal_on(d) && !h->terminal_built && h->have_model) {
-        int rc = condense(h, h->stream, false);
-        if (rc) return rc;
-    }
-    { int rc = ensure_hessian(h, h->stream); if (rc) return rc; }      // (the row groups decide whether the problem fits the LDS)
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    return rows_changed(h, true);
 }
 
 // the handle is routed to the stage-structured kernel: asked for (MultipleShooting), or the condensed kernels cannot take it
@@ -735,19 +903,6 @@ static int kf_cov_launch(mpcqp_handle h, int mode, const double* y0m, hipStream_
 static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* Ry,
                             const double* Ru, const double* d0, const double* Dhat0, double* Ztilde, double* u0,
                             int32_t* status, int32_t* iters, double* Yhat0, void* stream,
-                            const double* y0m, double* xhat0_out, int predict);
-
-int mpcqp_step_device(mpcqp_handle h, const double* xhat0, const double* lastu0,
-                      const double* Ry, const double* Ru, const double* d0, const double* Dhat0,
-                      double* Ztilde, double* u0, int32_t* status, int32_t* iters,
-                      double* Yhat0, void* stream) {
-    return step_device_impl(h, xhat0, lastu0, Ry, Ru, d0, Dhat0, Ztilde, u0, status, iters, Yhat0, stream,
-                            nullptr, nullptr, 0);
-}
-
-static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* Ry,
-                            const double* Ru, const double* d0, const double* Dhat0, double* Ztilde, double* u0,
-                            int32_t* status, int32_t* iters, double* Yhat0, void* stream,
                             const double* y0m, double* xhat0_out, int predict) {
     if (!h || !xhat0 || !lastu0 || !Ry || !Ztilde || !u0 || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
@@ -799,7 +954,7 @@ static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* l
 #endif
     // (refusals first: nothing is recorded on the stream for a step that does not run)
     if (uses_stage_kernel(h) && ms_unsupported(h)) return MPCQP_ERR_UNSUPPORTED;      // (the fused Kalman loop runs on the stage-structured kernel too since round 6)
-    if (h->have_im && (uses_stage_kernel(h) || d.nW > 0)) return MPCQP_ERR_UNSUPPORTED;  // (the stage kernel does not read B; custom rows need ŷs)
+    if (h->est == EST_IM && (uses_stage_kernel(h) || d.nW > 0)) return MPCQP_ERR_UNSUPPORTED;  // (the stage kernel does not read B; custom rows need ŷs)
     // (the step constants are handle data like H~: built before the step's time starts)
     if (!uses_stage_kernel(h)) { int rc = ensure_stepc(h, st); if (rc) return rc; }
     HIPCHK(hipEventRecord(h->ev_s0, st));
@@ -836,7 +991,7 @@ static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* l
         HIPCHK(launch_ms_step(dm, mm, io, ms, st));
     } else {
         { int rc = ensure_hessian(h, st); if (rc) return rc; }      // (skipped while the problem did not fit the LDS: see hessian_valid)
-        if (h->have_im) {       // InternalModel: the same kernels on B + Ŷs (k_im_correct keeps it current)
+        if (h->est == EST_IM) {       // InternalModel: the same kernels on B + Ŷs (k_im_correct keeps it current)
             Model mm = h->m;
             mm.Bvec = (double*)h->im_Beff.p;
             HIPCHK(launch_step(d, mm, io, st));
@@ -849,12 +1004,20 @@ static int step_device_impl(mpcqp_handle h, const double* xhat0, const double* l
     return MPCQP_OK;
 }
 
+int mpcqp_step_device(mpcqp_handle h, const double* xhat0, const double* lastu0,
+                      const double* Ry, const double* Ru, const double* d0, const double* Dhat0,
+                      double* Ztilde, double* u0, int32_t* status, int32_t* iters,
+                      double* Yhat0, void* stream) {
+    return step_device_impl(h, xhat0, lastu0, Ry, Ru, d0, Dhat0, Ztilde, u0, status, iters, Yhat0, stream,
+                            nullptr, nullptr, 0);
+}
+
 int mpcqp_loop_device(mpcqp_handle h, double* xhat0, const double* y0m, const double* lastu0,
                       const double* Ry, const double* Ru, const double* d0, const double* Dhat0,
                       double* Ztilde, double* u0, int32_t* status, int32_t* iters, double* Yhat0,
                       void* stream) {
     if (!h || !y0m || !xhat0) return MPCQP_ERR_NULL;
-    if (h->have_im) {
+    if (h->est == EST_IM) {
         // InternalModel: correct (ŷs, Ŷs, B + Ŷs), the step on x̂0 = x̂d, update (x̂d in place, x̂s), three calls on the caller's
         // stream.  Refusals first: a step that does not run leaves the estimator alone
         if (!lastu0 || !Ry || !Ztilde || !u0 || !status || (h->d.nd > 0 && (!d0 || !Dhat0))) return MPCQP_ERR_NULL;
@@ -864,7 +1027,7 @@ int mpcqp_loop_device(mpcqp_handle h, double* xhat0, const double* y0m, const do
         if (!rc) rc = step_device_impl(h, xhat0, lastu0, Ry, Ru, d0, Dhat0, Ztilde, u0, status, iters, Yhat0, stream, nullptr, nullptr, 0);
         return rc ? rc : mpcqp_im_update_device(h, xhat0, u0, d0, stream);
     }
-    if (h->mhe) {
+    if (h->est == EST_MHE) {
         // a MovingHorizonEstimator behind the controller: preparestate!, the step on the estimator's own x̂0 (read in place),
         // updatestate!, three calls on the caller's stream.  Refusals first: a step that does not run leaves the windows alone
         if (!lastu0 || !Ry || !Ztilde || !u0 || !status || (h->d.nd > 0 && (!d0 || !Dhat0))) return MPCQP_ERR_NULL;
@@ -880,11 +1043,11 @@ int mpcqp_loop_device(mpcqp_handle h, double* xhat0, const double* y0m, const do
         }
         return mpcqp_mhe_update_stream(h->mhe, u0, y0m, d0, stream);
     }
-    if (!h->have_kf) return MPCQP_ERR_ORDER;
+    if (!est_is_kf(h)) return MPCQP_ERR_ORDER;
     if (h->d.nxh > 4 * WAVE) return MPCQP_ERR_UNSUPPORTED;
     // K̂(k) and P̂(k+1|k) first, in either form: the recursion depends on which measurements are missing and on nothing else
     // (a refused step leaves P̂ one period ahead)
-    if (h->kf_tv) {
+    if (h->est == EST_KF_TV) {
         if (!lastu0 || !Ry || !Ztilde || !u0 || !status || (h->d.nd > 0 && (!d0 || !Dhat0))) return MPCQP_ERR_NULL;
         if (!h->have_model || !h->have_weights) return MPCQP_ERR_ORDER;
         if (uses_stage_kernel(h) && ms_unsupported(h)) return MPCQP_ERR_UNSUPPORTED;
@@ -895,39 +1058,44 @@ int mpcqp_loop_device(mpcqp_handle h, double* xhat0, const double* y0m, const do
                             y0m, xhat0, 1);
 }
 
+// The host-pointer step of one handle on its own stream, up to and without the wait: mpcqp_step waits for its handle,
+// mpcqp_multi_step for every shard after all of them are enqueued.  The caller has checked the pointers and holds the device.
+static int step_staged(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* Ry, const double* Ru,
+                       const double* d0, const double* Dhat0, double* Ztilde, double* u0, int32_t* status, int32_t* iters,
+                       double* Yhat0) {
+    const Dims& d = h->d;
+    const size_t B = d.B, sz = sizeof(double);
+    const size_t nry = (d.flags & MPCQP_FLAG_RY_CONSTANT) ? d.ny : d.nY;
+    Staging s{h};
+    const double* dx = s.in(h->s_x, xhat0, B * d.nxh);
+    const double* dlu = s.in(h->s_lu, lastu0, B * d.nu);
+    const double* dry = s.in(h->s_ry, Ry, B * nry);
+    const double* dru = s.in(h->s_ru, Ru, B * d.nU);
+    const double* dd0 = s.in(h->s_d0, d.nd > 0 ? d0 : nullptr, B * d.nd);
+    const double* ddh = s.in(h->s_dh, d.nd > 0 ? Dhat0 : nullptr, B * d.nD);
+    double* dZ = s.in(h->s_Z, Ztilde, B * d.nZ);
+    double* du0 = s.out<double>(h->s_u0, B * d.nu);
+    int32_t* dst = s.out<int32_t>(h->s_st, B);
+    int32_t* dit = s.out<int32_t>(h->s_it, B);
+    double* dyh = Yhat0 ? s.out<double>(h->s_yh, B * d.nY) : nullptr;
+    if (s.rc) return s.rc;
+    s.rc = mpcqp_step_device(h, dx, dlu, dry, dru, dd0, ddh, dZ, du0, dst, dit, dyh, h->stream);
+    s.down(Ztilde, h->s_Z, B * d.nZ * sz);
+    s.down(u0, h->s_u0, B * d.nu * sz);
+    s.down(status, h->s_st, B * sizeof(int32_t));
+    s.down(iters, h->s_it, B * sizeof(int32_t));
+    s.down(Yhat0, h->s_yh, B * d.nY * sz);
+    return s.rc;
+}
+
 int mpcqp_step(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* Ry,
                const double* Ru, const double* d0, const double* Dhat0, double* Ztilde,
                double* u0, int32_t* status, int32_t* iters, double* Yhat0) {
     if (!h || !xhat0 || !lastu0 || !Ry || !Ztilde || !u0 || !status) return MPCQP_ERR_NULL;
-    const Dims& d = h->d;
-    if (d.nd > 0 && (!d0 || !Dhat0)) return MPCQP_ERR_NULL;
+    if (h->d.nd > 0 && (!d0 || !Dhat0)) return MPCQP_ERR_NULL;
     ON_DEVICE(h);
-    const size_t B = d.B, sz = sizeof(double);
-    const size_t nry = (d.flags & MPCQP_FLAG_RY_CONSTANT) ? d.ny : d.nY;
-    int rc = upload(h, h->s_x, xhat0, B * d.nxh * sz);
-    if (!rc) rc = upload(h, h->s_lu, lastu0, B * d.nu * sz);
-    if (!rc) rc = upload(h, h->s_ry, Ry, B * nry * sz);
-    if (!rc && Ru) rc = upload(h, h->s_ru, Ru, B * d.nU * sz);
-    if (!rc && d.nd > 0) rc = upload(h, h->s_d0, d0, B * d.nd * sz);
-    if (!rc && d.nd > 0) rc = upload(h, h->s_dh, Dhat0, B * d.nD * sz);
-    if (!rc) rc = upload(h, h->s_Z, Ztilde, B * d.nZ * sz);
-    if (!rc) rc = dev_alloc(h, h->s_u0, B * d.nu * sz);
-    if (!rc) rc = dev_alloc(h, h->s_st, B * sizeof(int32_t));
-    if (!rc) rc = dev_alloc(h, h->s_it, B * sizeof(int32_t));
-    if (!rc && Yhat0) rc = dev_alloc(h, h->s_yh, B * d.nY * sz);
+    int rc = step_staged(h, xhat0, lastu0, Ry, Ru, d0, Dhat0, Ztilde, u0, status, iters, Yhat0);
     if (rc) return rc;
-    rc = mpcqp_step_device(h, (const double*)h->s_x.p, (const double*)h->s_lu.p,
-                           (const double*)h->s_ry.p, Ru ? (const double*)h->s_ru.p : nullptr,
-                           d.nd > 0 ? (const double*)h->s_d0.p : nullptr,
-                           d.nd > 0 ? (const double*)h->s_dh.p : nullptr, (double*)h->s_Z.p,
-                           (double*)h->s_u0.p, (int32_t*)h->s_st.p, (int32_t*)h->s_it.p,
-                           Yhat0 ? (double*)h->s_yh.p : nullptr, h->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(Ztilde, h->s_Z.p, B * d.nZ * sz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(u0, h->s_u0.p, B * d.nu * sz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(status, h->s_st.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (iters) HIPCHK(hipMemcpyAsync(iters, h->s_it.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (Yhat0) HIPCHK(hipMemcpyAsync(Yhat0, h->s_yh.p, B * d.nY * sz, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
 }
@@ -1091,15 +1259,7 @@ int mpcqp_set_model_continuous_device(mpcqp_handle h, const mpcqp_c2d_spec* spec
     a.dophat = in->dop ? (double*)h->dop.p : nullptr;
     a.status = status;
     HIPCHK(c2d::launch_c2d(a, st));
-    h->m.Ahat = (const double*)h->Ahat.p; h->m.Bu = (const double*)h->Bu.p; h->m.C = (const double*)h->C.p;
-    h->m.Bd = d.nd > 0 ? (const double*)h->Bd.p : nullptr;
-    h->m.Dd = d.nd > 0 ? (const double*)h->Dd.p : nullptr;
-    h->m.dop = in->dop ? (const double*)h->dop.p : nullptr;
-    h->have_model = true;
-    invalidate_stepc(h);
-    rc = condense(h, st, true);
-    if (!rc) rc = im_refresh(h, st);
-    return rc ? rc : explicit_refresh(h, st);
+    return model_resident(h, in->dop != nullptr, st);       // (no wait: everything is on the caller's stream)
 }
 
 int mpcqp_set_model_continuous(mpcqp_handle h, const mpcqp_c2d_spec* spec, const mpcqp_c2d_in* in, int32_t* status) {
@@ -1112,26 +1272,18 @@ int mpcqp_set_model_continuous(mpcqp_handle h, const mpcqp_c2d_spec* spec, const
     if (h->in_multi) return MPCQP_ERR_UNSUPPORTED;
     if (!c2d_in_ok(a, in)) return MPCQP_ERR_NULL;
     ON_DEVICE(h);
-    const size_t B = d.B, sz = sizeof(double);
-    const size_t nin[7] = {B * a.nx * a.nx * sz, B * a.nx * a.nu * sz, B * a.ny * a.nx * sz, B * a.nx * a.nd * sz, B * a.ny * a.nd * sz,
-                           B * sz, B * a.nxd * sz};
-    const void* hin[7] = {in->A, in->Bu, in->C, a.nd > 0 ? in->Bd : nullptr, a.nd > 0 ? in->Dd : nullptr, in->Ts, in->dop};
+    const size_t B = d.B;
+    const size_t nin[7] = {B * a.nx * a.nx, B * a.nx * a.nu, B * a.ny * a.nx, B * a.nx * a.nd, B * a.ny * a.nd, B, B * a.nxd};
+    const double* hin[7] = {in->A, in->Bu, in->C, a.nd > 0 ? in->Bd : nullptr, a.nd > 0 ? in->Dd : nullptr, in->Ts, in->dop};
     const double* din[7];
-    for (int i = 0; i < 7; ++i) {
-        din[i] = nullptr;
-        if (!hin[i]) continue;
-        rc = upload(h, h->c2d_s[i], hin[i], nin[i]);
-        if (rc) return rc;
-        din[i] = (const double*)h->c2d_s[i].p;
-    }
-    rc = dev_alloc(h, h->c2d_st, B * sizeof(int32_t));
-    if (rc) return rc;
+    Staging s{h};
+    for (int i = 0; i < 7; ++i) din[i] = s.in(h->c2d_s[i], hin[i], nin[i]);
+    int32_t* dst = s.out<int32_t>(h->c2d_st, B);
+    if (s.rc) return s.rc;
     mpcqp_c2d_in di{din[0], din[1], din[2], din[3], din[4], din[5], din[6]};
-    rc = mpcqp_set_model_continuous_device(h, spec, &di, (int32_t*)h->c2d_st.p, h->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(status, h->c2d_st.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    s.rc = mpcqp_set_model_continuous_device(h, spec, &di, dst, h->stream);
+    s.down(status, h->c2d_st, B * sizeof(int32_t));
+    return s.finish();
 }
 
 int mpcqp_get(mpcqp_handle h, int which, double* out) {
@@ -1146,6 +1298,14 @@ int mpcqp_get(mpcqp_handle h, int which, double* out) {
         HIPCHK(hipMemcpy(tmp.data(), src, n * sizeof(double), hipMemcpyDeviceToHost));
         return MPCQP_OK;
     };
+    // the arrays that go out as they lie on the device: the refusal of the case if there is one, else B * n doubles from src
+    auto plain = [&](int refuse, const void* src, size_t n) -> int {
+        if (refuse) return refuse;
+        HIPCHK(hipMemcpy(out, src, B * n * sizeof(double), hipMemcpyDeviceToHost));
+        return MPCQP_OK;
+    };
+    const int no_tables = h->stage_only ? MPCQP_ERR_UNSUPPORTED : !h->have_model ? MPCQP_ERR_ORDER : 0;   // (K1's tables)
+    const int no_im = h->est == EST_IM ? 0 : MPCQP_ERR_ORDER;
     std::vector<double> tmp;
     switch (which) {
         case MPCQP_GET_HESSIAN: {
@@ -1178,56 +1338,18 @@ int mpcqp_get(mpcqp_handle h, int which, double* out) {
                                 tmp[((b * d.Hp + mm) * d.ny + a) * d.nu + c];
             return MPCQP_OK;
         }
-        case MPCQP_GET_KMAT:
-            if (h->stage_only) return MPCQP_ERR_UNSUPPORTED;
-            if (!h->have_model) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->m.Ktab, B * d.nxh * d.nY * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
-        case MPCQP_GET_BVEC:
-            if (h->stage_only) return MPCQP_ERR_UNSUPPORTED;
-            if (!h->have_model) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->m.Bvec, B * d.nY * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
-        case MPCQP_GET_QTILDE:
-            if (!h->keep_q.p) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->keep_q.p, B * d.nZ * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
-        case MPCQP_GET_FVEC:
-            if (!h->keep_F.p) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->keep_F.p, B * d.nY * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
-        case MPCQP_GET_XHAT_MS:
-            if (!h->ms_X.p) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->ms_X.p, B * d.nxh * d.Hp * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
-        case MPCQP_GET_MS_DEFECT:
-            if (!h->ms_defect.p) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->ms_defect.p, B * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
-        case MPCQP_GET_AUDIT:
-            if (!h->audit.p) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->audit.p, B * 4 * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
-        case MPCQP_GET_KF_COV:
-            if (!h->have_kf || !(h->kf_tv || h->kf_steady)) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->kf_P.p, B * d.nxh * d.nxh * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
-        case MPCQP_GET_KF_GAIN:
-            if (!h->have_kf) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->kf_K.p, B * d.nxh * h->kf.nym * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
-        case MPCQP_GET_IM_XS:
-            if (!h->have_im) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->im_xs.p, B * h->im_nxs * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
-        case MPCQP_GET_IM_YS:
-            if (!h->have_im) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->im_ys.p, B * d.ny * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
-        case MPCQP_GET_IM_YHATS:
-            if (!h->have_im) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->im_Yhs.p, B * d.nY * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
+        case MPCQP_GET_KMAT: return plain(no_tables, h->m.Ktab, (size_t)d.nxh * d.nY);
+        case MPCQP_GET_BVEC: return plain(no_tables, h->m.Bvec, d.nY);
+        case MPCQP_GET_QTILDE: return plain(h->keep_q.p ? 0 : MPCQP_ERR_ORDER, h->keep_q.p, d.nZ);
+        case MPCQP_GET_FVEC: return plain(h->keep_F.p ? 0 : MPCQP_ERR_ORDER, h->keep_F.p, d.nY);
+        case MPCQP_GET_XHAT_MS: return plain(h->ms_X.p ? 0 : MPCQP_ERR_ORDER, h->ms_X.p, (size_t)d.nxh * d.Hp);
+        case MPCQP_GET_MS_DEFECT: return plain(h->ms_defect.p ? 0 : MPCQP_ERR_ORDER, h->ms_defect.p, 1);
+        case MPCQP_GET_AUDIT: return plain(h->audit.p ? 0 : MPCQP_ERR_ORDER, h->audit.p, 4);
+        case MPCQP_GET_KF_COV: return plain(est_has_cov(h) ? 0 : MPCQP_ERR_ORDER, h->kf_P.p, (size_t)d.nxh * d.nxh);
+        case MPCQP_GET_KF_GAIN: return plain(est_is_kf(h) ? 0 : MPCQP_ERR_ORDER, h->kf_K.p, (size_t)d.nxh * h->kf.nym);
+        case MPCQP_GET_IM_XS: return plain(no_im, h->im_xs.p, h->im_nxs);
+        case MPCQP_GET_IM_YS: return plain(no_im, h->im_ys.p, d.ny);
+        case MPCQP_GET_IM_YHATS: return plain(no_im, h->im_Yhs.p, d.nY);
         case MPCQP_GET_EXPLICIT_LAW: {
             if (!h->ex_prepared || !h->ex_law) return MPCQP_ERR_ORDER;
             const int n = d.nZ, ncol = ex::law_ncol(d), kp = ex::law_kp(d);
@@ -1252,91 +1374,23 @@ int mpcqp_get(mpcqp_handle h, int which, double* out) {
                 std::fill(out, out + B * n, 0.0);
                 return MPCQP_OK;
             }
-            HIPCHK(hipMemcpy(out, src, B * n * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
+            return plain(0, src, n);
         }
 #ifdef MPCQP_PROFILE
         case 99:    /* per-phase cycle counters of profiling builds (-DMPCQP_PROFILE): (16,B) */
-            if (!h->prof.p) return MPCQP_ERR_ORDER;
-            HIPCHK(hipMemcpy(out, h->prof.p, B * 16 * sizeof(double), hipMemcpyDeviceToHost));
-            return MPCQP_OK;
+            return plain(h->prof.p ? 0 : MPCQP_ERR_ORDER, h->prof.p, 16);
 #endif
         default:
             return MPCQP_ERR_ARG;
     }
 }
 
-// ---- ExplicitMPC (src/controller/explicitmpc.jl): H~ factored once per model, a solve or a gain per period ----------------
-
-// what mpcqp_explicit_prepare refuses with MPCQP_ERR_ARG, and what turns a prepared handle away from the explicit calls later
-static bool explicit_constrained(mpcqp_handle h) {
-    return h->d.neps != 0 || h->d.gmask != 0 || h->transcription != MPCQP_SINGLE_SHOOTING;
-}
-
-static void explicit_step_args(mpcqp_handle h, ex::StepArgs& a, uint32_t flags) {
-    a.d = h->d;
-    a.d.flags = flags;
-    a.m = h->m;
-    a.Hinv = (const double*)h->ex_Hinv.p;
-    a.Lsum = (const double*)h->ex_Lsum.p;
-    a.fstatus = (const int32_t*)h->ex_st.p;
-}
-
-// Factor (and law) of a prepared handle for the H~ that is resident now, enqueued on `st` behind K2.  Nothing on the host.
-// A handle that has become constrained since (its explicit calls answer MPCQP_ERR_ORDER, and with the row groups its problem
-// may have outgrown the condensed kernels) is only marked: the setter that called goes on serving the other kernels.
-static int explicit_refresh(mpcqp_handle h, hipStream_t st) {
-    if (!h->ex_prepared) return MPCQP_OK;
-    if (!h->have_model || !h->have_weights) return MPCQP_OK;
-    if (explicit_constrained(h)) { h->ex_stale = true; return MPCQP_OK; }
-    const Dims& d = h->d;
-    const size_t B = d.B, sz = sizeof(double);
-    { int rc = ensure_hessian(h, st); if (rc) return rc; }
-    if (!h->hessian_valid) return MPCQP_ERR_UNSUPPORTED;
-    h->ex_stale = false;
-    if (h->step_timed) HIPCHK(hipStreamWaitEvent(st, h->ev_s1, 0));     // (an explicit call on another stream may still read the tables)
-    ex::FactorArgs f{};
-    f.Hpk = h->m.Hpk; f.Ldiag = h->m.Ldiag; f.jl = h->m.jl;
-    f.Hinv = (double*)h->ex_Hinv.p; f.Lsum = (double*)h->ex_Lsum.p;
-    f.status = (int32_t*)h->ex_st.p; f.B = d.B; f.n = d.nZ; f.npk = d.npk; f.nu = d.nu; f.Hp = d.Hp;
-    HIPCHK(ex::launch_explicit_factor(f, st));
-    if (!h->ex_law) return MPCQP_OK;
-    // the law by superposition: the explicit step itself on the 1 + nx + nu + ny + nd unit inputs, held over the horizon
-    ex::LawBuildArgs lb{};
-    lb.xhat0 = (double*)h->ex_bx.p; lb.lastu0 = (double*)h->ex_blu.p; lb.ry = (double*)h->ex_bry.p;
-    lb.d0 = d.nd > 0 ? (double*)h->ex_bd0.p : nullptr; lb.Dhat0 = d.nd > 0 ? (double*)h->ex_bdh.p : nullptr;
-    lb.Z0 = (const double*)h->ex_bZ0.p; lb.Zk = (const double*)h->ex_bZk.p;
-    lb.table_z = (double*)h->ex_law_z.p; lb.table_u = (double*)h->ex_law_u.p;
-    lb.B = d.B; lb.n = d.nZ; lb.nx = d.nxh; lb.nu = d.nu; lb.ny = d.ny; lb.nd = d.nd; lb.Hp = d.Hp; lb.kp = ex::law_kp(d);
-    ex::StepArgs a{};
-    explicit_step_args(h, a, MPCQP_FLAG_RY_CONSTANT);
-    a.xhat0 = lb.xhat0; a.lastu0 = lb.lastu0; a.Ry = lb.ry; a.Ru = nullptr; a.d0 = lb.d0; a.Dhat0 = lb.Dhat0;
-    a.u0 = (double*)h->ex_bu0.p; a.status = (int32_t*)h->ex_bst.p;
-    const int ncol = ex::law_ncol(d);
-    for (int k = 0; k < ncol; ++k) {
-        HIPCHK(hipMemsetAsync(lb.xhat0, 0, B * d.nxh * sz, st));
-        HIPCHK(hipMemsetAsync(lb.lastu0, 0, B * d.nu * sz, st));
-        HIPCHK(hipMemsetAsync(lb.ry, 0, B * d.ny * sz, st));
-        if (d.nd > 0) {
-            HIPCHK(hipMemsetAsync(lb.d0, 0, B * d.nd * sz, st));
-            HIPCHK(hipMemsetAsync(lb.Dhat0, 0, B * d.nD * sz, st));
-        }
-        lb.k = k;
-        if (k > 0) HIPCHK(ex::launch_explicit_law_unit(lb, st));
-        a.Z = k == 0 ? (double*)h->ex_bZ0.p : (double*)h->ex_bZk.p;
-        HIPCHK(ex::launch_explicit_step(a, st));
-        HIPCHK(ex::launch_explicit_law_pack(lb, st));
-    }
-    return MPCQP_OK;
-}
-
-// what every explicit call does first: the factor of a handle whose H~ changed while it was constrained
-static int explicit_current(mpcqp_handle h, hipStream_t st) { return h->ex_stale ? explicit_refresh(h, st) : MPCQP_OK; }
+// ---- ExplicitMPC: the entry points (the factor and the law build are explicit_refresh, above) --------------------------------
 
 int mpcqp_explicit_prepare(mpcqp_handle h, int32_t with_law) {
     if (!h) return MPCQP_ERR_NULL;
     if (with_law & ~MPCQP_EXPLICIT_LAW) return MPCQP_ERR_ARG;
-    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;               // (the law has no Ŷs term)
+    if (h->est == EST_IM) return MPCQP_ERR_UNSUPPORTED;               // (the law has no Ŷs term)
     if (!h->have_model || !h->have_weights) return MPCQP_ERR_ORDER;
     if (explicit_constrained(h)) return MPCQP_ERR_ARG;          // "ExplicitMPC does not support constraints"
     const Dims& d = h->d;
@@ -1385,14 +1439,11 @@ int mpcqp_explicit_prepare(mpcqp_handle h, int32_t with_law) {
 
 int mpcqp_explicit_status(mpcqp_handle h, int32_t* out) {
     if (!h || !out) return MPCQP_ERR_NULL;
-    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;
+    if (h->est == EST_IM) return MPCQP_ERR_UNSUPPORTED;
     if (!h->ex_prepared || explicit_constrained(h)) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     { int rc = explicit_current(h, h->stream); if (rc) return rc; }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, h->ex_st.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MPCQP_OK;
+    return read_back_i32(h, h->ex_st, h->d.B, out);
 }
 
 int mpcqp_explicit_step_device(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* Ry,
@@ -1401,7 +1452,7 @@ int mpcqp_explicit_step_device(mpcqp_handle h, const double* xhat0, const double
     if (!h || !xhat0 || !lastu0 || !Ry || !Ztilde || !u0 || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && (!d0 || !Dhat0)) return MPCQP_ERR_NULL;
-    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;
+    if (h->est == EST_IM) return MPCQP_ERR_UNSUPPORTED;
     if (!h->ex_prepared || explicit_constrained(h)) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
@@ -1429,7 +1480,7 @@ int mpcqp_explicit_law_device(mpcqp_handle h, const double* xhat0, const double*
     if (!h || !xhat0 || !lastu0 || !ry || !u0 || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
-    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;
+    if (h->est == EST_IM) return MPCQP_ERR_UNSUPPORTED;
     if (!h->ex_prepared || !h->ex_law || explicit_constrained(h)) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
@@ -1452,33 +1503,29 @@ int mpcqp_explicit_step(mpcqp_handle h, const double* xhat0, const double* lastu
     if (!h || !xhat0 || !lastu0 || !Ry || !Ztilde || !u0 || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && (!d0 || !Dhat0)) return MPCQP_ERR_NULL;
-    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;
+    if (h->est == EST_IM) return MPCQP_ERR_UNSUPPORTED;
     if (!h->ex_prepared || explicit_constrained(h)) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     const size_t B = d.B, sz = sizeof(double);
     const size_t nry = (d.flags & MPCQP_FLAG_RY_CONSTANT) ? d.ny : d.nY;
-    int rc = upload(h, h->s_x, xhat0, B * d.nxh * sz);
-    if (!rc) rc = upload(h, h->s_lu, lastu0, B * d.nu * sz);
-    if (!rc) rc = upload(h, h->s_ry, Ry, B * nry * sz);
-    if (!rc && Ru) rc = upload(h, h->s_ru, Ru, B * d.nU * sz);
-    if (!rc && d.nd > 0) rc = upload(h, h->s_d0, d0, B * d.nd * sz);
-    if (!rc && d.nd > 0) rc = upload(h, h->s_dh, Dhat0, B * d.nD * sz);
-    if (!rc) rc = dev_alloc(h, h->s_Z, B * d.nZ * sz);
-    if (!rc) rc = dev_alloc(h, h->s_u0, B * d.nu * sz);
-    if (!rc) rc = dev_alloc(h, h->s_st, B * sizeof(int32_t));
-    if (!rc && Yhat0) rc = dev_alloc(h, h->s_yh, B * d.nY * sz);
-    if (rc) return rc;
-    rc = mpcqp_explicit_step_device(h, (const double*)h->s_x.p, (const double*)h->s_lu.p, (const double*)h->s_ry.p,
-                                    Ru ? (const double*)h->s_ru.p : nullptr, d.nd > 0 ? (const double*)h->s_d0.p : nullptr,
-                                    d.nd > 0 ? (const double*)h->s_dh.p : nullptr, (double*)h->s_Z.p, (double*)h->s_u0.p,
-                                    (int32_t*)h->s_st.p, Yhat0 ? (double*)h->s_yh.p : nullptr, h->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(Ztilde, h->s_Z.p, B * d.nZ * sz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(u0, h->s_u0.p, B * d.nu * sz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(status, h->s_st.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (Yhat0) HIPCHK(hipMemcpyAsync(Yhat0, h->s_yh.p, B * d.nY * sz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    Staging s{h};
+    const double* dx = s.in(h->s_x, xhat0, B * d.nxh);
+    const double* dlu = s.in(h->s_lu, lastu0, B * d.nu);
+    const double* dry = s.in(h->s_ry, Ry, B * nry);
+    const double* dru = s.in(h->s_ru, Ru, B * d.nU);
+    const double* dd0 = s.in(h->s_d0, d.nd > 0 ? d0 : nullptr, B * d.nd);
+    const double* ddh = s.in(h->s_dh, d.nd > 0 ? Dhat0 : nullptr, B * d.nD);
+    double* dZ = s.out<double>(h->s_Z, B * d.nZ);
+    double* du0 = s.out<double>(h->s_u0, B * d.nu);
+    int32_t* dst = s.out<int32_t>(h->s_st, B);
+    double* dyh = Yhat0 ? s.out<double>(h->s_yh, B * d.nY) : nullptr;
+    if (s.rc) return s.rc;
+    s.rc = mpcqp_explicit_step_device(h, dx, dlu, dry, dru, dd0, ddh, dZ, du0, dst, dyh, h->stream);
+    s.down(Ztilde, h->s_Z, B * d.nZ * sz);
+    s.down(u0, h->s_u0, B * d.nu * sz);
+    s.down(status, h->s_st, B * sizeof(int32_t));
+    s.down(Yhat0, h->s_yh, B * d.nY * sz);
+    return s.finish();
 }
 
 int mpcqp_explicit_law(mpcqp_handle h, const double* xhat0, const double* lastu0, const double* ry, const double* d0,
@@ -1486,27 +1533,24 @@ int mpcqp_explicit_law(mpcqp_handle h, const double* xhat0, const double* lastu0
     if (!h || !xhat0 || !lastu0 || !ry || !u0 || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
-    if (h->have_im) return MPCQP_ERR_UNSUPPORTED;
+    if (h->est == EST_IM) return MPCQP_ERR_UNSUPPORTED;
     if (!h->ex_prepared || !h->ex_law || explicit_constrained(h)) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     const size_t B = d.B, sz = sizeof(double);
-    int rc = upload(h, h->s_x, xhat0, B * d.nxh * sz);
-    if (!rc) rc = upload(h, h->s_lu, lastu0, B * d.nu * sz);
-    if (!rc) rc = upload(h, h->s_ry, ry, B * d.ny * sz);
-    if (!rc && d.nd > 0) rc = upload(h, h->s_d0, d0, B * d.nd * sz);
-    if (!rc && Ztilde) rc = dev_alloc(h, h->s_Z, B * d.nZ * sz);
-    if (!rc) rc = dev_alloc(h, h->s_u0, B * d.nu * sz);
-    if (!rc) rc = dev_alloc(h, h->s_st, B * sizeof(int32_t));
-    if (rc) return rc;
-    rc = mpcqp_explicit_law_device(h, (const double*)h->s_x.p, (const double*)h->s_lu.p, (const double*)h->s_ry.p,
-                                   d.nd > 0 ? (const double*)h->s_d0.p : nullptr, Ztilde ? (double*)h->s_Z.p : nullptr,
-                                   (double*)h->s_u0.p, (int32_t*)h->s_st.p, h->stream);
-    if (rc) return rc;
-    if (Ztilde) HIPCHK(hipMemcpyAsync(Ztilde, h->s_Z.p, B * d.nZ * sz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(u0, h->s_u0.p, B * d.nu * sz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(status, h->s_st.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    Staging s{h};
+    const double* dx = s.in(h->s_x, xhat0, B * d.nxh);
+    const double* dlu = s.in(h->s_lu, lastu0, B * d.nu);
+    const double* dry = s.in(h->s_ry, ry, B * d.ny);
+    const double* dd0 = s.in(h->s_d0, d.nd > 0 ? d0 : nullptr, B * d.nd);
+    double* dZ = Ztilde ? s.out<double>(h->s_Z, B * d.nZ) : nullptr;
+    double* du0 = s.out<double>(h->s_u0, B * d.nu);
+    int32_t* dst = s.out<int32_t>(h->s_st, B);
+    if (s.rc) return s.rc;
+    s.rc = mpcqp_explicit_law_device(h, dx, dlu, dry, dd0, dZ, du0, dst, h->stream);
+    s.down(Ztilde, h->s_Z, B * d.nZ * sz);
+    s.down(u0, h->s_u0, B * d.nu * sz);
+    s.down(status, h->s_st, B * sizeof(int32_t));
+    return s.finish();
 }
 
 int mpcqp_kf_set(mpcqp_handle h, const double* Khat, const int32_t* i_ym, int32_t nym) {
@@ -1514,25 +1558,14 @@ int mpcqp_kf_set(mpcqp_handle h, const double* Khat, const int32_t* i_ym, int32_
     const Dims& d = h->d;
     if (nym < 1 || nym > d.ny) return MPCQP_ERR_DIMS;
     if (d.nxh > 64) return MPCQP_ERR_UNSUPPORTED;
-    for (int i = 0; i < nym; ++i) {
-        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;     // validate_ym, construct.jl:190-196
-        for (int j = 0; j < i; ++j)
-            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
-    }
+    { int rc = check_iym(d, i_ym, nym); if (rc) return rc; }
     ON_DEVICE(h);
     int rc = upload(h, h->kf_K, Khat, (size_t)d.B * d.nxh * nym * sizeof(double));
     if (!rc) rc = upload(h, h->kf_iym, i_ym, (size_t)nym * sizeof(int32_t));
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->kf.Khat = (const double*)h->kf_K.p;
-    h->kf.i_ym = (const int*)h->kf_iym.p;
-    h->kf.nym = nym;
-    h->have_kf = true;
-    h->have_im = false;
-    h->mhe = nullptr;           // (a Kalman handle again)
-    h->kf_tv = false;           // (back to the steady gain: the covariance kernel no longer runs)
-    h->kf_steady = false;       // (a gain of the caller's: nothing to re-solve)
-    h->kf_place = false;
+    // (a Kalman handle again, on a gain of the caller's: the covariance kernel no longer runs, nothing to re-solve)
+    adopt_estimator(h, EST_KF_GAIN, (const double*)h->kf_K.p, nym);
     return MPCQP_OK;
 }
 
@@ -1553,15 +1586,11 @@ static bool kf_symmetric(const double* M, size_t B, int n) {
 int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* Rhat, const double* P0,
                              const int32_t* i_ym, int32_t nym) {
     if (!h || !Qhat || !Rhat || !i_ym) return MPCQP_ERR_NULL;
-    if (!P0 && !h->kf_tv) return MPCQP_ERR_NULL;        // (Q̂ / R̂ alone: only on a handle that carries a P̂)
+    if (!P0 && h->est != EST_KF_TV) return MPCQP_ERR_NULL;        // (Q̂ / R̂ alone: only on a handle that carries a P̂)
     const Dims& d = h->d;
     if (nym < 1 || nym > d.ny) return MPCQP_ERR_DIMS;
     if (!P0 && nym != h->kf.nym) return MPCQP_ERR_DIMS;
-    for (int i = 0; i < nym; ++i) {
-        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;     // validate_ym, construct.jl:190-196
-        for (int j = 0; j < i; ++j)
-            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
-    }
+    { int rc = check_iym(d, i_ym, nym); if (rc) return rc; }
     if (std::max(d.nxh, (int)nym) > mhe::NX_MAX || !kf::kf_cov_available()) return MPCQP_ERR_UNSUPPORTED;
     const size_t B = d.B, nn = (size_t)d.nxh * d.nxh, sz = sizeof(double);
     if (!kf_symmetric(Qhat, B, d.nxh) || !kf_symmetric(Rhat, B, nym) || (P0 && !kf_symmetric(P0, B, d.nxh))) return MPCQP_ERR_ARG;
@@ -1578,17 +1607,9 @@ int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* R
         HIPCHK(hipMemsetAsync(h->kf_st.p, 0, B * sizeof(int32_t), h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->kf.Khat = (const double*)h->kf_K.p;
-    h->kf.i_ym = (const int*)h->kf_iym.p;
-    h->kf.nym = nym;
     h->kf_NX = kf::kf_cov_columns_for(std::max(d.nxh, (int)nym));
     h->kf_waves = kf::kf_cov_waves_for(h->device, d.B, h->kf_NX);
-    h->have_kf = true;
-    h->have_im = false;
-    h->mhe = nullptr;
-    h->kf_tv = true;
-    h->kf_steady = false;
-    h->kf_place = false;
+    adopt_estimator(h, EST_KF_TV, (const double*)h->kf_K.p, nym);
     return MPCQP_OK;
 }
 
@@ -1617,11 +1638,7 @@ int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, 
     if (!h || !Qhat || !Rhat || !i_ym) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (nym < 1 || nym > d.ny) return MPCQP_ERR_DIMS;
-    for (int i = 0; i < nym; ++i) {
-        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;     // validate_ym, construct.jl:190-196
-        for (int j = 0; j < i; ++j)
-            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
-    }
+    { int rc = check_iym(d, i_ym, nym); if (rc) return rc; }
     if (std::max(d.nxh, (int)nym) > mhe::NX_MAX || !kf::kf_dare_available()) return MPCQP_ERR_UNSUPPORTED;
     const size_t B = d.B, nn = (size_t)d.nxh * d.nxh, nk = (size_t)d.nxh * nym, sz = sizeof(double);
     if (!kf_symmetric(Qhat, B, d.nxh) || !kf_symmetric(Rhat, B, nym)) return MPCQP_ERR_ARG;
@@ -1640,23 +1657,15 @@ int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, 
     HIPCHK(hipMemsetAsync(h->kf_K.p, 0, B * nk * sz, h->stream));
     HIPCHK(hipMemsetAsync(h->kf_st.p, 0, B * sizeof(int32_t), h->stream));
     HIPCHK(hipMemsetAsync(h->kf_it.p, 0, B * sizeof(int32_t), h->stream));
-    h->kf.Khat = (const double*)h->kf_K.p;
-    h->kf.i_ym = (const int*)h->kf_iym.p;
-    h->kf.nym = nym;
     h->kf_NX = kf::kf_cov_columns_for(std::max(d.nxh, (int)nym));
     h->kf_dare_waves = kf::kf_dare_waves_for(h->device, d.B, h->kf_NX);
-    h->have_kf = true;
-    h->have_im = false;
-    h->mhe = nullptr;
-    h->kf_tv = false;
-    h->kf_steady = true;
-    h->kf_place = false;
+    adopt_estimator(h, EST_KF_STEADY, (const double*)h->kf_K.p, nym);
     return mpcqp_kf_solve_steady(h);
 }
 
 int mpcqp_kf_solve_steady_device(mpcqp_handle h, void* stream) {
     if (!h) return MPCQP_ERR_NULL;
-    if (!h->kf_steady || !h->have_model) return MPCQP_ERR_ORDER;
+    if (h->est != EST_KF_STEADY || !h->have_model) return MPCQP_ERR_ORDER;
     return kf_dare_launch(h, (hipStream_t)stream);
 }
 
@@ -1670,22 +1679,14 @@ int mpcqp_kf_solve_steady(mpcqp_handle h) {
 
 int mpcqp_kf_steady_iters(mpcqp_handle h, int32_t* out) {
     if (!h || !out) return MPCQP_ERR_NULL;
-    if (!h->kf_steady) return MPCQP_ERR_ORDER;
-    ON_DEVICE(h);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, h->kf_it.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MPCQP_OK;
+    if (h->est != EST_KF_STEADY) return MPCQP_ERR_ORDER;
+    return read_back_i32(h, h->kf_it, h->d.B, out);
 }
 
 int mpcqp_kf_steady_path(mpcqp_handle h, int32_t* out) {
     if (!h || !out) return MPCQP_ERR_NULL;
-    if (!h->kf_steady) return MPCQP_ERR_ORDER;
-    ON_DEVICE(h);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, h->kf_path.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MPCQP_OK;
+    if (h->est != EST_KF_STEADY) return MPCQP_ERR_ORDER;
+    return read_back_i32(h, h->kf_path, h->d.B, out);
 }
 
 // One placement of a handle in pole mode (kf_place_kernels.hip: k_kf_place) on the model that is resident now.
@@ -1709,11 +1710,7 @@ int mpcqp_kf_set_poles(mpcqp_handle h, const double* poles, const int32_t* i_ym,
     if (!h || !poles || !i_ym) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (nym < 1 || nym > d.ny) return MPCQP_ERR_DIMS;
-    for (int i = 0; i < nym; ++i) {
-        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;     // validate_ym, construct.jl:190-196
-        for (int j = 0; j < i; ++j)
-            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
-    }
+    { int rc = check_iym(d, i_ym, nym); if (rc) return rc; }
     if (std::max(d.nxh, (int)nym) > kf::PLACE_NMAX || !kf::kf_place_available()) return MPCQP_ERR_UNSUPPORTED;
     const size_t B = d.B, nk = (size_t)d.nxh * nym, sz = sizeof(double);
     for (size_t i = 0; i < B * d.nxh; ++i)
@@ -1729,21 +1726,13 @@ int mpcqp_kf_set_poles(mpcqp_handle h, const double* poles, const int32_t* i_ym,
     HIPCHK(hipMemsetAsync(h->kf_K.p, 0, B * nk * sz, h->stream));
     HIPCHK(hipMemsetAsync(h->kf_st.p, 0, B * sizeof(int32_t), h->stream));
     HIPCHK(hipMemsetAsync(h->kf_it.p, 0, B * sizeof(int32_t), h->stream));
-    h->kf.Khat = (const double*)h->kf_K.p;
-    h->kf.i_ym = (const int*)h->kf_iym.p;
-    h->kf.nym = nym;
-    h->have_kf = true;
-    h->have_im = false;
-    h->mhe = nullptr;
-    h->kf_tv = false;
-    h->kf_steady = false;
-    h->kf_place = true;
+    adopt_estimator(h, EST_KF_PLACE, (const double*)h->kf_K.p, nym);
     return mpcqp_kf_place(h);
 }
 
 int mpcqp_kf_place_device(mpcqp_handle h, void* stream) {
     if (!h) return MPCQP_ERR_NULL;
-    if (!h->kf_place || !h->have_model) return MPCQP_ERR_ORDER;
+    if (h->est != EST_KF_PLACE || !h->have_model) return MPCQP_ERR_ORDER;
     return kf_place_launch(h, (hipStream_t)stream);
 }
 
@@ -1757,7 +1746,7 @@ int mpcqp_kf_place(mpcqp_handle h) {
 
 int mpcqp_kf_set_place_cap(mpcqp_handle h, int32_t cap) {
     if (!h) return MPCQP_ERR_NULL;
-    if (!h->kf_place) return MPCQP_ERR_ORDER;
+    if (h->est != EST_KF_PLACE) return MPCQP_ERR_ORDER;
     if (cap < 0 || cap > kf::PLACE_CAP_MAX) return MPCQP_ERR_ARG;
     h->kf_place_cap = cap;
     return MPCQP_OK;
@@ -1765,17 +1754,13 @@ int mpcqp_kf_set_place_cap(mpcqp_handle h, int32_t cap) {
 
 int mpcqp_kf_place_sweeps(mpcqp_handle h, int32_t* out) {
     if (!h || !out) return MPCQP_ERR_NULL;
-    if (!h->kf_place) return MPCQP_ERR_ORDER;
-    ON_DEVICE(h);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, h->kf_it.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MPCQP_OK;
+    if (h->est != EST_KF_PLACE) return MPCQP_ERR_ORDER;
+    return read_back_i32(h, h->kf_it, h->d.B, out);
 }
 
 int mpcqp_kf_set_state_covariance(mpcqp_handle h, const double* P) {
     if (!h || !P) return MPCQP_ERR_NULL;
-    if (!h->kf_tv) return MPCQP_ERR_ORDER;
+    if (h->est != EST_KF_TV) return MPCQP_ERR_ORDER;
     const Dims& d = h->d;
     if (!kf_symmetric(P, d.B, d.nxh)) return MPCQP_ERR_ARG;
     ON_DEVICE(h);
@@ -1788,28 +1773,24 @@ int mpcqp_kf_set_state_covariance(mpcqp_handle h, const double* P) {
 
 int mpcqp_kf_status(mpcqp_handle h, int32_t* out) {
     if (!h || !out) return MPCQP_ERR_NULL;
-    if (!h->kf_tv && !h->kf_steady && !h->kf_place) return MPCQP_ERR_ORDER;
-    ON_DEVICE(h);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, h->kf_st.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MPCQP_OK;
+    if (!est_has_cov(h) && h->est != EST_KF_PLACE) return MPCQP_ERR_ORDER;     // (a gain of the caller's has no status)
+    return read_back_i32(h, h->kf_st, h->d.B, out);
 }
 
 int mpcqp_kf_lanes_per_estimator(mpcqp_handle h) {
     if (!h) return MPCQP_ERR_NULL;
-    if (h->kf_place) return WAVE;       // (the placement: one member per wavefront at every size)
-    return (h->kf_tv || h->kf_steady) ? kf::kf_cov_lanes_for(h->kf_NX) : 0;
+    if (h->est == EST_KF_PLACE) return WAVE;       // (the placement: one member per wavefront at every size)
+    return est_has_cov(h) ? kf::kf_cov_lanes_for(h->kf_NX) : 0;
 }
 
 int mpcqp_kf_correct_device(mpcqp_handle h, double* xhat0, const double* y0m, const double* d0, void* stream) {
     if (!h || !xhat0) return MPCQP_ERR_NULL;
     if (h->d.nd > 0 && !d0) return MPCQP_ERR_NULL;
-    if (!h->have_model || !h->have_kf) return MPCQP_ERR_ORDER;
+    if (!h->have_model || !est_is_kf(h)) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     if (!y0m)       // ym = nothing: every estimator misses; x̂0, P̂ and K̂ stay, a time-varying handle records status 1
-        return h->kf_tv ? kf_cov_launch(h, kf::COV_NO_YM, nullptr, (hipStream_t)stream) : MPCQP_OK;
-    if (h->kf_tv) { int rc = kf_cov_launch(h, kf::COV_CORRECT, y0m, (hipStream_t)stream); if (rc) return rc; }
+        return h->est == EST_KF_TV ? kf_cov_launch(h, kf::COV_NO_YM, nullptr, (hipStream_t)stream) : MPCQP_OK;
+    if (h->est == EST_KF_TV) { int rc = kf_cov_launch(h, kf::COV_CORRECT, y0m, (hipStream_t)stream); if (rc) return rc; }
     HIPCHK(launch_kf_correct(h->d, h->m, h->kf, xhat0, y0m, d0, (hipStream_t)stream));
     return MPCQP_OK;
 }
@@ -1821,14 +1802,14 @@ int mpcqp_kf_predict_device(mpcqp_handle h, double* xhat0, const double* u0, con
     if (h->d.nxh > 64) return MPCQP_ERR_UNSUPPORTED;
     ON_DEVICE(h);
     HIPCHK(launch_kf_predict(h->d, h->m, xhat0, u0, d0, (hipStream_t)stream));
-    if (h->kf_tv) { int rc = kf_cov_launch(h, kf::COV_PREDICT, nullptr, (hipStream_t)stream); if (rc) return rc; }
+    if (h->est == EST_KF_TV) { int rc = kf_cov_launch(h, kf::COV_PREDICT, nullptr, (hipStream_t)stream); if (rc) return rc; }
     return MPCQP_OK;
 }
 
 int mpcqp_kf_set_direct(mpcqp_handle h, int32_t direct) {
     if (!h) return MPCQP_ERR_NULL;
     if (direct != 0 && direct != 1) return MPCQP_ERR_ARG;
-    if (h->have_im && direct == 0) return MPCQP_ERR_ARG;        // (InternalModel: always the filter form)
+    if (h->est == EST_IM && direct == 0) return MPCQP_ERR_ARG;        // (InternalModel: always the filter form)
     h->kf_direct = direct;
     return MPCQP_OK;
 }
@@ -1838,11 +1819,11 @@ int mpcqp_kf_set_direct(mpcqp_handle h, int32_t direct) {
 int mpcqp_kf_update_device(mpcqp_handle h, double* xhat0, const double* u0, const double* y0m, const double* d0, void* stream) {
     if (!h || !xhat0 || !u0) return MPCQP_ERR_NULL;
     if (h->d.nd > 0 && !d0) return MPCQP_ERR_NULL;
-    if (!h->have_model || !h->have_kf) return MPCQP_ERR_ORDER;
+    if (!h->have_model || !est_is_kf(h)) return MPCQP_ERR_ORDER;
     if (h->d.nxh > 64) return MPCQP_ERR_UNSUPPORTED;
     ON_DEVICE(h);
     hipStream_t st = (hipStream_t)stream;
-    if (h->kf_tv) {
+    if (h->est == EST_KF_TV) {
         int rc = kf_cov_launch(h, (y0m ? kf::COV_CORRECT : kf::COV_NO_YM) | kf::COV_PREDICT, y0m, st);
         if (rc) return rc;
     }
@@ -1853,22 +1834,20 @@ int mpcqp_kf_update_device(mpcqp_handle h, double* xhat0, const double* u0, cons
 
 int mpcqp_kf_update(mpcqp_handle h, double* xhat0, const double* u0, const double* y0m, const double* d0) {
     if (!h || !xhat0 || !u0) return MPCQP_ERR_NULL;
-    if (!h->have_model || !h->have_kf) return MPCQP_ERR_ORDER;
+    if (!h->have_model || !est_is_kf(h)) return MPCQP_ERR_ORDER;
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
     ON_DEVICE(h);
-    const size_t B = d.B, sz = sizeof(double);
-    int rc = upload(h, h->kf_x, xhat0, B * d.nxh * sz);
-    if (!rc) rc = upload(h, h->kf_u, u0, B * d.nu * sz);
-    if (!rc && y0m) rc = upload(h, h->kf_y, y0m, B * (size_t)h->kf.nym * sz);
-    if (!rc && d.nd > 0) rc = upload(h, h->kf_d, d0, B * d.nd * sz);
-    if (rc) return rc;
-    rc = mpcqp_kf_update_device(h, (double*)h->kf_x.p, (const double*)h->kf_u.p, y0m ? (const double*)h->kf_y.p : nullptr,
-                                d.nd > 0 ? (const double*)h->kf_d.p : nullptr, h->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(xhat0, h->kf_x.p, B * d.nxh * sz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    const size_t B = d.B;
+    Staging s{h};
+    double* dx = s.in(h->kf_x, xhat0, B * d.nxh);
+    const double* du = s.in(h->kf_u, u0, B * d.nu);
+    const double* dy = s.in(h->kf_y, y0m, B * (size_t)h->kf.nym);
+    const double* dd = s.in(h->kf_d, d.nd > 0 ? d0 : nullptr, B * d.nd);
+    if (s.rc) return s.rc;
+    s.rc = mpcqp_kf_update_device(h, dx, du, dy, dd, h->stream);
+    s.down(xhat0, h->kf_x, B * d.nxh * sizeof(double));
+    return s.finish();
 }
 
 static int kf_host(mpcqp_handle h, double* xhat0, const double* a, size_t na, const double* d0, bool correct) {
@@ -1876,22 +1855,19 @@ static int kf_host(mpcqp_handle h, double* xhat0, const double* a, size_t na, co
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
     ON_DEVICE(h);
-    const size_t B = d.B, sz = sizeof(double);
-    int rc = upload(h, h->kf_x, xhat0, B * d.nxh * sz);
-    if (!rc && a) rc = upload(h, correct ? h->kf_y : h->kf_u, a, B * na * sz);
-    if (!rc && d.nd > 0) rc = upload(h, h->kf_d, d0, B * d.nd * sz);
-    if (rc) return rc;
-    const double* dd = d.nd > 0 ? (const double*)h->kf_d.p : nullptr;
-    rc = correct ? mpcqp_kf_correct_device(h, (double*)h->kf_x.p, a ? (const double*)h->kf_y.p : nullptr, dd, h->stream)
-                 : mpcqp_kf_predict_device(h, (double*)h->kf_x.p, (const double*)h->kf_u.p, dd, h->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(xhat0, h->kf_x.p, B * d.nxh * sz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    const size_t B = d.B;
+    Staging s{h};
+    double* dx = s.in(h->kf_x, xhat0, B * d.nxh);
+    const double* da = s.in(correct ? h->kf_y : h->kf_u, a, B * na);
+    const double* dd = s.in(h->kf_d, d.nd > 0 ? d0 : nullptr, B * d.nd);
+    if (s.rc) return s.rc;
+    s.rc = correct ? mpcqp_kf_correct_device(h, dx, da, dd, h->stream) : mpcqp_kf_predict_device(h, dx, da, dd, h->stream);
+    s.down(xhat0, h->kf_x, B * d.nxh * sizeof(double));
+    return s.finish();
 }
 
 int mpcqp_kf_correct(mpcqp_handle h, double* xhat0, const double* y0m, const double* d0) {
-    if (h && !h->have_kf) return MPCQP_ERR_ORDER;
+    if (h && !est_is_kf(h)) return MPCQP_ERR_ORDER;
     return kf_host(h, xhat0, y0m, h ? (size_t)h->kf.nym : 0, d0, true);
 }
 
@@ -1899,28 +1875,7 @@ int mpcqp_kf_predict(mpcqp_handle h, double* xhat0, const double* u0, const doub
     return kf_host(h, xhat0, u0, h ? (size_t)h->d.nu : 0, d0, false);
 }
 
-// ---- InternalModel (include/mpcqp.h; kernels: im_bodies.h) -------------------------------------------------------------------
-
-static void im_args(mpcqp_handle h, im::ImArgs& a) {
-    const Dims& d = h->d;
-    a.Ahat = h->m.Ahat; a.Bu = h->m.Bu; a.C = h->m.C; a.Bd = d.nd > 0 ? h->m.Bd : nullptr; a.Dd = d.nd > 0 ? h->m.Dd : nullptr;
-    a.dop = h->m.dop; a.Bvec = h->m.Bvec; a.i_ym = h->kf.i_ym;
-    a.B = d.B; a.nx = d.nxh; a.nu = d.nu; a.ny = d.ny; a.nd = d.nd; a.nym = h->kf.nym; a.nxs = h->im_nxs; a.Hp = d.Hp;
-    a.G = im::group_lanes(a.nx, a.nu, a.ny, a.nd, a.nxs);
-    a.As = (const double*)h->im_As.p; a.Bs = (const double*)h->im_Bs.p; a.Cs = (const double*)h->im_Cs.p; a.Ds = (const double*)h->im_Ds.p;
-    a.Ahs = (double*)h->im_Ahs.p; a.Bhs = (double*)h->im_Bhs.p;
-    a.xs = (double*)h->im_xs.p; a.ys = (double*)h->im_ys.p; a.Yhs = (double*)h->im_Yhs.p; a.Beff = (double*)h->im_Beff.p;
-    a.z = (double*)h->im_z.p; a.status = (int32_t*)h->im_st.p;
-}
-
-// B_eff = B + Ŷs after k_predmat wrote a new B (mpcqp_set_model, mpcqp_recondense_device)
-static int im_refresh(mpcqp_handle h, hipStream_t st) {
-    if (!h->have_im) return MPCQP_OK;
-    im::ImArgs a{};
-    im_args(h, a);
-    HIPCHK(im::launch_im(a, im::IM_BEFF, st));
-    return MPCQP_OK;
-}
+// ---- InternalModel: the entry points (im_args and im_refresh are above) --------------------------------------------------------
 
 int mpcqp_im_set(mpcqp_handle h, int32_t nxs, const double* As, const double* Bs, const double* Cs, const double* Ds,
                  const int32_t* i_ym, int32_t nym) {
@@ -1931,11 +1886,7 @@ int mpcqp_im_set(mpcqp_handle h, int32_t nxs, const double* As, const double* Bs
     if (given != 0 && given != 4) return MPCQP_ERR_ARG;
     if (given == 0) nxs = nym;      // the default: the identity in all four
     if (nxs < 1) return MPCQP_ERR_ARG;
-    for (int i = 0; i < nym; ++i) {
-        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;     // validate_ym, construct.jl:190-196
-        for (int j = 0; j < i; ++j)
-            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
-    }
+    { int rc = check_iym(d, i_ym, nym); if (rc) return rc; }
     if (!im::im_available() || !im::dims_ok(d.nxh, d.nu, d.ny, d.nd, nym, nxs)) return MPCQP_ERR_UNSUPPORTED;
     if (h->in_multi || h->ex_prepared || d.nW > 0 || uses_stage_kernel(h)) return MPCQP_ERR_UNSUPPORTED;
     ON_DEVICE(h);
@@ -1962,36 +1913,31 @@ int mpcqp_im_set(mpcqp_handle h, int32_t nxs, const double* As, const double* Bs
     if (!rc) rc = dev_alloc(h, h->im_Yhs, B * d.nY * sz);
     if (!rc) rc = dev_alloc(h, h->im_Beff, B * d.nY * sz);
     if (!rc) rc = dev_alloc(h, h->im_st, B * sizeof(int32_t));
-    if (rc) { h->have_im = false; return rc; }
-    h->kf.Khat = nullptr;
-    h->kf.i_ym = (const int*)h->kf_iym.p;
-    h->kf.nym = nym;
+    if (rc) {       // (its buffers may be half replaced: an InternalModel is dropped, any other estimator is left alone)
+        if (h->est == EST_IM) h->est = EST_NONE;
+        return rc;
+    }
     h->im_nxs = nxs;
-    h->have_kf = h->kf_tv = h->kf_steady = h->kf_place = false;       // (replaces a Kalman filter or an attached MovingHorizonEstimator)
-    h->mhe = nullptr;
+    adopt_estimator(h, EST_IM, nullptr, nym);       // (replaces a Kalman filter or an attached MovingHorizonEstimator)
     h->kf_direct = 1;
-    h->have_im = true;
     im::ImArgs a{};
     im_args(h, a);
     const hipError_t e = im::launch_im(a, im::IM_SETUP, h->stream);
-    if (e != hipSuccess) { h->have_im = false; HIPCHK(e); }
+    if (e != hipSuccess) { h->est = EST_NONE; HIPCHK(e); }
     HIPCHK(hipStreamSynchronize(h->stream));
     return MPCQP_OK;
 }
 
 int mpcqp_im_status(mpcqp_handle h, int32_t* out) {
     if (!h || !out) return MPCQP_ERR_NULL;
-    if (!h->have_im) return MPCQP_ERR_ORDER;
-    ON_DEVICE(h);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, h->im_st.p, (size_t)h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MPCQP_OK;
+    if (h->est != EST_IM) return MPCQP_ERR_ORDER;
+    return read_back_i32(h, h->im_st, h->d.B, out);
 }
 
 int mpcqp_im_correct_device(mpcqp_handle h, const double* xhat0, const double* y0m, const double* d0, void* stream) {
     if (!h || !xhat0 || !y0m) return MPCQP_ERR_NULL;
     if (h->d.nd > 0 && !d0) return MPCQP_ERR_NULL;
-    if (!h->have_model || !h->have_im) return MPCQP_ERR_ORDER;
+    if (!h->have_model || h->est != EST_IM) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     im::ImArgs a{};
     im_args(h, a);
@@ -2003,7 +1949,7 @@ int mpcqp_im_correct_device(mpcqp_handle h, const double* xhat0, const double* y
 int mpcqp_im_update_device(mpcqp_handle h, double* xhat0, const double* u0, const double* d0, void* stream) {
     if (!h || !xhat0 || !u0) return MPCQP_ERR_NULL;
     if (h->d.nd > 0 && !d0) return MPCQP_ERR_NULL;
-    if (!h->have_model || !h->have_im) return MPCQP_ERR_ORDER;
+    if (!h->have_model || h->est != EST_IM) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
     im::ImArgs a{};
     im_args(h, a);
@@ -2016,20 +1962,17 @@ static int im_host(mpcqp_handle h, double* xhat0, const double* v, const double*
     if (!h || !xhat0 || !v) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
-    if (!h->have_model || !h->have_im) return MPCQP_ERR_ORDER;
+    if (!h->have_model || h->est != EST_IM) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
-    const size_t B = d.B, sz = sizeof(double);
-    int rc = upload(h, h->kf_x, xhat0, B * d.nxh * sz);
-    if (!rc) rc = upload(h, correct ? h->kf_y : h->kf_u, v, B * (size_t)(correct ? h->kf.nym : d.nu) * sz);
-    if (!rc && d.nd > 0) rc = upload(h, h->kf_d, d0, B * d.nd * sz);
-    if (rc) return rc;
-    const double* dd = d.nd > 0 ? (const double*)h->kf_d.p : nullptr;
-    rc = correct ? mpcqp_im_correct_device(h, (const double*)h->kf_x.p, (const double*)h->kf_y.p, dd, h->stream)
-                 : mpcqp_im_update_device(h, (double*)h->kf_x.p, (const double*)h->kf_u.p, dd, h->stream);
-    if (rc) return rc;
-    if (!correct) HIPCHK(hipMemcpyAsync(xhat0, h->kf_x.p, B * d.nxh * sz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    const size_t B = d.B;
+    Staging s{h};
+    double* dx = s.in(h->kf_x, xhat0, B * d.nxh);
+    const double* dv = s.in(correct ? h->kf_y : h->kf_u, v, B * (size_t)(correct ? h->kf.nym : d.nu));
+    const double* dd = s.in(h->kf_d, d.nd > 0 ? d0 : nullptr, B * d.nd);
+    if (s.rc) return s.rc;
+    s.rc = correct ? mpcqp_im_correct_device(h, dx, dv, dd, h->stream) : mpcqp_im_update_device(h, dx, dv, dd, h->stream);
+    s.down(correct ? nullptr : xhat0, h->kf_x, B * d.nxh * sizeof(double));      // (the correction leaves x̂0 as it is)
+    return s.finish();
 }
 
 int mpcqp_im_correct(mpcqp_handle h, const double* xhat0, const double* y0m, const double* d0) {
@@ -2042,7 +1985,10 @@ int mpcqp_im_update(mpcqp_handle h, double* xhat0, const double* u0, const doubl
 
 int mpcqp_mhe_attach(mpcqp_handle h, mpcqp_mhe e, const int32_t* i_ym, int32_t nym) {
     if (!h) return MPCQP_ERR_NULL;
-    if (!e) { h->mhe = nullptr; return MPCQP_OK; }
+    if (!e) {       // detach only: an attachment goes, any other estimator stays
+        if (h->est == EST_MHE) { h->est = EST_NONE; h->mhe = nullptr; }
+        return MPCQP_OK;
+    }
     if (!i_ym) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     mpcqp_mhe_dims ed{};
@@ -2050,20 +1996,12 @@ int mpcqp_mhe_attach(mpcqp_handle h, mpcqp_mhe e, const int32_t* i_ym, int32_t n
     if (ed.batch != d.B || ed.nxhat != d.nxh || ed.nu != d.nu || ed.nd != d.nd || ed.nym != nym || ed.device != h->device ||
         nym < 1 || nym > d.ny)
         return MPCQP_ERR_DIMS;
-    for (int i = 0; i < nym; ++i) {
-        if (i_ym[i] < 0 || i_ym[i] >= d.ny) return MPCQP_ERR_ARG;     // validate_ym, construct.jl:190-196
-        for (int j = 0; j < i; ++j)
-            if (i_ym[j] == i_ym[i]) return MPCQP_ERR_ARG;
-    }
+    { int rc = check_iym(d, i_ym, nym); if (rc) return rc; }
     ON_DEVICE(h);
     int rc = upload(h, h->kf_iym, i_ym, (size_t)nym * sizeof(int32_t));
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->kf.Khat = nullptr;
-    h->kf.i_ym = (const int*)h->kf_iym.p;
-    h->kf.nym = nym;
-    h->have_kf = h->kf_tv = h->kf_steady = h->kf_place = false;       // (the attachment replaces a Kalman filter)
-    h->have_im = false;
+    adopt_estimator(h, EST_MHE, nullptr, nym);      // (the attachment replaces a Kalman filter or an InternalModel)
     h->mhe = e;
     return MPCQP_OK;
 }
@@ -2073,7 +2011,7 @@ int mpcqp_est_initstate_device(mpcqp_handle h, double* xhat0, const double* u0, 
     if (!h || !xhat0 || !u0 || !y0m || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
-    if (h->have_im) {           // init_estimate! of the InternalModel: x̂d, ŷs and x̂s (k_im_init)
+    if (h->est == EST_IM) {           // init_estimate! of the InternalModel: x̂d, ŷs and x̂s (k_im_init)
         if (!h->have_model) return MPCQP_ERR_ORDER;
         ON_DEVICE(h);
         im::ImArgs a{};
@@ -2082,7 +2020,7 @@ int mpcqp_est_initstate_device(mpcqp_handle h, double* xhat0, const double* u0, 
         HIPCHK(im::launch_im(a, im::IM_INIT, (hipStream_t)stream));
         return MPCQP_OK;
     }
-    if (!(h->have_kf || h->mhe) || !h->have_model) return MPCQP_ERR_ORDER;
+    if (!est_any(h) || !h->have_model) return MPCQP_ERR_ORDER;
     if (std::max(d.nxh, h->kf.nym) > est::EST_INIT_NMAX || !est::est_init_available()) return MPCQP_ERR_UNSUPPORTED;
     ON_DEVICE(h);
     est::InitArgs a{};
@@ -2098,22 +2036,20 @@ int mpcqp_est_initstate(mpcqp_handle h, double* xhat0, const double* u0, const d
     if (!h || !xhat0 || !u0 || !y0m || !status) return MPCQP_ERR_NULL;
     const Dims& d = h->d;
     if (d.nd > 0 && !d0) return MPCQP_ERR_NULL;
-    if (!(h->have_kf || h->mhe || h->have_im) || !h->have_model) return MPCQP_ERR_ORDER;
+    if (!est_any(h) || !h->have_model) return MPCQP_ERR_ORDER;
     ON_DEVICE(h);
-    const size_t B = d.B, sz = sizeof(double);
-    int rc = upload(h, h->ei_x, xhat0, B * d.nxh * sz);
-    if (!rc) rc = upload(h, h->ei_u, u0, B * d.nu * sz);
-    if (!rc) rc = upload(h, h->ei_y, y0m, B * (size_t)h->kf.nym * sz);
-    if (!rc && d.nd > 0) rc = upload(h, h->ei_d, d0, B * d.nd * sz);
-    if (!rc) rc = dev_alloc(h, h->ei_st, B * sizeof(int32_t));
-    if (rc) return rc;
-    rc = mpcqp_est_initstate_device(h, (double*)h->ei_x.p, (const double*)h->ei_u.p, (const double*)h->ei_y.p,
-                                    d.nd > 0 ? (const double*)h->ei_d.p : nullptr, (int32_t*)h->ei_st.p, h->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(xhat0, h->ei_x.p, B * d.nxh * sz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(status, h->ei_st.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    const size_t B = d.B;
+    Staging s{h};
+    double* dx = s.in(h->ei_x, xhat0, B * d.nxh);
+    const double* du = s.in(h->ei_u, u0, B * d.nu);
+    const double* dy = s.in(h->ei_y, y0m, B * (size_t)h->kf.nym);
+    const double* dd = s.in(h->ei_d, d.nd > 0 ? d0 : nullptr, B * d.nd);
+    int32_t* dst = s.out<int32_t>(h->ei_st, B);
+    if (s.rc) return s.rc;
+    s.rc = mpcqp_est_initstate_device(h, dx, du, dy, dd, dst, h->stream);
+    s.down(xhat0, h->ei_x, B * d.nxh * sizeof(double));
+    s.down(status, h->ei_st, B * sizeof(int32_t));
+    return s.finish();
 }
 
 // ---- sim!: the closed loop of the whole batch, plant included (include/mpcqp.h; kernel: sim_bodies.h) ----------------------
@@ -2141,11 +2077,9 @@ int mpcqp_sim_set_plant(mpcqp_handle h, int32_t nxp, const double* A, const doub
     return MPCQP_OK;
 }
 
-static bool explicit_constrained(mpcqp_handle h);
-
 // the handle's side of the fused path's eligibility (include/mpcqp.h); the call's side is sim_fused below
 static bool sim_fused_handle(mpcqp_handle h) {
-    if (!sim::sim_fused_available() || !h->have_plant || !h->have_kf || h->kf_tv) return false;
+    if (!sim::sim_fused_available() || !h->have_plant || !est_is_kf(h) || h->est == EST_KF_TV) return false;
     if (!h->have_model || !h->have_weights || !h->ex_prepared || !h->ex_law || explicit_constrained(h)) return false;
     const Dims& d = h->d;
     sim::PlantArgs p{};
@@ -2177,8 +2111,8 @@ static int sim_check(mpcqp_handle h, const mpcqp_sim_io* io) {
     if (!h || !io) return MPCQP_ERR_NULL;
     if (io->N <= 0 || (io->flags & ~(MPCQP_SIM_FLAG_RY_PER_PERIOD | MPCQP_SIM_FLAG_NO_FUSE))) return MPCQP_ERR_ARG;
     const int ctrl = sim_controller(h, io);
-    if (!h->have_plant || !(h->have_kf || h->mhe || h->have_im) || ctrl == SIM_CTRL_NONE) return MPCQP_ERR_ORDER;
-    if (h->have_im && (ctrl != SIM_CTRL_STEP || uses_stage_kernel(h) || h->d.nW > 0)) return MPCQP_ERR_UNSUPPORTED;
+    if (!h->have_plant || !est_any(h) || ctrl == SIM_CTRL_NONE) return MPCQP_ERR_ORDER;
+    if (h->est == EST_IM && (ctrl != SIM_CTRL_STEP || uses_stage_kernel(h) || h->d.nW > 0)) return MPCQP_ERR_UNSUPPORTED;
     if (!io->ry || !io->x0 || !io->xhat0 || !io->lastu0 || (h->d.nd > 0 && !io->d)) return MPCQP_ERR_NULL;
     if (!io->Ztilde && ctrl != SIM_CTRL_EXPLICIT_LAW) return MPCQP_ERR_NULL;
     if ((io->sigma_u && !io->w_u) || (io->sigma_y && !io->w_y) || (io->sigma_x && !io->w_x) ||
@@ -2225,7 +2159,7 @@ int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io_in, void* stream) {
     a.Bd = h->sp_has_Bd ? (const double*)h->sp_Bd.p : nullptr; a.Dd = h->sp_has_Dd ? (const double*)h->sp_Dd.p : nullptr;
     a.fx = h->sp_has_fx ? (const double*)h->sp_fx.p : nullptr;
     a.Chat = h->m.C; a.Dhd = d.nd > 0 ? h->m.Dd : nullptr; a.i_ym = h->kf.i_ym;
-    a.yhs = h->have_im ? (const double*)h->im_ys.p : nullptr;       // evaloutput of the InternalModel: + ŷs
+    a.yhs = h->est == EST_IM ? (const double*)h->im_ys.p : nullptr;       // evaloutput of the InternalModel: + ŷs
     a.B = d.B; a.nxp = h->sim_nxp; a.nu = d.nu; a.ny = d.ny; a.nd = d.nd; a.nym = h->kf.nym; a.nxh = d.nxh; a.Hp = d.Hp; a.N = N;
     a.G = sim::group_lanes(a.nxp, a.nu, a.ny, a.nd, a.nym);
     a.ry = io->ry; a.d = io->d; a.ry_per_period = per_period ? 1 : 0;
@@ -2268,7 +2202,7 @@ int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io_in, void* stream) {
     HIPCHK(plant(-1, -1, 0));
     for (int i = 0; i < N; ++i) {
         if (est) { rc = mpcqp_mhe_prepare_stream(est, y0m, d0, stream); if (rc) return rc; }      // (predictor form: nothing)
-        else if (h->have_im) { rc = mpcqp_im_correct_device(h, io->xhat0, y0m, d0, stream); if (rc) return rc; }
+        else if (h->est == EST_IM) { rc = mpcqp_im_correct_device(h, io->xhat0, y0m, d0, stream); if (rc) return rc; }
         else if (h->kf_direct) { rc = mpcqp_kf_correct_device(h, io->xhat0, y0m, d0, stream); if (rc) return rc; }
         if (io->Xhat || io->Yhat) HIPCHK(plant(i, -1, -1));
         switch (ctrl) {
@@ -2287,7 +2221,7 @@ int mpcqp_sim_device(mpcqp_handle h, const mpcqp_sim_io* io_in, void* stream) {
             if (rc) return rc;
             // the estimator's status of this period (the solve of preparestate! or, predictor form, of updatestate!)
             HIPCHK(hipMemcpyAsync((int32_t*)h->sim_est.p + (size_t)i * B, est_st, B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        } else if (h->have_im) {
+        } else if (h->est == EST_IM) {
             rc = mpcqp_im_update_device(h, io->xhat0, u0, d0, stream);
             if (rc) return rc;
         } else {
@@ -2309,9 +2243,7 @@ int mpcqp_sim_est_status(mpcqp_handle h, int32_t* out, int32_t N) {
     if (h->sim_est_N < 1 || !h->sim_est.p) return MPCQP_ERR_ORDER;
     if (N < 1 || N > h->sim_est_N) return MPCQP_ERR_ARG;
     ON_DEVICE(h);
-    HIPCHK(hipDeviceSynchronize());         // (the run may have been enqueued on a stream of the caller's)
-    HIPCHK(hipMemcpy(out, h->sim_est.p, (size_t)N * h->d.B * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MPCQP_OK;
+    return read_back_i32(h, h->sim_est, (size_t)N * h->d.B, out);
 }
 
 int mpcqp_sim(mpcqp_handle h, const mpcqp_sim_io* io) {
@@ -2321,52 +2253,43 @@ int mpcqp_sim(mpcqp_handle h, const mpcqp_sim_io* io) {
     const size_t B = d.B, N = (size_t)io->N, sz = sizeof(double), nxp = (size_t)h->sim_nxp;
     const size_t nry = (io->flags & MPCQP_SIM_FLAG_RY_PER_PERIOD) ? N * d.ny : (size_t)d.ny;
     mpcqp_sim_io dv = *io;
-    int rc = MPCQP_OK, k = 0;
+    Staging s{h};
+    int k = 0;
     // inputs and the in/out state go up, records are allocated; every array has its own staging buffer
-    auto in = [&](const double*& p, size_t n) {
-        DBuf& b = h->sim_s[k++];
-        if (!p || rc) return;
-        rc = upload(h, b, p, B * n * sz);
-        p = (const double*)b.p;
-    };
+    auto in = [&](const double*& p, size_t n) { p = s.in(h->sim_s[k++], p, B * n); };
     auto io_ = [&](double*& p, size_t n, bool up) {
         DBuf& b = h->sim_s[k++];
-        if (!p || rc) return;
-        rc = up ? upload(h, b, p, B * n * sz) : dev_alloc(h, b, B * n * sz);
-        p = (double*)b.p;
+        p = !p ? nullptr : up ? s.in(b, p, B * n) : s.out<double>(b, B * n);
     };
     in(dv.ry, nry); in(dv.Ru, d.nU); in(dv.d, d.nd);
     in(dv.u_step, d.nu); in(dv.y_step, d.ny); in(dv.d_step, d.nd);
     in(dv.sigma_u, d.nu); in(dv.sigma_y, d.ny); in(dv.sigma_d, d.nd); in(dv.sigma_x, nxp);
     in(dv.w_u, N * d.nu); in(dv.w_y, N * d.ny); in(dv.w_d, N * d.nd); in(dv.w_x, N * nxp);
+    const int k_out = k;
     io_(dv.x0, nxp, true); io_(dv.xhat0, d.nxh, true); io_(dv.lastu0, d.nu, true); io_(dv.Ztilde, d.nZ, true);
     io_(dv.Y, N * d.ny, false); io_(dv.X, N * nxp, false); io_(dv.D, N * d.nd, false); io_(dv.Xhat, N * d.nxh, false);
     io_(dv.Yhat, N * d.ny, false); io_(dv.U, N * d.nu, false); io_(dv.Ud, N * d.nu, false);
-    if (!rc && io->status) {
-        rc = dev_alloc(h, h->sim_s[k], B * N * sizeof(int32_t));
-        dv.status = (int32_t*)h->sim_s[k].p;
-    }
-    if (rc) return rc;
+    dv.status = io->status ? s.out<int32_t>(h->sim_s[k], B * N) : nullptr;
+    if (s.rc) return s.rc;
     if (d.nd == 0) dv.d = dv.d_step = dv.sigma_d = dv.w_d = nullptr, dv.D = nullptr;
-    rc = mpcqp_sim_device(h, &dv, h->stream);
-    if (rc) return rc;
-    auto down = [&](void* host, const void* dev, size_t bytes) {
-        return (host && dev) ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-    };
-    HIPCHK(down(io->x0, dv.x0, B * nxp * sz));
-    HIPCHK(down(io->xhat0, dv.xhat0, B * d.nxh * sz));
-    HIPCHK(down(io->lastu0, dv.lastu0, B * d.nu * sz));
-    HIPCHK(down(io->Ztilde, dv.Ztilde, B * d.nZ * sz));
-    HIPCHK(down(io->Y, dv.Y, B * N * d.ny * sz));
-    HIPCHK(down(io->X, dv.X, B * N * nxp * sz));
-    HIPCHK(down(io->D, dv.D, B * N * d.nd * sz));
-    HIPCHK(down(io->Xhat, dv.Xhat, B * N * d.nxh * sz));
-    HIPCHK(down(io->Yhat, dv.Yhat, B * N * d.ny * sz));
-    HIPCHK(down(io->U, dv.U, B * N * d.nu * sz));
-    HIPCHK(down(io->Ud, dv.Ud, B * N * d.nu * sz));
-    HIPCHK(down(io->status, dv.status, B * N * sizeof(int32_t)));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MPCQP_OK;
+    s.rc = mpcqp_sim_device(h, &dv, h->stream);
+    // back in the same order, from the same buffers (what the device call was not given -- D without a measured
+    // disturbance -- stays as the caller has it)
+    k = k_out;
+    auto down = [&](void* host, const void* dev, size_t bytes) { s.down(dev ? host : nullptr, h->sim_s[k++], bytes); };
+    down(io->x0, dv.x0, B * nxp * sz);
+    down(io->xhat0, dv.xhat0, B * d.nxh * sz);
+    down(io->lastu0, dv.lastu0, B * d.nu * sz);
+    down(io->Ztilde, dv.Ztilde, B * d.nZ * sz);
+    down(io->Y, dv.Y, B * N * d.ny * sz);
+    down(io->X, dv.X, B * N * nxp * sz);
+    down(io->D, dv.D, B * N * d.nd * sz);
+    down(io->Xhat, dv.Xhat, B * N * d.nxh * sz);
+    down(io->Yhat, dv.Yhat, B * N * d.ny * sz);
+    down(io->U, dv.U, B * N * d.nu * sz);
+    down(io->Ud, dv.Ud, B * N * d.nu * sz);
+    down(io->status, dv.status, B * N * sizeof(int32_t));
+    return s.finish();
 }
 
 static thread_local std::string g_build_err;
@@ -2375,14 +2298,6 @@ const char* mpcqp_last_build_error(void) { return g_build_err.c_str(); }
 
 // One cold-started step of the first few controllers of the handle on pseudo-random states / set points, once
 // with the on-demand specialisation and once with the runtime-dimension kernel: same iterates up to rounding.
-static int self_test_spec_impl(mpcqp_handle h, double* worst, std::string* why, DBuf& yh, DBuf& in, DBuf& out, DBuf& sti);
-static int self_test_spec(mpcqp_handle h, double* worst, std::string* why) {
-    DBuf yh, in, out, sti;           // scratch of the comparison: released on every path
-    const int rc = self_test_spec_impl(h, worst, why, yh, in, out, sti);
-    (void)hipStreamSynchronize(h->stream);
-    dev_release(h, yh); dev_release(h, in); dev_release(h, out); dev_release(h, sti);
-    return rc;
-}
 static int self_test_spec_impl(mpcqp_handle h, double* worst, std::string* why, DBuf& yh, DBuf& in, DBuf& out, DBuf& sti) {
     Dims d = h->d;
     d.B = d.B < 8 ? d.B : 8;
@@ -2483,6 +2398,14 @@ static int self_test_spec_impl(mpcqp_handle h, double* worst, std::string* why, 
     // one figure for the caller's tolerance (1e-6): the first iterates are held to 1e-8
     *worst = std::fmax(rel_opt, worst_it * 100.0);
     return MPCQP_OK;
+}
+
+static int self_test_spec(mpcqp_handle h, double* worst, std::string* why) {
+    DBuf yh, in, out, sti;           // scratch of the comparison: released on every path
+    const int rc = self_test_spec_impl(h, worst, why, yh, in, out, sti);
+    (void)hipStreamSynchronize(h->stream);
+    dev_release(h, yh); dev_release(h, in); dev_release(h, out); dev_release(h, sti);
+    return rc;
 }
 
 int mpcqp_prepare(mpcqp_handle h) {
@@ -2705,40 +2628,18 @@ int mpcqp_multi_step(mpcqp_multi mh, const double* xhat0, const double* lastu0, 
     if (!mh || !xhat0 || !lastu0 || !Ry || !Ztilde || !u0 || !status) return MPCQP_ERR_NULL;
     const Dims& dd = mh->d;
     if (dd.nd > 0 && (!d0 || !Dhat0)) return MPCQP_ERR_NULL;
-    const size_t sz = sizeof(double);
-    // phase 1: uploads and the step kernel enqueued on every device's stream
+    // phase 1: uploads, the step kernel and the gather -- each shard's results into its slice of the caller's arrays --
+    // enqueued on every device's stream
     for (size_t g = 0; g < mh->h.size(); ++g) {
         mpcqp_handle h = mh->h[g];
         const Dims& d = h->d;
         const int o = mh->off[g];
-        const size_t B = d.B;
         const size_t nry = (d.flags & MPCQP_FLAG_RY_CONSTANT) ? d.ny : d.nY;
         ON_DEVICE(h);
-        int rc = upload(h, h->s_x, shard_of(xhat0, o, d.nxh), B * d.nxh * sz);
-        if (!rc) rc = upload(h, h->s_lu, shard_of(lastu0, o, d.nu), B * d.nu * sz);
-        if (!rc) rc = upload(h, h->s_ry, shard_of(Ry, o, nry), B * nry * sz);
-        if (!rc && Ru) rc = upload(h, h->s_ru, shard_of(Ru, o, d.nU), B * d.nU * sz);
-        if (!rc && d.nd > 0) rc = upload(h, h->s_d0, shard_of(d0, o, d.nd), B * d.nd * sz);
-        if (!rc && d.nd > 0) rc = upload(h, h->s_dh, shard_of(Dhat0, o, d.nD), B * d.nD * sz);
-        if (!rc) rc = upload(h, h->s_Z, shard_of(Ztilde, o, d.nZ), B * d.nZ * sz);
-        if (!rc) rc = dev_alloc(h, h->s_u0, B * d.nu * sz);
-        if (!rc) rc = dev_alloc(h, h->s_st, B * sizeof(int32_t));
-        if (!rc) rc = dev_alloc(h, h->s_it, B * sizeof(int32_t));
-        if (!rc && Yhat0) rc = dev_alloc(h, h->s_yh, B * d.nY * sz);
+        const int rc = step_staged(h, shard_of(xhat0, o, d.nxh), shard_of(lastu0, o, d.nu), shard_of(Ry, o, nry), shard_of(Ru, o, d.nU),
+                                   shard_of(d0, o, d.nd), shard_of(Dhat0, o, d.nD), shard_of(Ztilde, o, d.nZ), shard_of(u0, o, d.nu),
+                                   shard_of(status, o, 1), shard_of(iters, o, 1), shard_of(Yhat0, o, d.nY));
         if (rc) return rc;
-        rc = mpcqp_step_device(h, (const double*)h->s_x.p, (const double*)h->s_lu.p, (const double*)h->s_ry.p,
-                               Ru ? (const double*)h->s_ru.p : nullptr,
-                               d.nd > 0 ? (const double*)h->s_d0.p : nullptr,
-                               d.nd > 0 ? (const double*)h->s_dh.p : nullptr, (double*)h->s_Z.p,
-                               (double*)h->s_u0.p, (int32_t*)h->s_st.p, (int32_t*)h->s_it.p,
-                               Yhat0 ? (double*)h->s_yh.p : nullptr, h->stream);
-        if (rc) return rc;
-        // the gather: each shard's results into its slice of the caller's arrays
-        HIPCHK(hipMemcpyAsync(shard_of(Ztilde, o, d.nZ), h->s_Z.p, B * d.nZ * sz, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(shard_of(u0, o, d.nu), h->s_u0.p, B * d.nu * sz, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(shard_of(status, o, 1), h->s_st.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (iters) HIPCHK(hipMemcpyAsync(shard_of(iters, o, 1), h->s_it.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if (Yhat0) HIPCHK(hipMemcpyAsync(shard_of(Yhat0, o, d.nY), h->s_yh.p, B * d.nY * sz, hipMemcpyDeviceToHost, h->stream));
     }
     // phase 2: wait for every device
     for (mpcqp_handle h : mh->h) {
