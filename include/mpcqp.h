@@ -294,7 +294,25 @@ int mpcqp_recondense_device(mpcqp_handle h, void* stream);
 #define MPCQP_GET_MODEL_BD   19
 #define MPCQP_GET_MODEL_DD   20
 #define MPCQP_GET_MODEL_DOP  21
+/* the remaining prediction tables of K1 (init_predmat, transcription.jl:115-194), as they lie on the device (row-major inside a
+ * member unless said otherwise).  MPCQP_ERR_UNSUPPORTED on a handle whose problem only the stage-structured kernel takes
+ * (nothing is condensed); MPCQP_ERR_ORDER before mpcqp_set_model and -- the last four -- while the terminal tables are not
+ * built (they are built with the first finite x̂ bound of mpcqp_set_bounds); MPCQP_ERR_ARG for GDTAB / XDTAB when nd = 0.
+ *   GDTAB  [B][Hp][ny][nd]   block t = Ĉ Â^t B̂d          (G, and J below its diagonal: transcription.jl:172-179)
+ *   XDTAB  [B][Hp][nx̂][nd]   block t = Â^t B̂d            (gx̂ = block Hp-1, jx̂ block j = block Hp-j-1: transcription.jl:167, 180)
+ *   EXHAT  [B][Hc][nx̂][nu]   block j = S(Hp - j_j - 1) B̂u, j_j the first step of move-blocking interval j (transcription.jl:164)
+ *   KXHAT  [B] nx̂ x nx̂ column-major   Â^Hp              (transcription.jl:142)
+ *   BXHAT  [B][nx̂]           S(Hp-1)(f̂op - x̂op), zeros when none is set      (transcription.jl:191) */
+#define MPCQP_GET_GDTAB      22
+#define MPCQP_GET_XDTAB      23
+#define MPCQP_GET_EXHAT      24
+#define MPCQP_GET_KXHAT      25
+#define MPCQP_GET_BXHAT      26
 int mpcqp_get(mpcqp_handle h, int which, double* out);
+/* Which form of K1 builds this handle's prediction tables in this process: 0 the LDS loops, 1 the chains of
+ * v_mfma_f64_16x16x4 (nx̂ <= 16, ny <= 16, nu + 1 + nd <= 16 and nx̂ >= MPCQP_K1_MFMA_MIN_NX, default 10; the environment
+ * variable of that name, read once, moves the threshold).  Both forms write the same tables. */
+int mpcqp_predmat_form(mpcqp_handle h);
 
 /* ---- LinModel(sys, Ts) and augment_model for the whole batch, on the device --------------------------------------------
  * What the reference does on the host before LinMPC(model) exists: LinModel(sys, Ts) (src/model/linmodel.jl:165-198) turns a

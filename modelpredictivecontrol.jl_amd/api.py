@@ -37,6 +37,7 @@ GET_KF_COV, GET_KF_GAIN = 10, 11
 GET_EXPLICIT_LAW = 12
 GET_IM_XS, GET_IM_YS, GET_IM_YHATS = 13, 14, 15
 GET_MODEL_AHAT, GET_MODEL_BU, GET_MODEL_C, GET_MODEL_BD, GET_MODEL_DD, GET_MODEL_DOP = 16, 17, 18, 19, 20, 21
+GET_GDTAB, GET_XDTAB, GET_EXHAT, GET_KXHAT, GET_BXHAT = 22, 23, 24, 25, 26      # K1's remaining tables, device layouts
 C2D_TUSTIN, C2D_ZOH = 0, 1                       # mpcqp_c2d_spec.d_method
 C2D_OK, C2D_REFUSED = 0, 2                       # per-member status of mpcqp_c2d / mpcqp_set_model_continuous
 IM_STATUS_OK, IM_STATUS_SINGULAR = 0, 2          # mpcqp_im_status
@@ -61,7 +62,7 @@ EXPORTS = ("mpcqp_version", "mpcqp_strerror", "mpcqp_last_hip_error", "mpcqp_cre
            "mpcqp_set_model_continuous", "mpcqp_set_model_continuous_device",
            "mpcqp_im_set", "mpcqp_im_status", "mpcqp_im_correct", "mpcqp_im_correct_device", "mpcqp_im_update", "mpcqp_im_update_device",
            "mpcqp_set_output_weight_blocks", "mpcqp_set_dense_weights", "mpcqp_set_custom_constraints", "mpcqp_set_custom_bounds",
-           "mpcqp_set_flags", "mpcqp_set_iteration_limit", "mpcqp_set_transcription", "mpcqp_transcription_supported", "mpcqp_set_current_setpoint", "mpcqp_prepare", "mpcqp_kernel_kind", "mpcqp_lds_bytes", "mpcqp_row_groups", "mpcqp_step_consts_builds", "mpcqp_prebuild",
+           "mpcqp_set_flags", "mpcqp_set_iteration_limit", "mpcqp_set_transcription", "mpcqp_transcription_supported", "mpcqp_set_current_setpoint", "mpcqp_prepare", "mpcqp_kernel_kind", "mpcqp_predmat_form", "mpcqp_lds_bytes", "mpcqp_row_groups", "mpcqp_step_consts_builds", "mpcqp_prebuild",
            "mpcqp_last_build_error", "mpcqp_multi_create", "mpcqp_multi_destroy", "mpcqp_multi_ndev",
            "mpcqp_multi_handle", "mpcqp_multi_shard", "mpcqp_multi_set_model", "mpcqp_multi_set_weights",
            "mpcqp_multi_set_bounds", "mpcqp_multi_prepare", "mpcqp_multi_step", "mpcqp_multi_gather_device",
@@ -267,6 +268,7 @@ def load_library(path: str | None = None):
         lib.mpcqp_set_model_continuous_device.argtypes = [C.c_void_p, C.POINTER(C2dSpec), C.POINTER(C2dIn), C.c_void_p, C.c_void_p]
     lib.mpcqp_prepare.argtypes = [C.c_void_p]
     lib.mpcqp_kernel_kind.argtypes = [C.c_void_p]
+    lib.mpcqp_predmat_form.argtypes = [C.c_void_p]
     lib.mpcqp_lds_bytes.argtypes = [C.c_void_p]
     lib.mpcqp_step_consts_builds.argtypes = [C.c_void_p]
     lib.mpcqp_row_groups.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
@@ -618,6 +620,10 @@ class Handle:
     def kernel_kind(self):
         return self.lib.mpcqp_kernel_kind(self.h)
 
+    def predmat_form(self):
+        """Which form of K1 builds this handle's prediction tables in this process: 0 the LDS loops, 1 the matrix cores."""
+        return self.lib.mpcqp_predmat_form(self.h)
+
     def step_consts_builds(self):
         """How often the handle has built its block of step constants (0: the steps form the values themselves)."""
         return self.lib.mpcqp_step_consts_builds(self.h)
@@ -816,7 +822,10 @@ class Handle:
                  GET_XHAT_MS: (self.B, self.Hp, self.nxhat), GET_MS_DEFECT: (self.B,),
                  GET_EXPLICIT_LAW: (self.B, 1 + self.nxhat + self.nu + self.ny + self.nd, self.nZ),
                  GET_KF_COV: (self.B, self.nxhat, self.nxhat), GET_KF_GAIN: (self.B, getattr(self, "nym", 0), self.nxhat),
-                 GET_IM_XS: (self.B, getattr(self, "nxs", 0)), GET_IM_YS: (self.B, self.ny), GET_IM_YHATS: (self.B, self.nY)}[which]
+                 GET_IM_XS: (self.B, getattr(self, "nxs", 0)), GET_IM_YS: (self.B, self.ny), GET_IM_YHATS: (self.B, self.nY),
+                 GET_GDTAB: (self.B, self.Hp, self.ny, self.nd), GET_XDTAB: (self.B, self.Hp, self.nxhat, self.nd),
+                 GET_EXHAT: (self.B, self.Hc, self.nxhat, self.nu), GET_KXHAT: (self.B, self.nxhat, self.nxhat),
+                 GET_BXHAT: (self.B, self.nxhat)}[which]
         out = np.empty(shape)
         _chk(self.lib, self.lib.mpcqp_get(self.h, which, _ptr(out)))
         return out

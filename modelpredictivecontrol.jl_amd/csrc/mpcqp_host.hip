@@ -1376,6 +1376,16 @@ int mpcqp_get(mpcqp_handle h, int which, double* out) {
             }
             return plain(0, src, n);
         }
+        // K1's remaining tables, in their device layouts; the terminal ones exist once a finite x̂ bound had them built
+        case MPCQP_GET_GDTAB: return plain(no_tables ? no_tables : d.nd == 0 ? MPCQP_ERR_ARG : 0, h->m.Gdtab, (size_t)d.Hp * d.ny * d.nd);
+        case MPCQP_GET_XDTAB: case MPCQP_GET_EXHAT: case MPCQP_GET_KXHAT: case MPCQP_GET_BXHAT: {
+            if (no_tables) return no_tables;
+            if (!h->terminal_built) return MPCQP_ERR_ORDER;
+            if (which == MPCQP_GET_XDTAB) return plain(d.nd == 0 ? MPCQP_ERR_ARG : 0, h->m.Xdtab, (size_t)d.Hp * d.nxh * d.nd);
+            if (which == MPCQP_GET_EXHAT) return plain(0, h->m.exT, (size_t)d.Hc * d.nxh * d.nu);
+            if (which == MPCQP_GET_KXHAT) return plain(0, h->m.kxT, (size_t)d.nxh * d.nxh);
+            return plain(0, h->m.bxv, d.nxh);
+        }
 #ifdef MPCQP_PROFILE
         case 99:    /* per-phase cycle counters of profiling builds (-DMPCQP_PROFILE): (16,B) */
             return plain(h->prof.p ? 0 : MPCQP_ERR_ORDER, h->prof.p, 16);
@@ -2476,6 +2486,11 @@ int mpcqp_kernel_kind(mpcqp_handle h) {
     if (!h) return MPCQP_ERR_NULL;
     if (uses_stage_kernel(h)) return ms_unsupported(h) ? MPCQP_ERR_UNSUPPORTED : MPCQP_KERNEL_MS;
     return step_kernel_kind(h->d, h->m);
+}
+
+int mpcqp_predmat_form(mpcqp_handle h) {
+    if (!h) return MPCQP_ERR_NULL;
+    return predmat_form_is_mfma(h->d) ? 1 : 0;
 }
 
 int mpcqp_step_consts_builds(mpcqp_handle h) {

@@ -33,7 +33,7 @@ namespace mpcqp {
 #ifndef MPCQP_K1_MFMA_MIN_NX
 #define MPCQP_K1_MFMA_MIN_NX 10   // below, the 16-wide tiles are mostly padding and the LDS loops are faster (C2, nx̂ = 6: 0.55 vs 0.66 ms)
 #endif
-static bool predmat_on_mfma(const Dims& d) {
+bool predmat_on_mfma(const Dims& d) {
     static const int min_nx = [] {          // (MPCQP_K1_MFMA_MIN_NX=1 in the environment: every eligible shape, for the tests)
         const char* e = getenv("MPCQP_K1_MFMA_MIN_NX");
         return e && atoi(e) > 0 ? atoi(e) : MPCQP_K1_MFMA_MIN_NX;

@@ -9,6 +9,11 @@
 
 namespace mpcqp {
 hipError_t launch_predmat(const Dims& d, const Model& m, bool terminal, hipStream_t st);
+// The form launch_predmat takes for these dimensions: the matrix-core chains, else the LDS loops.  WEAK declaration, as
+// launch_step_consts below: predmat_mfma is device code, so a library linked without it (the CPU emulator of tests/emu, whose
+// launch_predmat has the LDS loops only) defines nothing here and reports the LDS loops.
+__attribute__((weak)) bool predmat_on_mfma(const Dims& d);
+inline bool predmat_form_is_mfma(const Dims& d) { return predmat_on_mfma != nullptr && predmat_on_mfma(d); }
 hipError_t launch_hessian(const Dims& d, const Model& m, hipStream_t st);
 hipError_t launch_step(const Dims& d, const Model& m, const StepIO& io, hipStream_t st);
 hipError_t launch_step_spec_or_aot(const Dims& d, const Model& m, const StepIO& io, hipStream_t st);   // never the small-problem kernel

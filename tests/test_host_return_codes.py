@@ -5,7 +5,9 @@ entry point (which refusal wins) and which estimator sits behind the handle afte
 library as it stood before the estimator kind became one field (`python -m tests.test_host_return_codes` prints the table
 of the library at hand), and a change of the host code that moves one entry fails here.  The CPU test runs on tests/emu/libmpcqp_emu_all.so
 (tests/emu/all.mk: every launcher that csrc/*_launch.h declares weak is present, so nothing answers MPCQP_ERR_UNSUPPORTED for
-want of one), the `gpu` twin runs the same calls on the product library; both read the same table."""
+want of one), the `gpu` twin runs the same calls on the product library; both read the same table.  The read-back of K1's
+remaining tables (MPCQP_GET_GDTAB .. MPCQP_GET_BXHAT) and mpcqp_predmat_form have a table of their own, EXPECTED_K1, written
+from the header's contract and keyed by nd, since Gd and Xd answer MPCQP_ERR_ARG without a measured disturbance."""
 import ctypes as C
 import os
 import subprocess
@@ -311,9 +313,37 @@ def arguments(lib, nd):
     r.close()
     # every `which` of mpcqp_get on a fresh handle
     r = Rig(lib, nd, model=False, weights=False)
-    out["get on a fresh handle"] = {str(w): r.lib.mpcqp_get(r.h, w, p(r.big)) for w in range(0, 24)}
+    out["get on a fresh handle"] = {str(w): r.lib.mpcqp_get(r.h, w, p(r.big)) for w in range(0, 30)}
     out["get on a fresh handle"]["out=NULL"] = r.lib.mpcqp_get(r.h, 1, None)
     r.close()
+    return out
+
+
+K1_GETS = {"gdtab": 22, "xdtab": 23, "exhat": 24, "kxhat": 25, "bxhat": 26}
+
+
+def k1_tables(lib, nd):
+    """mpcqp_get of K1's remaining tables and mpcqp_predmat_form: before the model, with it, once a finite x̂ bound had the
+    terminal tables built, and on a handle that only the stage-structured kernel takes (nZ̃ = 300: nothing is condensed)"""
+    out = {}
+    r = Rig(lib, nd, model=False, weights=False)
+    gets = lambda h: {name: r.lib.mpcqp_get(h, which, p(r.big)) for name, which in K1_GETS.items()}
+    out["before the model"] = gets(r.h)
+    assert r.set_model() == 0 and r.set_weights() == 0
+    out["model"] = gets(r.h)
+    b, x0max = mpcqp.api.Bounds(), np.full((B, NX), 50.0)
+    b.x0max = x0max.ctypes.data_as(C.POINTER(C.c_double))
+    out["model"]["set_bounds(x0max)"] = r.lib.mpcqp_set_bounds(r.h, C.byref(b))
+    out["terminal tables built"] = gets(r.h)
+    out["terminal tables built"]["set_model"] = r.set_model()
+    out["after another set_model"] = gets(r.h)
+    out["predmat_form"] = {"h=NULL": r.lib.mpcqp_predmat_form(None), "tiny handle": r.lib.mpcqp_predmat_form(r.h)}
+    r.close()
+    h = C.c_void_p()
+    dims = mpcqp.api.Dims(B, NX, NU, NY, nd, 300, 300, None, 0, 0, 0, 0, 0.0, 0.0, 0.0)
+    assert lib.mpcqp_create(C.byref(dims), C.byref(h)) == 0
+    out["stage-only handle"] = gets(h)
+    lib.mpcqp_destroy(h)
     return out
 
 
@@ -358,6 +388,31 @@ def check(lib, kind):
         want = {k: v for k, v in EXPECTED.items() if nd or k != "states without d0"}     # (no measured disturbance: d0 is NULL anyway)
         wrong = compare(record(lib, nd), want, kind, "nd=%d" % nd)
         assert not wrong, "\n".join(wrong)
+        wrong = compare(k1_tables(lib, nd), EXPECTED_K1[nd], kind, "K1 tables, nd=%d" % nd)
+        assert not wrong, "\n".join(wrong)
+
+
+# K1's remaining tables (MPCQP_GET_GDTAB .. MPCQP_GET_BXHAT) and mpcqp_predmat_form, written from the contract in
+# include/mpcqp.h: MPCQP_ERR_UNSUPPORTED (-4) on a stage-only handle, MPCQP_ERR_ORDER (-5) without a model and -- the terminal
+# tables -- before a finite x̂ bound had them built, MPCQP_ERR_ARG (-3) for Gd / Xd when nd = 0.  Keyed by nd.
+EXPECTED_K1 = {
+    0: {
+        'before the model': {'gdtab': -5, 'xdtab': -5, 'exhat': -5, 'kxhat': -5, 'bxhat': -5},
+        'model': {'gdtab': -3, 'xdtab': -5, 'exhat': -5, 'kxhat': -5, 'bxhat': -5, 'set_bounds(x0max)': 0},
+        'terminal tables built': {'gdtab': -3, 'xdtab': -3, 'exhat': 0, 'kxhat': 0, 'bxhat': 0, 'set_model': 0},
+        'after another set_model': {'gdtab': -3, 'xdtab': -3, 'exhat': 0, 'kxhat': 0, 'bxhat': 0},
+        'predmat_form': {'h=NULL': -1, 'tiny handle': 0},
+        'stage-only handle': {'gdtab': -4, 'xdtab': -4, 'exhat': -4, 'kxhat': -4, 'bxhat': -4},
+    },
+    1: {
+        'before the model': {'gdtab': -5, 'xdtab': -5, 'exhat': -5, 'kxhat': -5, 'bxhat': -5},
+        'model': {'gdtab': 0, 'xdtab': -5, 'exhat': -5, 'kxhat': -5, 'bxhat': -5, 'set_bounds(x0max)': 0},
+        'terminal tables built': {'gdtab': 0, 'xdtab': 0, 'exhat': 0, 'kxhat': 0, 'bxhat': 0, 'set_model': 0},
+        'after another set_model': {'gdtab': 0, 'xdtab': 0, 'exhat': 0, 'kxhat': 0, 'bxhat': 0},
+        'predmat_form': {'h=NULL': -1, 'tiny handle': 0},
+        'stage-only handle': {'gdtab': -4, 'xdtab': -4, 'exhat': -4, 'kxhat': -4, 'bxhat': -4},
+    },
+}
 
 
 # Recorded on the emulator from csrc/mpcqp_host.hip as it stood with six estimator flags in the handle.  The codes are the same
@@ -475,7 +530,7 @@ EXPECTED = {
         'before explicit_prepare': {'step': 0, 'explicit_step': -5, 'explicit_status': -5, 'explicit_status(out=NULL)': -1, 'set_output_weight_blocks': 0, 'set_dense_weights': 0, 'set_custom_bounds': -5, 'explicit_prepare(2)': -3, 'next': 0},
         'prepared': {'step': 0, 'explicit_step': 0, 'explicit_status': 0, 'explicit_status(out=NULL)': -1, 'next': 0, 'im_set': -4, 'after: im_status': -5},
         'custom rows': {'set_custom_bounds before the constraints': -5, 'im_set': 0, 'set_custom_constraints on an InternalModel': -4, 'kf_set': 0, 'set_custom_constraints': 0, 'set_custom_bounds': 0, 'set_custom_bounds(C_wmin without a slack)': -3, 'im_set with custom rows': -4, 'after: get_gain': 0, 'step': 0},
-        'get on a fresh handle': {'0': -3, '1': -5, '2': -5, '3': -5, '4': -5, '5': -5, '6': -5, '7': -5, '8': -5, '9': -5, '10': -5, '11': -5, '12': -5, '13': -5, '14': -5, '15': -5, '16': -5, '17': -5, '18': -5, '19': -5, '20': -5, '21': -5, '22': -3, '23': -3, 'out=NULL': -1},
+        'get on a fresh handle': {'0': -3, '1': -5, '2': -5, '3': -5, '4': -5, '5': -5, '6': -5, '7': -5, '8': -5, '9': -5, '10': -5, '11': -5, '12': -5, '13': -5, '14': -5, '15': -5, '16': -5, '17': -5, '18': -5, '19': -5, '20': -5, '21': -5, '22': -5, '23': -5, '24': -5, '25': -5, '26': -5, '27': -3, '28': -3, '29': -3, 'out=NULL': -1},
     },
 }
 
