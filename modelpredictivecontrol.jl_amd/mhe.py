@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import api
-from .api import MpcqpError, _chk, _f64, _ptr, colmajor
+from .api import MpcqpError, _addr, _chk, _f64, _ptr, colmajor
 
 EXPORTS = ("mpcqp_mhe_create", "mpcqp_mhe_destroy", "mpcqp_mhe_set_model", "mpcqp_mhe_set_bounds", "mpcqp_mhe_set_bounds_window", "mpcqp_mhe_set_softness", "mpcqp_mhe_set_softness_window", "mpcqp_mhe_init", "mpcqp_mhe_set_state", "mpcqp_mhe_shift_windows",
            "mpcqp_mhe_prepare", "mpcqp_mhe_update", "mpcqp_mhe_prepare_device", "mpcqp_mhe_update_device",
@@ -153,16 +153,13 @@ class MheHandle:
 
     def prepare_stream(self, y0m, d0=0, stream=0):
         """mpcqp_mhe_prepare_stream: device addresses, asynchronous on `stream` (0: the default stream)."""
-        v = lambda p: C.c_void_p(int(p)) if p else None
-        _chk(self.lib, self.lib.mpcqp_mhe_prepare_stream(self._h, v(y0m), v(d0), v(stream)))
+        _chk(self.lib, self.lib.mpcqp_mhe_prepare_stream(self._h, _addr(y0m), _addr(d0), _addr(stream)))
 
     def update_stream(self, u0, y0m=0, d0=0, stream=0):
-        v = lambda p: C.c_void_p(int(p)) if p else None
-        _chk(self.lib, self.lib.mpcqp_mhe_update_stream(self._h, v(u0), v(y0m), v(d0), v(stream)))
+        _chk(self.lib, self.lib.mpcqp_mhe_update_stream(self._h, _addr(u0), _addr(y0m), _addr(d0), _addr(stream)))
 
     def set_state_stream(self, xhat0, stream=0):
-        v = lambda p: C.c_void_p(int(p)) if p else None
-        _chk(self.lib, self.lib.mpcqp_mhe_set_state_stream(self._h, v(xhat0), v(stream)))
+        _chk(self.lib, self.lib.mpcqp_mhe_set_state_stream(self._h, _addr(xhat0), _addr(stream)))
 
     def dims(self):
         out = MheDims()

@@ -46,7 +46,7 @@ def solve(nxh, B, semidefinite, run=None):
     hd.kf_set_steady(Q, R, np.arange(ny))
     med, mn = kt.timed(lambda sp: hd.kf_solve_steady_device(stream=sp))
     it, st = hd.kf_steady_iters(), hd.kf_status()
-    path = hd.kf_steady_path() if hasattr(hd, "kf_steady_path") else np.zeros(B, np.int32)
+    path = hd.kf_steady_path() if hasattr(hd.lib, "mpcqp_kf_steady_path") else np.zeros(B, np.int32)
     refused_with_gain = int((hd.kf_gain().any(axis=(1, 2)) & (st != 0)).sum())      # must be 0: a status never comes with a gain
     nK = min(B, 64)                                             # the result is the host's, on a sample
     K = mpcqp.steady_kalman_gain(A[:nK], C[:nK], Q[:nK], R[:nK])

@@ -154,7 +154,7 @@ def test_mirror_validates_like_the_reference():
     assert mpc.kf_timevarying and mpc.xhat0.shape == (2, 3) and Recorder.calls[0][0].shape == (2, 3, 3)
     mpc.setstate([0.0, 1.0, 2.0], Phat=np.eye(3))
     assert Recorder.calls[-1][0] == "P" and mpc.xhat0[1].tolist() == [0.0, 1.0, 2.0]
-    mpc.kf_timevarying = False
+    mpc.est_kind = mpcqp.controller.EST_STEADY
     with pytest.raises(ValueError, match="no covariance"):
         mpc.setstate([0.0, 1.0, 2.0], Phat=np.eye(3))
 

@@ -98,10 +98,13 @@ def test_library_without_the_second_pass_keeps_status_2():
 
 
 def test_mirror_without_the_entry_point_keeps_todays_getinfo():
-    """A handle without kf_steady_path (an older build of the library): Handle raises AttributeError, nothing else changes."""
+    """A library without mpcqp_kf_steady_path (an older build): the Handle methods raise NotImplementedError naming the entry
+    point, like every other optional one."""
     h = mpcqp.api.Handle.__new__(mpcqp.api.Handle)
     h.lib = object()
-    assert not hasattr(h, "kf_steady_path") and not hasattr(h, "kf_set_steady")
+    for call, name in ((h.kf_steady_path, "mpcqp_kf_steady_path"), (lambda: h.kf_set_steady(None, None, [0]), "mpcqp_kf_set_steady")):
+        with pytest.raises(NotImplementedError, match="this library has no " + name):
+            call()
 
 
 def test_host_code_under_sanitizers(tmp_path):
