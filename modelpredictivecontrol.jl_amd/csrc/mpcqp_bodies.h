@@ -3132,23 +3132,15 @@ struct Step {
     // sweep over the panel's finished columns (up to 12 columns x 4 FMA chains per lane and block).
     template <int P, int Bk>
     __device__ __forceinline__ void chol_block_update() {
+        if constexpr (PHL) { chol_block_update_q4<P, Bk>(); return; }
         typedef double v4d_ __attribute__((ext_vector_type(4)));
         constexpr int n = DM::nZ, NT = (n + 15) / 16, K0 = 16 * P + 4 * Bk;
         const int li = w.lane & 15, lk = w.lane >> 4;
         double x[NT];
-        // PHL: every address below is ONE per-lane register (row li of tile 0, column lk of a block) plus an immediate; the
-        // clamped rows of a ragged last tile keep a second one
-        double* const xb = Phi + 4 * li + lk;
-        const int lrow = 16 * (NT - 1) + li < n ? 16 * (NT - 1) + li : n - 1;
-        const double* const xl = (n % 16 == 0) ? xb : Phi + 4 * lrow + lk - 64 * (NT - 1);
         MPCQP_UNROLL
         for (int T = P; T < NT; ++T) {
-            if constexpr (PHL) {
-                x[T] = (T == NT - 1 ? xl : xb)[coloff(K0) + 64 * T];
-            } else {
-                const int row = 16 * T + li < n ? 16 * T + li : n - 1;
-                x[T] = Phi[pk(row, 0) + K0 + lk];
-            }
+            const int row = 16 * T + li < n ? 16 * T + li : n - 1;
+            x[T] = Phi[pk(row, 0) + K0 + lk];
         }
         const double xPs = one_row_per_lane<DM>() ? x[P] * gt[K0 + lk] : x[P];   // (M D M': d of the block's columns, written by chol_static)
         double* const trash = sm + c.zero + 4;
@@ -3164,12 +3156,7 @@ struct Step {
             for (int r = Bk + 1; r < 4; ++r) {
                 if (16 * P + 4 * r >= n) continue;
                 const int row = 16 * T + li, col = 16 * P + 4 * r + lk;
-                if constexpr (PHL) {
-                    const bool ok = (16 * T + 15 < n || row < n) && (T > P || col <= row);
-                    q_[T][r] = ok ? xb + coloff(16 * P + 4 * r) + 64 * T : trash;
-                } else {
-                    q_[T][r] = (row < n && col <= row) ? Phi + pk(row, col) : trash;
-                }
+                q_[T][r] = (row < n && col <= row) ? Phi + pk(row, col) : trash;
                 old_[T][r] = *q_[T][r];
             }
         }
@@ -3181,6 +3168,71 @@ struct Step {
                 if (16 * P + 4 * r >= n) continue;
                 *q_[T][r] = old_[T][r] - acc[r];
             }
+        }
+        w.sync();
+    }
+
+    // The in-panel update of the column-block-major layout (PHL: one wavefront, one row per lane) on quarter tiles.  The
+    // 16x16x4 product above covers all 16 columns of the panel and keeps the blocks r > Bk: 3, 2 or 1 quarters of it.
+    // v_mfma_f64_4x4x4_4b (lane maps: EtDE_share_, B4) forms one 4-column block of a row tile per instruction, at a quarter
+    // of the matrix-pipe cycles:
+    //   A = X_T as loaded above: lane (li, lk) holds row block q = li >> 2, row i = li & 3, k = lk of tile T -- no move
+    //   B = d_k L[16P + 4r + j][K0 + k], j = li & 3, the same block in all four quads: one 8-byte read per later block r
+    //       from ONE per-lane base (row li & 3 of tile 0, column lk) plus an immediate; rows >= n of the matrix's last,
+    //       ragged block are clamped like the rows of a ragged last tile
+    //   D: lane 16 i + 4 q + j holds the update of entry (16T + 4q + i, 16P + 4r + j): one per-lane base plus an immediate
+    // Per entry still old - (the four products in the same k order on a zero accumulator).  Entries without a slot (above
+    // the diagonal in tile T = P, rows >= n) go to the trash slot; every old value is requested before the first
+    // matrix-core instruction and every write comes after (see above).  Block Bk + 1 -- all that the next chol_static
+    // block waits for -- is issued and written back first.
+    template <int P, int Bk>
+    __device__ __forceinline__ void chol_block_update_q4() {
+        static_assert(PHL, "quarter-tile update outside the column-block-major layout");
+        constexpr int n = DM::nZ, NT = (n + 15) / 16, K0 = 16 * P + 4 * Bk;
+        const int li = w.lane & 15, lk = w.lane >> 4, lq = li >> 2, lj = li & 3;
+        const double* const xb = Phi + 4 * li + lk;
+        const int lrow = 16 * (NT - 1) + li < n ? 16 * (NT - 1) + li : n - 1;
+        const double* const xl = (n % 16 == 0) ? xb : Phi + 4 * lrow + lk - 64 * (NT - 1);
+        const double* const bq = Phi + 4 * lj + lk;
+        double* const rb = Phi + 4 * (4 * lq + lk) + lj;
+        double x[NT], bs[4];
+        MPCQP_UNROLL
+        for (int T = P; T < NT; ++T) x[T] = (T == NT - 1 ? xl : xb)[coloff(K0) + 64 * T];
+        MPCQP_UNROLL
+        for (int r = Bk + 1; r < 4; ++r) {
+            const int c0 = 16 * P + 4 * r;
+            if (c0 >= n) continue;
+            if (c0 + 3 < n) {
+                bs[r] = bq[coloff(K0) + 4 * c0];
+            } else {
+                const int brow = c0 + lj < n ? c0 + lj : n - 1;
+                bs[r] = Phi[4 * brow + lk + coloff(K0)];
+            }
+        }
+        const double dk = gt[K0 + lk];                   // (M D M': d of the block's columns, written by chol_static)
+        double* const trash = sm + c.zero + 4;
+        double* q_[4][NT];
+        double old_[4][NT];
+        MPCQP_UNROLL
+        for (int r = Bk + 1; r < 4; ++r) {
+            if (16 * P + 4 * r >= n) continue;
+            MPCQP_UNROLL
+            for (int T = P; T < NT; ++T) {
+                const int row = 16 * T + 4 * lq + lk, col = 16 * P + 4 * r + lj;
+                const bool ok = (16 * T + 15 < n || row < n) && (T > P || col <= row);
+                q_[r][T] = ok ? rb + coloff(16 * P + 4 * r) + 64 * T : trash;
+                old_[r][T] = *q_[r][T];
+            }
+        }
+        MPCQP_UNROLL
+        for (int r = Bk + 1; r < 4; ++r) {
+            if (16 * P + 4 * r >= n) continue;
+            const double br = bs[r] * dk;
+            double acc[NT];
+            MPCQP_UNROLL
+            for (int T = P; T < NT; ++T) acc[T] = __builtin_amdgcn_mfma_f64_4x4x4f64(x[T], br, 0.0, 0, 0, 0);
+            MPCQP_UNROLL
+            for (int T = P; T < NT; ++T) *q_[r][T] = old_[r][T] - acc[T];
         }
         w.sync();
     }

@@ -42,7 +42,7 @@
 
 // Revision of the kernel sources / device structs: part of the name of cached on-demand
 // specialisations, so that objects built from older sources are never loaded.
-#define MPCQP_KERNEL_REV 19       // 19: the ragged last tile row of E'DE (nDU mod 16 = 4 or 8, nu = ny = 4, register operands) on v_mfma_f64_4x4x4_4b, its ϵ row left to the caller (EtDE_share_, B4); 18: E'w of the nu = ny = 4 one-wavefront kernels on the 16 x 4 lane map of the E'DE operands (Et_apply_share_, DevWave::swap32 / swap16); 17: the polish assembles Phi = H̃ (Model::Hpk) + rho G_A'G_A from the K steps of the working set only (add_GtDG<POL>, EtDE_share_ MK); 16: Phi of the one-row-per-lane kernels column-block-major in LDS (phi(), phi_layout()); 15: StepIO::kf_late (predictor-form placement of the fused correction), NaN rule of the estimator corrections; 14: one row per lane: a lane's own vector entries handed over in registers across the Newton solve (Step::lane_regs); 13: Model::stepc (per-handle step constants), one load phase for the set-up; 12: matrix-core operands of E'DE in registers (EtDE_add_mfma, register-operand form); 11: on-demand objects compiled with the pragma-unroll threshold lifted (no scratch arrays / flat accesses from eight tile rows on); 10: the row eps >= 0 rides in a Ŷ group (eps_host_group); 9: a blocked step (alpha < 1/2) no longer passes the last-step test; 8: MPCQP_FLAG_KEEP_ITERATE
+#define MPCQP_KERNEL_REV 20       // 20: in-panel update of the one-wavefront one-row-per-lane factorisation on v_mfma_f64_4x4x4_4b, one instruction per (row tile, later column block) (chol_block_update_q4); 19: the ragged last tile row of E'DE (nDU mod 16 = 4 or 8, nu = ny = 4, register operands) on v_mfma_f64_4x4x4_4b, its ϵ row left to the caller (EtDE_share_, B4); 18: E'w of the nu = ny = 4 one-wavefront kernels on the 16 x 4 lane map of the E'DE operands (Et_apply_share_, DevWave::swap32 / swap16); 17: the polish assembles Phi = H̃ (Model::Hpk) + rho G_A'G_A from the K steps of the working set only (add_GtDG<POL>, EtDE_share_ MK); 16: Phi of the one-row-per-lane kernels column-block-major in LDS (phi(), phi_layout()); 15: StepIO::kf_late (predictor-form placement of the fused correction), NaN rule of the estimator corrections; 14: one row per lane: a lane's own vector entries handed over in registers across the Newton solve (Step::lane_regs); 13: Model::stepc (per-handle step constants), one load phase for the set-up; 12: matrix-core operands of E'DE in registers (EtDE_add_mfma, register-operand form); 11: on-demand objects compiled with the pragma-unroll threshold lifted (no scratch arrays / flat accesses from eight tile rows on); 10: the row eps >= 0 rides in a Ŷ group (eps_host_group); 9: a blocked step (alpha < 1/2) no longer passes the last-step test; 8: MPCQP_FLAG_KEEP_ITERATE
 
 namespace mpcqp {
 
