@@ -499,7 +499,9 @@ int mpcqp_kf_update_device(mpcqp_handle h, double* xhat0, const double* u0, cons
  *          reference's cholesky! throws): P̂ and K̂ keep their values, and so does P̂ in the prediction of that period --
  *          only status 2 holds the covariance prediction back; the next correction that succeeds puts 0 back.
  * The other estimators of the batch and the LinMPC step statuses are unaffected.
- * mpcqp_kf_lanes_per_estimator: 0 on a gain from mpcqp_kf_set, else 16 (max(nx̂, nym) <= 16: four estimators per wavefront) or 64. */
+ * mpcqp_kf_lanes_per_estimator: 0 on a gain from mpcqp_kf_set, else 16 (max(nx̂, nym) <= 16: four estimators per wavefront) or 64;
+ * after mpcqp_kf_set_steady with 32 < max(nx̂, nym) <= 64: 64 T, T the wavefronts of the workgroup that held an estimator in
+ * the last solve (256 by default). */
 int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* Rhat, const double* P0,
                              const int32_t* i_ym, int32_t nym);
 int mpcqp_kf_set_state_covariance(mpcqp_handle h, const double* P);
@@ -519,11 +521,18 @@ int mpcqp_kf_lanes_per_estimator(mpcqp_handle h);
  * the same iteration (csrc/kf_dare_bodies.h, its square-root form: H(k) = L L' without pivoting, columns of pivots <= 0 dropped,
  * S = L (I + L'GL)⁻¹ L').  There a pivot of H(k) below -1e-8 max(1, max diag H(k)) is no rounding: an indefinite Q̂ keeps
  * status 2.  A build without the second pass (the kernel is missing) gives a semidefinite Q̂ status 2, as before.
+ * 32 < max(nx̂, nym) <= 64: the same iteration in its definite form with the operands in LDS, one estimator per workgroup
+ * of T wavefronts (csrc/kf_dare_lds_bodies.h; T = 4).  There is no second pass at this size: an estimator whose Q̂ is
+ * numerically singular by the rule above, semidefinite or indefinite gets status 2, and mpcqp_kf_steady_path answers 0
+ * for every estimator.  MPCQP_KF_DARE_TEAM = 1, 2 or 4 in the environment (read at every solve; any other value is
+ * ignored) picks another compiled T -- a test hook: the result is bit-identical for every T.
  *
  * mpcqp_kf_set_steady: Qhat (nx̂,nx̂,B), Rhat (nym,nym,B), i_ym [nym]: layouts, symmetry check (MPCQP_ERR_ARG) and i_ym
  * validation of mpcqp_kf_set_covariances.  Needs the model (MPCQP_ERR_ORDER).  Stores Q̂ and R̂, fills K̂, P̂∞ and the
- * status with zeros, and solves (host-synchronous).  max(nx̂, nym) > 32, or a build without the kernel:
- * MPCQP_ERR_UNSUPPORTED, and the handle keeps what it had.  In every other respect the handle is then one with a steady
+ * status with zeros, and solves (host-synchronous).  max(nx̂, nym) > 64, or a build without the kernel of that size (one
+ * without the LDS-resident kernels stops at 32): MPCQP_ERR_UNSUPPORTED, and the handle keeps what it had.  (Only this
+ * solve goes beyond 32: mpcqp_kf_set_covariances, mpcqp_kf_set_poles and mpcqp_est_initstate keep answering
+ * MPCQP_ERR_UNSUPPORTED there, and a steady handle of that size keeps its solved gain when they do.)  In every other respect the handle is then one with a steady
  * gain: no launch is added to a period, and mpcqp_kf_correct / _predict / _update / mpcqp_loop_device are those of
  * mpcqp_kf_set, in both forms of mpcqp_kf_set_direct.
  * mpcqp_kf_solve_steady / _solve_steady_device: solve again on the model resident now (host-synchronous / enqueued on
@@ -542,7 +551,7 @@ int mpcqp_kf_lanes_per_estimator(mpcqp_handle h);
  *                         the second pass refuses the estimator: a non-zero status never comes with a gain of that
  *                         solve; the rest of the batch is unaffected, bit for bit;
  *       MPCQP_GET_KF_COV  returns P̂∞;
- *       mpcqp_kf_lanes_per_estimator answers 16 or 64.
+ *       mpcqp_kf_lanes_per_estimator answers 16 or 64, beyond 32 states or measured outputs 64 T (256).
  * A later mpcqp_kf_set or mpcqp_kf_set_covariances leaves the mode: mpcqp_kf_solve_steady[_device],
  * mpcqp_kf_steady_iters and mpcqp_kf_steady_path then answer MPCQP_ERR_ORDER. */
 int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, const int32_t* i_ym, int32_t nym);

@@ -821,7 +821,9 @@ class Handle:
     def kf_set_steady(self, Qhat, Rhat, i_ym):
         """Qhat (B,nx̂,nx̂) symmetric positive semidefinite, Rhat (B,nym,nym) symmetric positive definite.  Solves the Riccati
         equation of every member on the resident model; kf_gain() / kf_covariance() / kf_status() / kf_steady_iters() read
-        the result back."""
+        the result back.  max(nx̂, nym) <= 64 (-4 beyond); above 32 the operands of the solve live in LDS, one member per
+        workgroup (csrc/kf_dare_lds_bodies.h), Q̂ has to be positive definite (status 2 otherwise), and kf_set_covariances,
+        kf_set_poles and est_initstate still answer -4 on such a handle, which keeps its solved gain."""
         fn = self._need("mpcqp_kf_set_steady")
         iy = np.ascontiguousarray(i_ym, dtype=np.int32)
         _chk(self.lib, fn(self.h, _ptr(colmajor(Qhat)), _ptr(colmajor(Rhat)), _ptr(iy), int(iy.size)))
@@ -884,7 +886,8 @@ class Handle:
         return self._read_i32(self.lib.mpcqp_kf_status)
 
     def kf_lanes_per_estimator(self):
-        """0 on a steady gain; 16 / 64 lanes per estimator of the covariance kernel otherwise."""
+        """0 on a steady gain; 16 / 64 lanes per estimator of the covariance kernel otherwise; 256 (a workgroup of four
+        wavefronts) after kf_set_steady beyond 32 states or measured outputs."""
         n = self.lib.mpcqp_kf_lanes_per_estimator(self.h)
         if n < 0:
             _chk(self.lib, n)

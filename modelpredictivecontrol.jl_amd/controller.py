@@ -498,7 +498,9 @@ class BatchLinMPC:
 
         `steady=dict(Qhat=…, Rhat=…)` is the SteadyKalmanFilter as the reference constructs it, from Q̂ and R̂ (kalman.jl:205-222):
         the steady-state gain of every member is solved for on the device (R̂ positive definite, Q̂ positive semidefinite,
-        max(nx̂, nym) <= 32; `getinfo()["kf_steady_path"]` tells which form of the iteration served a member), and `setmodel`
+        max(nx̂, nym) <= 64; `getinfo()["kf_steady_path"]` tells which form of the iteration served a member; beyond 32 states
+        or measured outputs Q̂ has to be positive definite -- a semidefinite one gets `kf_status` 2 -- and `initstate`,
+        `covariances=` and `luenberger=` still stop at 32 there, with the error -4 they give today), and `setmodel`
         solves again on the new model --
         which the reference's SteadyKalmanFilter refuses.  Members whose equation has no solution (an undetectable pair) or
         whose solve broke down keep a zero gain and are counted in one RuntimeWarning; `getinfo` shows `kf_status`.

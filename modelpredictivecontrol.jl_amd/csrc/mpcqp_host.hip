@@ -17,6 +17,7 @@
 #include "im_launch.h"
 #include "kf_cov_launch.h"
 #include "kf_dare_launch.h"
+#include "kf_dare_lds_launch.h"
 #include "kf_place_launch.h"
 #include "mpcqp_hostutil.h"
 #include "mpcqp_launch.h"
@@ -94,6 +95,10 @@ struct mpcqp_handle_s {
     DBuf kf_it;
     DBuf kf_path;     // which body produced each estimator's result (kf_dare_launch.h: DareArgs::path)
     int kf_dare_waves = 0;
+    // 32 < max(nx̂, nym) <= 64: the solve runs on the LDS-resident kernels (kf_dare_lds_bodies.h), kf_NX is their padded
+    // order, kf_dare_waves their workgroups, kf_dare_team the wavefronts per estimator of the last solve
+    bool kf_dare_lds = false;
+    int kf_dare_team = 0;
     // Luenberger observer from its poles (EST_KF_PLACE): kf_K holds the gain the placement kernel (kf_place_bodies.h)
     // found, kf_st / kf_it its status and sweep count
     DBuf kf_poles;
@@ -1626,8 +1631,11 @@ int mpcqp_kf_set_covariances(mpcqp_handle h, const double* Qhat, const double* R
 // One Riccati solve of a handle in steady mode (kf_kernels.hip: k_kf_dare*) on the model that is resident now: the definite
 // body for the whole batch, then (a library that has it) the square-root body, which reads and factors every Q̂ and solves
 // again the estimators that the definite body left broken down or whose Q̂ is numerically singular (kf_dare_launch.h).
+// A handle beyond 32 states or measured outputs (kf_dare_lds): one launch of the LDS-resident kernel, which refuses such
+// estimators itself; path stays 0.  MPCQP_KF_DARE_TEAM = 1, 2, 4 picks another of its compiled teams (a test hook, read at
+// every solve; anything else is ignored).
 static int kf_dare_launch(mpcqp_handle h, hipStream_t st) {
-    if (!kf::kf_dare_available()) return MPCQP_ERR_UNSUPPORTED;
+    if (h->kf_dare_lds ? !kf::kf_dare_lds_available() : !kf::kf_dare_available()) return MPCQP_ERR_UNSUPPORTED;
     ON_DEVICE(h);
     const Dims& d = h->d;
     kf::DareArgs a{};
@@ -1639,6 +1647,12 @@ static int kf_dare_launch(mpcqp_handle h, hipStream_t st) {
     a.NX = h->kf_NX; a.nwaves = h->kf_dare_waves;
     a.path = (int32_t*)h->kf_path.p;
     HIPCHK(hipMemsetAsync(h->kf_path.p, 0, (size_t)d.B * sizeof(int32_t), st));
+    if (h->kf_dare_lds) {
+        const char* e = getenv("MPCQP_KF_DARE_TEAM");
+        h->kf_dare_team = kf::kf_dare_lds_team_for(e ? atoi(e) : 0);
+        HIPCHK(kf::launch_kf_dare_lds(a, h->kf_dare_team, st));
+        return MPCQP_OK;
+    }
     HIPCHK(kf::launch_kf_dare(a, st));
     if (kf::kf_dare_psd_available()) HIPCHK(kf::launch_kf_dare_psd(a, st));
     return MPCQP_OK;
@@ -1649,7 +1663,9 @@ int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, 
     const Dims& d = h->d;
     if (nym < 1 || nym > d.ny) return MPCQP_ERR_DIMS;
     { int rc = check_iym(d, i_ym, nym); if (rc) return rc; }
-    if (std::max(d.nxh, (int)nym) > mhe::NX_MAX || !kf::kf_dare_available()) return MPCQP_ERR_UNSUPPORTED;
+    const int nmax = std::max(d.nxh, (int)nym);
+    const bool lds = nmax > mhe::NX_MAX;              // beyond the row-lane kernels: operands in LDS, up to DARE_LDS_NMAX
+    if (lds ? nmax > kf::DARE_LDS_NMAX || !kf::kf_dare_lds_available() : !kf::kf_dare_available()) return MPCQP_ERR_UNSUPPORTED;
     const size_t B = d.B, nn = (size_t)d.nxh * d.nxh, nk = (size_t)d.nxh * nym, sz = sizeof(double);
     if (!kf_symmetric(Qhat, B, d.nxh) || !kf_symmetric(Rhat, B, nym)) return MPCQP_ERR_ARG;
     if (!h->have_model) return MPCQP_ERR_ORDER;
@@ -1667,8 +1683,10 @@ int mpcqp_kf_set_steady(mpcqp_handle h, const double* Qhat, const double* Rhat, 
     HIPCHK(hipMemsetAsync(h->kf_K.p, 0, B * nk * sz, h->stream));
     HIPCHK(hipMemsetAsync(h->kf_st.p, 0, B * sizeof(int32_t), h->stream));
     HIPCHK(hipMemsetAsync(h->kf_it.p, 0, B * sizeof(int32_t), h->stream));
-    h->kf_NX = kf::kf_cov_columns_for(std::max(d.nxh, (int)nym));
-    h->kf_dare_waves = kf::kf_dare_waves_for(h->device, d.B, h->kf_NX);
+    h->kf_dare_lds = lds;
+    h->kf_NX = lds ? kf::kf_dare_lds_order_for(nmax) : kf::kf_cov_columns_for(nmax);
+    h->kf_dare_waves = lds ? kf::kf_dare_lds_waves_for(h->device, d.B, h->kf_NX) : kf::kf_dare_waves_for(h->device, d.B, h->kf_NX);
+    h->kf_dare_team = lds ? kf::kf_dare_lds_team_for(0) : 0;
     adopt_estimator(h, EST_KF_STEADY, (const double*)h->kf_K.p, nym);
     return mpcqp_kf_solve_steady(h);
 }
@@ -1790,6 +1808,7 @@ int mpcqp_kf_status(mpcqp_handle h, int32_t* out) {
 int mpcqp_kf_lanes_per_estimator(mpcqp_handle h) {
     if (!h) return MPCQP_ERR_NULL;
     if (h->est == EST_KF_PLACE) return WAVE;       // (the placement: one member per wavefront at every size)
+    if (h->est == EST_KF_STEADY && h->kf_dare_lds) return WAVE * h->kf_dare_team;     // (a team of wavefronts per estimator)
     return est_has_cov(h) ? kf::kf_cov_lanes_for(h->kf_NX) : 0;
 }
 
