@@ -8,3 +8,12 @@
 #define MPCQP_SPECIALIZATIONS(X)        \
     X(2, 2, 6, 20, 5, 1, 0x0Fu)         \
     X(4, 4, 16, 30, 10, 1, 0x8Cu)
+
+// One visit of the list per library:  template <class F> static bool first_aot(F&& f) { MPCQP_SPECIALIZATIONS(MPCQP_AOT_TRY)
+// return false; }  calls f(AotEntry<SD>{}) with the StaticDims types of the entries in order and stops at the first call that
+// returns true.  MPCQP_AOT_TRY_NB: an entry for any move-blocking vector (the CPU emulator's extra shapes).
+namespace mpcqp {
+template <class SD> struct AotEntry { using type = SD; };
+}
+#define MPCQP_AOT_TRY(...) if (f(mpcqp::AotEntry<mpcqp::StaticDims<__VA_ARGS__, 1>>{})) return true;
+#define MPCQP_AOT_TRY_NB(...) if (f(mpcqp::AotEntry<mpcqp::StaticDims<__VA_ARGS__, 0>>{})) return true;

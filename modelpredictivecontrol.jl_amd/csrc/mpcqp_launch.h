@@ -6,6 +6,7 @@
 #include <string>
 
 #include "mpcqp_types.h"
+#include "spec_cache.h"
 
 namespace mpcqp {
 hipError_t launch_predmat(const Dims& d, const Model& m, bool terminal, hipStream_t st);
@@ -23,16 +24,12 @@ hipError_t launch_step_spec_or_aot(const Dims& d, const Model& m, const StepIO& 
 __attribute__((weak)) hipError_t launch_step_consts(const Dims& d, const Model& m, double* out, hipStream_t st);
 inline bool step_consts_available() { return launch_step_consts != nullptr; }
 size_t step_lds_bytes(const Dims& d);
-// kernel a step runs on: 0 runtime-dimension kernel, 1 ahead-of-time specialisation, 2 on-demand specialisation
+// kernel a step runs on: 0 runtime-dimension kernel, 1 ahead-of-time specialisation, 2 on-demand specialisation (spec_cache.h),
+// 3 the small-problem kernel
 int step_kernel_kind(const Dims& d, const Model& m);   // (m: the handle's arrays -- a block / dense M_Hp excludes the small-problem kernel)
 int step_kernel_kind_other(const Dims& d);   // ... of the steps the small-problem kernel (kind 3) does not take
 int prepare_step(const Dims& d, const Model& m, std::string* err);     // compile (if needed) + load; returns the kind
 int prebuild_step(const Dims& d, std::string* err);    // compile only; -1 on failure
-// one-time check of an on-demand kernel against the runtime-dimension kernel (see mpcqp_prepare)
-bool spec_verified(const Dims& d);
-bool spec_present(const Dims& d);      // an on-demand object of this shape is loaded / loadable (verified or not)
-void mark_spec_verified(const Dims& d);
-void reject_spec(const Dims& d);
 hipError_t launch_step_generic(const Dims& d, const Model& m, const StepIO& io, hipStream_t st);
 hipError_t launch_step_unverified_spec(const Dims& d, const Model& m, const StepIO& io, hipStream_t st);   // self-test only
 // Small problems (nZ~ <= 16; box, input-bound and -- nY <= 64 -- output-bound rows): four controllers per wavefront

@@ -1,7 +1,7 @@
 // mpcqp_spec.hip -- ONE specialisation of the step / Hessian kernels, compiled on demand by
 // libmpcqp.so for dimensions that are not in its ahead-of-time list (mpcqp_dispatch.h):
 //   hipcc --offload-arch=gfx950 -O3 -shared -fPIC -DMPCQP_SPEC_DIMS=NU,NY,NXH,HP,HC,NEPS,GMASK,DEFAULT_NB ...
-// The resulting object is dlopen'ed and cached next to the library (see jit_specialise()).
+// The resulting object is dlopen'ed and cached next to the library (spec_build() / spec_find() of spec_cache.cpp).
 #include <hip/hip_runtime.h>
 
 #include "mpcqp_bodies.h"

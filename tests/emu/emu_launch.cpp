@@ -10,14 +10,6 @@
 #include "mpcqp_dispatch.h"
 #include "mpcqp_launch.h"
 
-// specialisations of the small test problems of tests/test_abi_and_host.py, so that the
-// compile-time-dims code path (incl. move-blocking vectors and nd > 0) is exercised on the CPU too
-#define MPCQP_EMU_SPECIALIZATIONS(X) \
-    MPCQP_SPECIALIZATIONS(X)         \
-    XNB(1, 1, 3, 6, 3, 1, 0x09Fu)    \
-    XNB(1, 1, 3, 6, 3, 1, 0x39Fu)    \
-    XNB(1, 1, 3, 6, 3, 1, 0x08Cu)
-
 #define MPCQP_EMU_FIBER_IMPL        // (the context switch of emu_fiber.h is assembled in this unit)
 #include "emu_wave.h"
 
@@ -27,56 +19,41 @@ hipError_t launch_predmat(const Dims& d, const Model& m, bool terminal, hipStrea
     run_waves(d.B, predmat_lds_doubles(d), [&](EmuWave& w, int b, double* sm) { predmat_body(w, d, m, b, sm, terminal); });
     return hipSuccess;
 }
-hipError_t launch_hessian(const Dims& d, const Model& m, hipStream_t) {
+// the library's ahead-of-time list plus the small test problems of tests/test_abi_and_host.py, so that the
+// compile-time-dims code path (incl. move-blocking vectors and nd > 0) is exercised on the CPU too
+template <class F> static bool first_aot(F&& f) {
+    MPCQP_SPECIALIZATIONS(MPCQP_AOT_TRY)
+    MPCQP_AOT_TRY_NB(1, 1, 3, 6, 3, 1, 0x09Fu)
+    MPCQP_AOT_TRY_NB(1, 1, 3, 6, 3, 1, 0x39Fu)
+    MPCQP_AOT_TRY_NB(1, 1, 3, 6, 3, 1, 0x08Cu)
+    return false;
+}
+static bool generic_forced() {          // (the emulator reads it at every call)
     const char* fg = getenv("MPCQP_FORCE_GENERIC");
-    if (!(fg && fg[0] == '1') && !m.Mfull && !m.Ndense && !m.Ldense) {
-#define XNB(NU, NY, NXH, HP, HC, NEPS, GM) XX(NU, NY, NXH, HP, HC, NEPS, GM, 0)
-#define X(NU, NY, NXH, HP, HC, NEPS, GM) XX(NU, NY, NXH, HP, HC, NEPS, GM, 1)
-#define XX(NU, NY, NXH, HP, HC, NEPS, GM, NB)                                                  \
-        {                                                                                      \
-            using SD = StaticDims<NU, NY, NXH, HP, HC, NEPS, GM, NB>;                          \
-            if (SD::matches_dims(d)) {                                                         \
-                const SD sd(d);                                                                \
-                run_waves(d.B, make_carve(sd).total, [&](EmuWave& w, int b, double* sm) {      \
-                    hessian_body(w, sd, m, b, sm); });                                         \
-                return hipSuccess;                                                             \
-            }                                                                                  \
-        }
-        MPCQP_EMU_SPECIALIZATIONS(X)
-#undef X
-#undef XX
-#undef XNB
-    }
-    run_waves(d.B, make_carve(d).total, [&](EmuWave& w, int b, double* sm) { hessian_body(w, d, m, b, sm); });
+    return fg && fg[0] == '1';
+}
+// `body(w, dims, b, sm)` on every problem: with the first static shape that `matches` (where `aot` allows one), else with `d`
+template <class M, class Body> static hipError_t run_body(const Dims& d, bool aot, M matches, Body body) {
+    if (!aot || !first_aot([&](auto e) {
+            if (!matches(e)) return false;
+            const typename decltype(e)::type sd(d);
+            run_waves(d.B, make_carve(sd).total, [&](EmuWave& w, int b, double* sm) { body(w, sd, b, sm); });
+            return true;
+        }))
+        run_waves(d.B, make_carve(d).total, [&](EmuWave& w, int b, double* sm) { body(w, d, b, sm); });
     return hipSuccess;
 }
+hipError_t launch_hessian(const Dims& d, const Model& m, hipStream_t) {
+    return run_body(d, !generic_forced() && !m.Mfull && !m.Ndense && !m.Ldense, [&](auto e) { return decltype(e)::type::matches_dims(d); },
+                    [&](EmuWave& w, const auto& dm, int b, double* sm) { hessian_body(w, dm, m, b, sm); });
+}
 hipError_t launch_step(const Dims& d, const Model& m, const StepIO& io, hipStream_t st) {
-    const char* fg = getenv("MPCQP_FORCE_GENERIC");
-    if (!(fg && fg[0] == '1') && small_eligible(d, m, io)) return launch_step_small(d, m, io, st);
+    if (!generic_forced() && small_eligible(d, m, io)) return launch_step_small(d, m, io, st);
     return launch_step_spec_or_aot(d, m, io, st);
 }
 hipError_t launch_step_spec_or_aot(const Dims& d, const Model& m, const StepIO& io, hipStream_t) {
-    const char* fg = getenv("MPCQP_FORCE_GENERIC");
-    if (!(fg && fg[0] == '1') && !d.dense_w) {
-#define XNB(NU, NY, NXH, HP, HC, NEPS, GM) XX(NU, NY, NXH, HP, HC, NEPS, GM, 0)
-#define X(NU, NY, NXH, HP, HC, NEPS, GM) XX(NU, NY, NXH, HP, HC, NEPS, GM, 1)
-#define XX(NU, NY, NXH, HP, HC, NEPS, GM, NB)                                                  \
-        {                                                                                      \
-            using SD = StaticDims<NU, NY, NXH, HP, HC, NEPS, GM, NB>;                          \
-            if (SD::matches(d)) {                                                              \
-                const SD sd(d);                                                                \
-                run_waves(d.B, make_carve(sd).total, [&](EmuWave& w, int b, double* sm) {      \
-                    step_body(w, sd, m, io, b, sm); });                                        \
-                return hipSuccess;                                                             \
-            }                                                                                  \
-        }
-        MPCQP_EMU_SPECIALIZATIONS(X)
-#undef X
-#undef XX
-#undef XNB
-    }
-    run_waves(d.B, make_carve(d).total, [&](EmuWave& w, int b, double* sm) { step_body(w, d, m, io, b, sm); });
-    return hipSuccess;
+    return run_body(d, !generic_forced() && !d.dense_w, [&](auto e) { return decltype(e)::type::matches(d); },
+                    [&](EmuWave& w, const auto& dm, int b, double* sm) { step_body(w, dm, m, io, b, sm); });
 }
 hipError_t launch_kf_correct(const Dims& d, const Model& m, const KfParams& kf, double* xhat0,
                              const double* y0m, const double* d0, hipStream_t) {

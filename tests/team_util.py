@@ -123,7 +123,7 @@ def team_of_symbols(names):
 
 def find_cached_objects(pattern):
     """On-demand objects whose file name matches the glob `pattern` in the directories the library searches
-    (csrc/mpcqp_kernels.hip search_dirs: MPCQP_CACHE_DIR alone when set, else <library dir>/spec_cache and the user's cache)."""
+    (csrc/spec_cache.cpp search_dirs: MPCQP_CACHE_DIR alone when set, else <library dir>/spec_cache and the user's cache)."""
     if os.environ.get("MPCQP_CACHE_DIR"):
         dirs = [os.environ["MPCQP_CACHE_DIR"]]
     else:
